@@ -345,7 +345,7 @@ def write_model(model, path, batch=1, hw=224, precision="fp32", scales=None, ren
     V = lambda n: n if n == "data" else R(n) + "_out"                                        # noqa: E731 - a layer's output variable
     nodes, produced = [], {}            # produced: variable -> (node, readers)
     int8 = precision == "int8"
-    f9 = lambda x: float(np.float32(float("%.9g" % x)))      # noqa: E731 - the float a 9-digit decimal record becomes (the text model's route)
+    f32 = lambda x: float(np.float32(x))      # noqa: E731 - the float32 a scale / coefficient rounds to, once (the text model's records hold the same)
 
     def node(name, op, ins, outs, attrs, prec_of=None):
         # Graph::SetOpPrec is called for the node that carries the layer's name (and the Split behind it) - the BatchNorm / Scale / ReLU
@@ -387,7 +387,7 @@ def write_model(model, path, batch=1, hw=224, precision="fp32", scales=None, ren
         elif kd == "eltwise":
             relu = bool(l["relu"])
             c = 1.0 / scales[l["name"]] if int8 and scales else 1.0
-            node(nm, "Eltwise", [V(l["a"]), V(l["b"])], [nm + "_sum" if relu else V(l["name"])], {"type": "Add", "coeff": [f9(c)] * 2})
+            node(nm, "Eltwise", [V(l["a"]), V(l["b"])], [nm + "_sum" if relu else V(l["name"])], {"type": "Add", "coeff": [f32(c)] * 2})
             if relu:
                 node(nm + "_relu", "ReLU", [nm + "_sum"], [V(l["name"])], {"alpha": 0.0})
         elif kd == "fc":
@@ -410,7 +410,7 @@ def write_model(model, path, batch=1, hw=224, precision="fp32", scales=None, ren
             writer[v] = n["name"]
     layer_of_var = {V(l["name"]): l["name"] for l in spec}
     layer_of_var["data"] = "data"
-    var_scale = {v: f9(scales[layer_of_var[v]]) for v in layer_of_var if int8 and scales and calibration_in_file and layer_of_var[v] in scales}
+    var_scale = {v: f32(scales[layer_of_var[v]]) for v in layer_of_var if int8 and scales and calibration_in_file and layer_of_var[v] in scales}
     edges, outs = [], []           # (bottom node, top node, scale or None)
     for v, w in list(writer.items()):
         rd = readers.get(v, [])

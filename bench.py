@@ -10,7 +10,13 @@ stride-up shortcut poolings folded into a residual read). The unfused 76-op list
 (`reference_op_list`). Protocol mirrors the reference's (README.md:44, benchmark/CNN/run.sh): warm-up, then K timed
 iterations; images/s = batch * K / time.
 
-  python bench.py [--gpus N] [--steps K] [--warmup W] [--batch 8]
+  python bench.py [--gpus N] [--steps K] [--warmup W] [--batch 8] [--dump-outputs DIR] [--full]
+
+A plain run sets up, warms up, times the K steps and prints one JSON line (value, ms_per_step, config). --full adds everything
+else the bench measures: the per-step latency distribution, the roofline and per-kernel table, the batch-1 leg, passes in flight,
+the unfused reference list and the reference's own Net<MI355X> / Worker, Gemm<MI355X, float>, the CPU baseline and, with N > 1, the
+per-request exchange. --dump-outputs DIR writes the timed path's output of its last step (the softmax `prob` of every image of the
+global batch, float32) as DIR/prob.npy; inputs, weights and scales are seeded, so two builds can be compared output for output.
 
 N > 1: one rank per GPU under torch.distributed.run — started by the driver, or by this script itself when it is called
 plainly with --gpus N (it re-executes under torch.distributed.run on 127.0.0.1). The batch is sharded as independent
@@ -72,12 +78,12 @@ def parse():
     ap.add_argument("--compact-arena", type=int, default=0,
                     help="1: after kernel selection the net's arena is re-laid out with lifetime aliasing (saber_hip_net_compact_arena: what the "
                          "reference's MemoryScheduler does for a Net's edges; ResNet50 INT8 batch 8: 72.3 -> 24.5 MB); 0 (default): every edge keeps "
-                         "its own slot - measured 3 % FASTER single-stream (0.2152 vs 0.2216 ms, profiles/r06/compact_ab.txt); the multi-stream "
+                         "its own slot - measured 3 %% FASTER single-stream (0.2152 vs 0.2216 ms, profiles/r06/compact_ab.txt); the multi-stream "
                          "leg reports both forms")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-b1", action="store_true", help="skip the batch-1 latency leg")
     ap.add_argument("--cpu-seconds", type=float, default=15.0)
-    ap.add_argument("--per-op", action="store_true", help="print the per-op time table to stderr")
+    ap.add_argument("--per-op", action="store_true", help="print the per-op time table to stderr (needs --full)")
     ap.add_argument("--no-stem-pair", action="store_true",
                     help="INT8: conv1 + pool1 and the sibling pair reading pool1 stay two launches (saber_hip_net_optimize flag 512 off)")
     ap.add_argument("--head-pair", action="store_true",
@@ -89,7 +95,15 @@ def parse():
     ap.add_argument("--timed-only", action="store_true",
                     help="profiling aid: only warm-up + timed region (no latency / per-op / cpu legs), so the last "
                          "dispatches of a rocprofv3 trace are exactly one forward pass")
-    return ap.parse_args()
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline: latency distribution, roofline / per-kernel table, batch-1 leg, passes in flight, the reference "
+                         "op list and Net / Worker, Gemm, the CPU baseline, the per-request exchange (N > 1); off: the headline line only")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps write the output of the last step (the softmax `prob` of every image, float32) as DIR/prob.npy")
+    args = ap.parse_args()
+    if args.per_op and not args.full:
+        ap.error("--per-op is part of the --full measurements")
+    return args
 
 
 def build_net(W, model, scales, batch, args, stage=True, shared_device=False):
@@ -178,7 +192,8 @@ def respawn_under_torchrun(args):
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", str(args.gpus),
            "--master-addr", "127.0.0.1", "--master-port", str(port), os.path.abspath(__file__)] + sys.argv[1:]
     os.environ.setdefault("MASTER_ADDR", "127.0.0.1")
-    os.execv(sys.executable, cmd)
+    import subprocess
+    sys.exit(subprocess.call(cmd))     # a fresh child process; this one never touches the GPU
 
 
 def cpu_baseline_fp32(args, model):
@@ -225,10 +240,25 @@ def cpu_baseline_fp32(args, model):
                 "sample": "cpu baseline failed to run on this host"}
 
 
+def dump_outputs(d, prob, world, rank):
+    """the timed path's output after its last step: `prob` of this rank's images, all ranks' concatenated in rank order, as float32"""
+    import torch
+    torch.cuda.synchronize()
+    mine = prob.detach().float().cpu().numpy()
+    parts = [mine]
+    if world > 1:
+        import torch.distributed as dist
+        parts = [None] * world
+        dist.all_gather_object(parts, mine)
+    if rank == 0:
+        os.makedirs(d, exist_ok=True)
+        np.save(os.path.join(d, "prob.npy"), np.concatenate(parts, axis=0).astype(np.float32))
+
+
 def main():
     args = parse()
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
-        respawn_under_torchrun(args)          # does not return
+        respawn_under_torchrun(args)          # does not return: exits with the ranks' status
     import torch
     import torch.distributed as dist
     from anakin_amd import lib as L
@@ -361,7 +391,7 @@ def main():
     # split 8 ways pays when its answer must be complete before the next request starts; the headline amortises the exchange over
     # --gather-every steps (a request's logits then arrive up to that many steps late). Every rank takes part; reported beside it.
     per_request = None
-    if world > 1 and gather is not None and args.gather_every != 1:
+    if args.full and world > 1 and gather is not None and args.gather_every != 1:
         ag1 = shard.BatchedLogitGather(logits, world, every=1)
         n1 = max(20, min(args.steps, 200))
         timed_steps(net, 10, use_graph, lambda: ag1.step(logits), ag1.finish)
@@ -375,6 +405,9 @@ def main():
         per_request = {"every_steps": 1, "steps": n1, "ms_per_step": round(dt1 * 1000.0 / n1, 4),
                        "images_per_s": round(n_gpus * B * n1 / dt1, 1)}
 
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, logits, world, rank)
+
     out = None
     if args.timed_only:
         if rank == 0:
@@ -383,7 +416,7 @@ def main():
         if world > 1:
             dist.destroy_process_group()
         return
-    if rank == 0:
+    if rank == 0 and args.full:
         # ---------------- per-step latency distribution (hipEvents around each replay) -------------
         # (>= 1000 iterations with per-iteration events -> mean / p50 / p99; ~0.25 s at batch 8)
         lat = []
@@ -615,7 +648,7 @@ def main():
                                 what="workloads.framework_spec one op per reference operator (the list Graph::Optimize + "
                                      "Net<MI355X>::init produce, tests/test_net_oplist.py), through saber_hip_net_run")
                 del rn
-                exe = os.path.join(ROOT, "integration", "_build", "test_net_mi355x.bin")
+                exe = os.path.join(ROOT, "oracle", "_ref", "integration", "test_net_mi355x.bin")
                 if os.path.exists(exe) and args.model == "resnet50":
                     import subprocess
                     import tempfile
@@ -790,6 +823,7 @@ def main():
         elif not args.no_cpu_baseline and world == 1:
             cpu = cpu_baseline_fp32(args, model)
 
+    if rank == 0:
         out = {
             # BASELINE.json's metric: value = images/s at batch 8 per GPU; the p50 latencies at batch 8 and batch 1 are
             # in latency_ms / batch1
@@ -831,6 +865,9 @@ def main():
                             "VGG16 FP32 b8 within 1e-4 on two criteria; "
                             "tests/test_gpu_net.py: the same through the reference's own Net<MI355X> (every edge at batch 2, every image's "
                             "output at batch 8, plan == operator loop)",
+        }
+    if rank == 0 and args.full:
+        out.update({
             # value_p50 = batch / p50 of the per-iteration event pairs (1000 samples): what `value` would be if the timed region were
             # long - under the driver's --steps 20 `value` rests on a ~4 ms region and moves by +-1 % between runs
             "value_p50": round(B * n_gpus * 1000.0 / p50, 1),
@@ -841,7 +878,7 @@ def main():
             "gemm_f32": gemm,
             "roofline": roof,
             "cpu_baseline": cpu,
-        }
+        })
     if world > 1:
         dist.barrier()
         dist.destroy_process_group()

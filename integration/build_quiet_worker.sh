@@ -8,7 +8,7 @@ HERE=$(cd "$(dirname "$0")" && pwd)
 ROOT=$(dirname "$HERE")
 B=$HERE/_build
 A=$B/anakin
-[ -f $B/test_net_mi355x.bin ] || bash $HERE/build_mi355x_test.sh
+[ -f $ROOT/oracle/_ref/integration/test_net_mi355x.bin ] || bash $HERE/build_mi355x_test.sh
 [ -d $A ] || { echo "integration: no patched copy (build container only)"; exit 0; }
 Q=$B/quiet_inc
 mkdir -p $Q/utils/logger $B/obj_quiet

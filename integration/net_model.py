@@ -77,7 +77,7 @@ def calibrator_files(spec, scales, outdir):
             f.write("%s(%s)    %s    MI355X \n" % (n_, op, p))
     with open(cal, "w") as f:
         for e, s in edges:
-            f.write("%s %.9g\n" % (e, s))
+            f.write("%s %.9g\n" % (e, np.float32(s)))     # 9 digits of the float32: read back as exactly that float
     return cfg, cal
 
 
@@ -118,7 +118,7 @@ def write_model(model, scales, batch, outdir, precision="int8", hw=224, calibrat
             lines.append("pool %s %s AVG 7 7 0 1" % (nm, l["src"]))
         elif kd == "eltwise":
             # the INT8 eltwise ignores its output scale (saber_eltwise.cpp:85): the requantisation rides in the coefficients
-            c = 1.0 / scales[nm] if precision == "int8" else 1.0
+            c = np.float32(1.0 / scales[nm] if precision == "int8" else 1.0)
             lines.append("eltwise %s %s %s %d %.9g %.9g" % (nm, l["a"], l["b"], int(l["relu"]), c, c))
         elif kd == "fc":
             lines.append("fc %s %s %d %d %d" % (nm, l["src"], l["cin"], l["cout"], int(bool(l.get("relu")))))
@@ -135,9 +135,9 @@ def write_model(model, scales, batch, outdir, precision="int8", hw=224, calibrat
             lines.append("prec %s %s" % (l["name"], prec[l["name"]]))
             if consumers.get(l["name"], 0) > 1:      # Graph::Freeze inserts `<var>split` (graph.cpp:262-284)
                 lines.append("precsplit %s %s" % (l["name"], prec[l["name"]]))
-        lines.append("scale data %.9g" % scales["data"])
+        lines.append("scale data %.9g" % np.float32(scales["data"]))
         for l in spec:
-            lines.append("scale %s %.9g" % (l["name"], scales[l["name"]]))
+            lines.append("scale %s %.9g" % (l["name"], np.float32(scales[l["name"]])))
     mt, wb = os.path.join(outdir, "model.txt"), os.path.join(outdir, "weights.bin")
     open(mt, "w").write("\n".join(lines) + "\n")
     with open(wb, "wb") as f:

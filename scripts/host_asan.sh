@@ -2,7 +2,7 @@
 # The HOST side of the C-ABI library under AddressSanitizer (CPU only: the GPU pool has no sanitizers). The api_*.hip translation units - op-list
 # construction, saber_hip_net_optimize's rewrites, capture, finalize, the arena's lifetime aliasing, selection bookkeeping - are rebuilt with
 # -fsanitize=address -fno-gpu-sanitize (device code untouched), linked with the product's other objects into /tmp/saber_asan/libsaber_mi355x.so, and the
-# reference's own framework (integration/_build/test_net_mi355x.bin) runs Graph::load -> Optimize -> Net<MI355X>::init with the captured plan on the
+# reference's own framework (oracle/_ref/integration/test_net_mi355x.bin) runs Graph::load -> Optimize -> Net<MI355X>::init with the captured plan on the
 # malloc-backed mock HIP runtime against it: ResNet50 INT8 (set calls and calibrator files), ResNet101 INT8, ResNet50 FP32, VGG16 FP32, the Worker with
 # three pool threads, the eight-device mode. The string / memcmp INTERCEPTORS are off: with them the first report is the reference's own use-after-free in
 # GraphBase::remove_byio (framework/graph/graph_base.inl:218-240) - its freed node names compared through memcmp - and the run ends there;
@@ -37,8 +37,8 @@ import os, subprocess, sys, tempfile
 sys.path.insert(0, os.getcwd())
 from anakin_amd import workloads as W
 from integration import net_model as NM
-BIN = os.path.abspath("integration/_build/test_net_mi355x.bin")
-MOCK = os.path.abspath("integration/_build/libmock_hip.so")
+BIN = os.path.abspath("oracle/_ref/integration/test_net_mi355x.bin")
+MOCK = os.path.abspath("oracle/_ref/integration/libmock_hip.so")
 env = dict(os.environ, LD_PRELOAD=os.environ["SABER_ASAN_RT"] + " " + MOCK, LD_LIBRARY_PATH=os.environ["SABER_ASAN_LIBDIR"] + ":" + os.environ.get("LD_LIBRARY_PATH", ""),
            UBSAN_OPTIONS="halt_on_error=1:exitcode=98:print_stacktrace=1", ASAN_OPTIONS="detect_leaks=0:exitcode=97:abort_on_error=0:detect_odr_violation=0:replace_str=0:intercept_memcmp=0:intercept_strlen=0:intercept_strchr=0:intercept_strstr=0:intercept_strcmp=0", SABER_MI355X_NET_PLAN_TUNE="0")
 bad = 0
@@ -70,7 +70,7 @@ sys.exit(1 if bad else 0)
 PY
 rc=$?
 # proof that the instrumented library is the one that ran
-LD_LIBRARY_PATH=$D ldd $ROOT/integration/_build/test_net_mi355x.bin | grep saber_mi355x >> $OUT
+LD_LIBRARY_PATH=$D ldd $ROOT/oracle/_ref/integration/test_net_mi355x.bin | grep saber_mi355x >> $OUT
 nm -D $D/libsaber_mi355x.so | grep -c "__asan\|__ubsan" | sed 's/^/sanitizer symbols referenced by the library: /' >> $OUT
 tail -12 $OUT
 exit $rc

@@ -6,7 +6,7 @@ if python -c "import json,sys; sys.exit(0 if json.load(open('gpurun_out/boxcheck
   echo SLOW BOX
   bash scripts/probe/cons_ab.sh | tee gpurun_out/slowbox_cons_ab.txt
   SABER_HIP_AUTOTUNE_WARM=1 python bench.py --steps 400 --warmup 20 --timed-only 2>/dev/null | tail -1 | sed "s/^/warm-tuned /" | tee -a gpurun_out/slowbox_cons_ab.txt
-  python bench.py --steps 100 --warmup 10 --no-cpu-baseline --no-b1 --per-op 2>&1 >/dev/null | grep -v "in the chain\|amdgpu" | awk '{print $4}' | sort | uniq -c | sort -rn | tee -a gpurun_out/slowbox_cons_ab.txt
+  python bench.py --steps 100 --warmup 10 --no-cpu-baseline --no-b1 --full --per-op 2>&1 >/dev/null | grep -v "in the chain\|amdgpu" | awk '{print $4}' | sort | uniq -c | sort -rn
 else
   echo fast box
 fi

@@ -1,7 +1,7 @@
 mkdir -p gpurun_out/r05l; O=gpurun_out/r05l
 cd /tmp && export TMPDIR=/tmp && cd $GRAFT_REPO_ROOT
 (timeout 900 python -m pytest tests/test_gpu_parity.py -m gpu -q --maxfail=12 -p no:cacheprovider -k "weights_through_lds" 2>&1 | tail -40) > $O/pytest.txt
-SABER_HIP_AUTOTUNE_LOG=1 timeout 300 python bench.py --steps 200 --precision fp32 --no-cpu-baseline --no-b1 --per-op > $O/bench_r50_fp32.json 2> $O/log_r50_fp32.txt
+SABER_HIP_AUTOTUNE_LOG=1 timeout 300 python bench.py --steps 200 --precision fp32 --no-cpu-baseline --no-b1 --full --per-op > $O/bench_r50_fp32.json 2> $O/log_r50_fp32.txt
 tail -30 $O/pytest.txt; python -c "
 import json; v=json.load(open('$O/bench_r50_fp32.json')); print('r50 fp32', v['value'], v['ms_per_step'], v['config']['launches']); [print('  ', k['kernel'], k['launches'], k['avg_us']) for k in v['roofline']['per_kernel'][:18]]"
 python - $O/log_r50_fp32.txt <<'PY'

@@ -1,7 +1,7 @@
 mkdir -p gpurun_out/r05m; O=gpurun_out/r05m
 cd /tmp && export TMPDIR=/tmp && cd $GRAFT_REPO_ROOT
 for b in 1 4; do
-SABER_HIP_AUTOTUNE_LOG=1 timeout 300 python bench.py --steps 200 --precision fp32 --batch $b --no-cpu-baseline --no-b1 --per-op > $O/bench_r50_fp32_b$b.json 2> $O/log_b$b.txt
+SABER_HIP_AUTOTUNE_LOG=1 timeout 300 python bench.py --steps 200 --precision fp32 --batch $b --no-cpu-baseline --no-b1 --full --per-op > $O/bench_r50_fp32_b$b.json 2> $O/log_b$b.txt
 python -c "
 import json; v=json.load(open('$O/bench_r50_fp32_b$b.json')); print('r50 fp32 b$b', v['value'], v['ms_per_step'], v['config']['launches']); [print('  ', k['kernel'], k['launches'], k['avg_us']) for k in v['roofline']['per_kernel'][:12] if 'wlds' in k['kernel']]"
 python - $O/log_b$b.txt <<'PY'

@@ -14,7 +14,7 @@ OUT=gpurun_out/$TAG
 mkdir -p $OUT
 cd /tmp && export TMPDIR=/tmp && cd $GRAFT_REPO_ROOT
 rm -f $OUT/tune.json
-python bench.py --steps 400 --warmup 10 --per-op --tune-cache $OUT/tune.json $EXTRA > $OUT/bench.json 2> $OUT/per_op.txt
+python bench.py --steps 400 --warmup 10 --full --per-op --tune-cache $OUT/tune.json $EXTRA > $OUT/bench.json 2> $OUT/per_op.txt
 ARGS="--steps 20 --warmup 5 --timed-only --tune-cache $OUT/tune.json $EXTRA"
 rocprofv3 --kernel-trace --stats -d $OUT/trace -o t -- python bench.py $ARGS > $OUT/bench_trace.log 2>&1
 grep -h '"value"' $OUT/bench_trace.log | head -1 > $OUT/bench_under_trace.json

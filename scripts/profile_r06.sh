@@ -10,7 +10,7 @@ cd /tmp && export TMPDIR=/tmp && cd $GRAFT_REPO_ROOT
 rm -f $OUT/tune.json
 # the untraced run autotunes on this box and WRITES the selection (batch 8 and batch 1); every later pass applies it. Copied to
 # profiles/tune.json it is also what the driver's default `python bench.py` applies (keyed by configuration + source hash)
-python bench.py --steps 400 --warmup 10 --per-op --retune --write-tune-cache --tune-cache $OUT/tune.json $EXTRA > $OUT/bench.json 2> $OUT/per_op.txt
+python bench.py --steps 400 --warmup 10 --full --per-op --retune --write-tune-cache --tune-cache $OUT/tune.json $EXTRA > $OUT/bench.json 2> $OUT/per_op.txt
 for B in 2 4; do      # the other two BASELINE batch sizes into the same cache (their bench lines go to configs.jsonl later, applying these)
   python bench.py --batch $B --steps 100 --warmup 10 --no-cpu-baseline --no-b1 --retune --write-tune-cache --tune-cache $OUT/tune.json $EXTRA > $OUT/bench_b$B.json 2>/dev/null
 done

@@ -10,7 +10,7 @@ case $STEP in
 baseline)   # this round's box: the headline line, the FP32 lines WITH the x86 FP32 baseline (BASELINE configs[0])
   python bench.py --steps 400 --no-cpu-baseline > $O/bench_b8_int8.json 2> $O/bench_b8_int8.err
   python bench.py --precision fp32 --batch 1 --steps 200 --no-b1 --cpu-seconds 30 > $O/fp32_b1.json 2> $O/fp32_b1.err
-  python bench.py --precision fp32 --batch 8 --steps 200 --no-b1 --no-cpu-baseline --per-op > $O/fp32_b8.json 2> $O/fp32_b8_per_op.txt
+  python bench.py --precision fp32 --batch 8 --steps 200 --no-b1 --no-cpu-baseline --full --per-op > $O/fp32_b8.json 2> $O/fp32_b8_per_op.txt
   python bench.py --model vgg16 --precision fp32 --batch 8 --steps 100 --no-b1 --cpu-seconds 20 > $O/vgg16_b8.json 2> $O/vgg16.err
   nproc > $O/host.txt; lscpu | head -20 >> $O/host.txt ;;
 compact_ab) # the arena with lifetime aliasing against every edge materialised: the headline pass, batch 1, multi-stream; retunes once (new sources)
@@ -95,12 +95,12 @@ PY
 stage_b1)   # the XCD-resident res5 stage launch against the ops one by one at batch 1 / 2 / 8 (round-5 verdict item 3: re-measure at batch 1)
   for n in 1 2 8; do python scripts/probe/stage_time.py $n; done > $O/stage_time.txt 2>&1; cat $O/stage_time.txt ;;
 fp32)       # ResNet50 FP32 b8 / b1 (+ VGG16) bench lines with the per-op table
-  python bench.py --precision fp32 --batch 8 --steps 200 --no-b1 --no-cpu-baseline --per-op > $O/fp32_b8.json 2> $O/fp32_b8_per_op.txt
-  python bench.py --precision fp32 --batch 1 --steps 200 --no-b1 --no-cpu-baseline --per-op > $O/fp32_b1.json 2> $O/fp32_b1_per_op.txt
-  SABER_HIP_STEM_F32_TILE=1 python bench.py --precision fp32 --batch 8 --steps 200 --no-b1 --no-cpu-baseline --per-op > $O/fp32_b8_t1.json 2> $O/fp32_b8_t1_per_op.txt
-  SABER_HIP_STEM_F32_TILE=2 python bench.py --precision fp32 --batch 8 --steps 200 --no-b1 --no-cpu-baseline --per-op > $O/fp32_b8_t2.json 2> $O/fp32_b8_t2_per_op.txt
-  SABER_HIP_STEM_F32_TILE=3 python bench.py --precision fp32 --batch 8 --steps 200 --no-b1 --no-cpu-baseline --per-op > $O/fp32_b8_t3.json 2> $O/fp32_b8_t3_per_op.txt
-  SABER_HIP_STEM_F32_TILE=2 python bench.py --precision fp32 --batch 1 --steps 200 --no-b1 --no-cpu-baseline --per-op > $O/fp32_b1_t2.json 2> $O/fp32_b1_t2_per_op.txt
+  python bench.py --precision fp32 --batch 8 --steps 200 --no-b1 --no-cpu-baseline --full --per-op > $O/fp32_b8.json 2> $O/fp32_b8_per_op.txt
+  python bench.py --precision fp32 --batch 1 --steps 200 --no-b1 --no-cpu-baseline --full --per-op > $O/fp32_b1.json 2> $O/fp32_b1_per_op.txt
+  SABER_HIP_STEM_F32_TILE=1 python bench.py --precision fp32 --batch 8 --steps 200 --no-b1 --no-cpu-baseline --full --per-op > $O/fp32_b8_t1.json 2> $O/fp32_b8_t1_per_op.txt
+  SABER_HIP_STEM_F32_TILE=2 python bench.py --precision fp32 --batch 8 --steps 200 --no-b1 --no-cpu-baseline --full --per-op > $O/fp32_b8_t2.json 2> $O/fp32_b8_t2_per_op.txt
+  SABER_HIP_STEM_F32_TILE=3 python bench.py --precision fp32 --batch 8 --steps 200 --no-b1 --no-cpu-baseline --full --per-op > $O/fp32_b8_t3.json 2> $O/fp32_b8_t3_per_op.txt
+  SABER_HIP_STEM_F32_TILE=2 python bench.py --precision fp32 --batch 1 --steps 200 --no-b1 --no-cpu-baseline --full --per-op > $O/fp32_b1_t2.json 2> $O/fp32_b1_t2_per_op.txt
   python - <<'PY'
 import json
 for f in ("fp32_b8","fp32_b1","fp32_b8_t1","fp32_b8_t2","fp32_b8_t3","fp32_b1_t2"):
@@ -109,8 +109,8 @@ PY
   for f in fp32_b8 fp32_b1 fp32_b8_t1 fp32_b8_t2 fp32_b8_t3 fp32_b1_t2; do echo $f; grep -h "^ *0 " $O/${f}_per_op.txt; done ;;
 nosplit)    # what bf16-plane FP32 edges could gain AT MOST: the product library against the probe build whose plane split costs one instruction (wrong results, timing only)
   for b in 8 1; do
-    python bench.py --precision fp32 --batch $b --steps 200 --no-b1 --no-cpu-baseline --per-op --retune > $O/fp32_b${b}_product.json 2> $O/fp32_b${b}_product_per_op.txt
-    SABER_MI355X_LIB=$PWD/anakin_amd/build_probe/libsaber_mi355x_nosplit.so python bench.py --precision fp32 --batch $b --steps 200 --no-b1 --no-cpu-baseline --per-op --retune > $O/fp32_b${b}_nosplit.json 2> $O/fp32_b${b}_nosplit_per_op.txt
+    python bench.py --precision fp32 --batch $b --steps 200 --no-b1 --no-cpu-baseline --full --per-op --retune > $O/fp32_b${b}_product.json 2> $O/fp32_b${b}_product_per_op.txt
+    SABER_MI355X_LIB=$PWD/anakin_amd/build_probe/libsaber_mi355x_nosplit.so python bench.py --precision fp32 --batch $b --steps 200 --no-b1 --no-cpu-baseline --full --per-op --retune > $O/fp32_b${b}_nosplit.json 2> $O/fp32_b${b}_nosplit_per_op.txt
   done
   SABER_MI355X_LIB=$PWD/anakin_amd/build_probe/libsaber_mi355x_nosplit.so python bench.py --model vgg16 --precision fp32 --batch 8 --steps 100 --no-b1 --no-cpu-baseline --retune > $O/vgg16_nosplit.json 2> $O/vgg16_nosplit.err
   python bench.py --model vgg16 --precision fp32 --batch 8 --steps 100 --no-b1 --no-cpu-baseline --retune > $O/vgg16_product.json 2> $O/vgg16_product.err
@@ -124,8 +124,8 @@ PY
   ;;
 fctail)     # the FP32 classifier tail: split-K fc (+ softmax in the launch) against the one-workgroup-per-tile fc + the softmax launch
   for b in 8 1; do
-    python bench.py --precision fp32 --batch $b --steps 200 --no-b1 --no-cpu-baseline --per-op > $O/split_b$b.json 2> $O/split_b${b}_per_op.txt
-    SABER_HIP_FC_F32_SPLITK=0 python bench.py --precision fp32 --batch $b --steps 200 --no-b1 --no-cpu-baseline --per-op > $O/plain_b$b.json 2> $O/plain_b${b}_per_op.txt
+    python bench.py --precision fp32 --batch $b --steps 200 --no-b1 --no-cpu-baseline --full --per-op > $O/split_b$b.json 2> $O/split_b${b}_per_op.txt
+    SABER_HIP_FC_F32_SPLITK=0 python bench.py --precision fp32 --batch $b --steps 200 --no-b1 --no-cpu-baseline --full --per-op > $O/plain_b$b.json 2> $O/plain_b${b}_per_op.txt
   done
   for f in split_b8 plain_b8 split_b1 plain_b1; do echo $f; python -c "import json;d=json.load(open('$O/$f.json'));print(d['value'],d['ms_per_step'],d['config']['launches'])"; tail -n 4 $O/${f}_per_op.txt; done ;;
 final)      # the round's evidence run, one box: GPU test suite, the INT8 profile (tune cache, traces, PMC), every BASELINE configuration, the other models' profiles

@@ -6,7 +6,7 @@ O=gpurun_out/$TAG
 mkdir -p $O
 cd /tmp && export TMPDIR=/tmp && cd $GRAFT_REPO_ROOT
 rm -f $O/tune.json
-python bench.py --steps 200 --warmup 10 --no-cpu-baseline --no-b1 --per-op --tune-cache $O/tune.json "$@" > $O/bench.json 2> $O/per_op.txt
+python bench.py --steps 200 --warmup 10 --no-cpu-baseline --no-b1 --full --per-op --tune-cache $O/tune.json "$@" > $O/bench.json 2> $O/per_op.txt
 rocprofv3 --kernel-trace --stats -d $O/trace -o t -- python bench.py --steps 20 --warmup 5 --timed-only --tune-cache $O/tune.json "$@" > $O/bench_trace.log 2>&1
 grep -h '"value"' $O/bench_trace.log | head -1 > $O/bench_under_trace.json
 N=$(python -c "import json;d=json.load(open('$O/bench_under_trace.json'));print(d.get('launches', d['ops']))")

@@ -24,9 +24,9 @@ from anakin_amd import workloads as W            # noqa: E402
 pb = pytest.importorskip("google.protobuf")
 import anakin_proto as AP                         # noqa: E402
 
-BIN = os.path.join(ROOT, "integration", "_build", "test_net_mi355x.bin")
-MOCK = os.path.join(ROOT, "integration", "_build", "libmock_hip.so")
-needs_integration = pytest.mark.skipif(not (os.path.exists(BIN) and os.path.exists(MOCK)), reason="integration/_build not built (needs /root/reference at build time)")
+BIN = os.path.join(ROOT, "oracle", "_ref", "integration", "test_net_mi355x.bin")
+MOCK = os.path.join(ROOT, "oracle", "_ref", "integration", "libmock_hip.so")
+needs_integration = pytest.mark.skipif(not (os.path.exists(BIN) and os.path.exists(MOCK)), reason="oracle/_ref/integration not built (needs the reference tree at build time)")
 
 
 @pytest.fixture(scope="module")
@@ -267,9 +267,8 @@ def test_int8_scales_and_precisions_travel_in_the_file(tmp_path):
     scales = W.calibrate(model, W.make_input(2))
     wire = AB.write_model(model, None, batch=1, precision="int8", scales=scales)
     m2 = AB.load_model(wire)
-    f9 = lambda x: float(np.float32(float("%.9g" % x)))      # noqa: E731
     assert set(m2["scales"]) == set(scales)
-    assert all(m2["scales"][k] == f9(v) for k, v in scales.items())
+    assert all(m2["scales"][k] == float(np.float32(v)) for k, v in scales.items())
     assert m2["precisions"]["prob"] == "fp32" and m2["precisions"]["conv1"] == "int8" and m2["precisions"]["res5c"] == "int8"
 
 

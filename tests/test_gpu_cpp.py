@@ -27,7 +27,7 @@ def test_cpp_test_binary_is_built():
     assert os.path.exists(BIN)
 
 
-MI355X_BIN = os.path.join(ROOT, "integration", "_build", "test_saber_conv_mi355x.bin")
+MI355X_BIN = os.path.join(ROOT, "oracle", "_ref", "integration", "test_saber_conv_mi355x.bin")
 
 
 @pytest.mark.gpu
@@ -38,7 +38,7 @@ def test_mi355x_target_inside_the_reference_operator_stack(tmp_path):
     the Conv facade ladder) and drives Conv<MI355X,AK_INT8>::init -> BaseFunc::operator() (incl. the shape-change
     re-create path, base.h:151-161) -> SaberConv2D<MI355X> -> integration/saber_mi355x_adaptor.h -> the C ABI;
     every output byte equals the oracle's."""
-    assert os.path.exists(MI355X_BIN), "integration/_build/test_saber_conv_mi355x.bin is missing: run __graft_entry__.build()"
+    assert os.path.exists(MI355X_BIN), "oracle/_ref/integration/test_saber_conv_mi355x.bin is missing: run __graft_entry__.build()"
     p = subprocess.run([MI355X_BIN], capture_output=True, text=True, timeout=600, cwd=str(tmp_path))   # (the reference's logger writes ./log/)
     assert p.returncode == 0, p.stdout[-3000:] + p.stderr[-2000:]
     assert "0 failed" in p.stdout and "bit-exact" in p.stdout and "SaberTimer<MI355X>" in p.stdout

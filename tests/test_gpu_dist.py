@@ -38,8 +38,8 @@ def test_bench_four_ranks_share_one_gpu_and_report_the_per_request_exchange():
     for k in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_PORT"):
         env.pop(k, None)
     env.update(BENCH_DIST_BACKEND="gloo", BENCH_SHARE_GPU="1")
-    p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "4", "--steps", "40", "--warmup", "5", "--no-cpu-baseline",
-                        "--no-b1"], capture_output=True, text=True, env=env, cwd=ROOT, timeout=1200)
+    p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "4", "--steps", "40", "--warmup", "5", "--full",
+                        "--no-cpu-baseline", "--no-b1"], capture_output=True, text=True, env=env, cwd=ROOT, timeout=1200)
     assert p.returncode == 0, p.stdout[-2000:] + p.stderr[-3000:]
     lines = [l for l in p.stdout.splitlines() if l.startswith("{")]
     assert len(lines) == 1, p.stdout[-2000:]

@@ -19,7 +19,7 @@ import pytest
 pytestmark = pytest.mark.gpu
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-BIN = os.path.join(ROOT, "integration", "_build", "test_net_mi355x.bin")
+BIN = os.path.join(ROOT, "oracle", "_ref", "integration", "test_net_mi355x.bin")
 
 from anakin_amd import workloads as W          # noqa: E402
 from integration import net_model as NM        # noqa: E402
@@ -29,7 +29,7 @@ NP = {"s8": np.int8, "u8": np.uint8, "f32": np.float32}
 
 
 def run_net(tmp_path, name, precision, batch, iters=0, calibrator_config=False, rename=None):
-    assert os.path.exists(BIN), "integration/_build/test_net_mi355x.bin is missing: run __graft_entry__.build()"
+    assert os.path.exists(BIN), "oracle/_ref/integration/test_net_mi355x.bin is missing: run __graft_entry__.build()"
     model = W.build_model(name)
     x = W.make_input(batch)
     scales = W.calibrate(model, x) if precision == "int8" else {}
@@ -191,7 +191,7 @@ def test_net_mi355x_resnet50_int8_batch8_prediction_through_the_plan(tmp_path):
 
 
 def _run_mode(tmp_path, name, batch, x, mode_args, env_extra=None, precision="fp32", scales=None):
-    assert os.path.exists(BIN), "integration/_build/test_net_mi355x.bin is missing: run __graft_entry__.build()"
+    assert os.path.exists(BIN), "oracle/_ref/integration/test_net_mi355x.bin is missing: run __graft_entry__.build()"
     model = W.build_model(name)
     d = str(tmp_path)
     mt, wb = NM.write_model(model, scales or {}, batch, d, precision, calibrator_config=precision == "int8")
@@ -342,7 +342,7 @@ def test_net_mi355x_from_an_anakin_bin(tmp_path, precision, route):
     Optimize -> Net::init -> prediction. INT8: every edge and the logits are the oracle's bits, with the precisions / scales either in the file
     (bit_type + per-edge scale) or in the two calibrator text files next to it; FP32: every edge within 1e-4."""
     from anakin_amd import anakin_bin as AB
-    assert os.path.exists(BIN), "integration/_build/test_net_mi355x.bin is missing: run __graft_entry__.build()"
+    assert os.path.exists(BIN), "oracle/_ref/integration/test_net_mi355x.bin is missing: run __graft_entry__.build()"
     batch = 2
     model = W.build_model("resnet50")
     x = W.make_input(batch)
@@ -405,9 +405,8 @@ def test_ctypes_route_from_an_anakin_bin_answers_with_the_oracles_bits(tmp_path)
     loaded = AB.load_model(path)
     fm = W.framework_model(dict(loaded, name="resnet50"), "int8")
     ref = NO.run_int8(W.framework_model(model, "int8"), dict(scales), x)
-    # the file carries the scales as 9-digit decimals' floats (the text route's records): calibrate() values rounded the same way
-    f9 = lambda v: float(np.float32(float("%.9g" % v)))      # noqa: E731
-    assert all(loaded["scales"][k] == f9(v) for k, v in scales.items())
+    # the file carries the scales as the float32 each calibrate() value rounds to (what the oracle and the C ABI use too)
+    assert all(loaded["scales"][k] == float(np.float32(v)) for k, v in scales.items())
     net = W.build_int8_net(fm, dict(scales), 2)
     net.tensor("data").copy_(torch.from_numpy(x).cuda())
     net.run()
@@ -430,7 +429,7 @@ def test_net_mi355x_random_resnet_like_int8_every_edge_bit_exact(tmp_path, seed)
     oracle's bytes on workloads.framework_spec, prediction() == the op-by-op pass == the operator loop."""
     import importlib
     G = importlib.import_module("tests.test_gpu_resnet")
-    assert os.path.exists(BIN), "integration/_build/test_net_mi355x.bin is missing: run __graft_entry__.build()"
+    assert os.path.exists(BIN), "oracle/_ref/integration/test_net_mi355x.bin is missing: run __graft_entry__.build()"
     rng = np.random.default_rng(4200 + seed)
     model, hw = G._random_resnet_like(rng)
     batch = int(rng.choice([1, 2, 3, 8]))

@@ -1,6 +1,6 @@
 """The op list of `anakin_amd.workloads.framework_spec` IS what the reference's own optimiser emits.
 
-`integration/_build/test_net_mi355x.bin` is the reference's framework — Graph / fusion pass / stride-up / schedulers /
+`oracle/_ref/integration/test_net_mi355x.bin` is the reference's framework — Graph / fusion pass / stride-up / schedulers /
 memory planner / Net, compiled unmodified against the MI355X target (integration/apply_mi355x_target.py) — driven with the
 network as ORIGINAL operators (Convolution + BatchNorm + Scale + ReLU ...). Here it runs `dry` on the malloc-backed mock HIP
 runtime (integration/mock_hip): Graph::Optimize() and Net<MI355X>::init() execute for real (they are host code), nothing
@@ -20,10 +20,10 @@ sys.path.insert(0, ROOT)
 from anakin_amd import workloads as W          # noqa: E402
 from integration import net_model as NM        # noqa: E402
 
-BIN = os.path.join(ROOT, "integration", "_build", "test_net_mi355x.bin")
-MOCK = os.path.join(ROOT, "integration", "_build", "libmock_hip.so")
+BIN = os.path.join(ROOT, "oracle", "_ref", "integration", "test_net_mi355x.bin")
+MOCK = os.path.join(ROOT, "oracle", "_ref", "integration", "libmock_hip.so")
 pytestmark = pytest.mark.skipif(not (os.path.exists(BIN) and os.path.exists(MOCK)),
-                                reason="integration/_build not built (needs /root/reference at build time)")
+                                reason="oracle/_ref/integration not built (needs the reference tree at build time)")
 
 DT = {W.F32: "f32", W.S8: "s8", W.U8: "u8"}
 
