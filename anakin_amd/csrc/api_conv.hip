@@ -572,6 +572,7 @@ int saber_hip_conv2d_set_weights(saber_hip_conv_t* op, const void* w, int w_dtyp
         if (w_dtype != SABER_HIP_F32) return fail(SABER_HIP_INVALID_VALUE, "FP32 conv needs f32 weights");
         const float* wf = (const float*)w;
         std::vector<float> wr;
+        bool weights_b3 = false;
         if (d.group == 1 && Cg == 3 && kh == 7 && kw == 7 && K == 64) op->w_stem_host.assign(wf, wf + (size_t)K * inner);      // (the FP32 stem launch packs its own planes: set_pooling)
         if (op->algo == ALGO_IGEMM_F32) {
             wr.assign((size_t)K_pad * op->Kg_pad, 0.f);
@@ -650,6 +651,7 @@ int saber_hip_conv2d_set_weights(saber_hip_conv_t* op, const void* w, int w_dtyp
                 pl[i] = h; pl[n + i] = m; pl[2 * n + i] = rne(r2);
             }
             HIP_TRY(op->d_w3.upload(planes));
+            weights_b3 = true;
             // 3x3 / stride 1 / pad 1 on NHWC f32: the same planes once more in MFMA A-fragment order for the LDS-halo kernel
             // (conv3x3_b3h.hip): [16-row tile][32-channel chunk][tap][plane][lane] x 8 bf16. Row rho of tile i of a wave's tm
             // tiles is channel  base + (rho >> 2) * 4 tm + 4 i + (rho & 3)  (a lane then owns 4 tm consecutive channels).
@@ -683,7 +685,22 @@ int saber_hip_conv2d_set_weights(saber_hip_conv_t* op, const void* w, int w_dtyp
             // eligible FP32 convolution (0 keeps the f32-MFMA kernels); unset: see f32_static_b3()
             const char* e = getenv("SABER_HIP_F32_BF16X3");
             const bool want = e ? (e[0] == '1') : f32_static_b3(op);
-            if (want && !op->pair_k2) { op->b3 = 1; op->ks = 1; op->dma = 0; name_algo(op); }
+            if (!op->weights_set && want && !op->pair_k2) { op->b3 = 1; op->ks = 1; op->dma = 0; name_algo(op); }      // (a later set_weights keeps the selection the op has)
+        }
+        // weights set again on a live op: the packings that are NOT made above follow the new weights too - the FP32 stem launch's planes
+        // (packed by set_pooling) and the pointwise kernels' fragment-ordered planes (packed on demand from d_w3 by pw_prepare)
+        if (op->stem32) {
+            std::vector<uint8_t> fr;
+            stem_f32_pack(op->w_stem_host.data(), fr);
+            HIP_TRY(op->d_wstem32.upload(fr));
+        }
+        if (op->d_wpw.p) {
+            op->d_wpw.release();
+            if (op->pw) {
+                if (!weights_b3) return fail(SABER_HIP_INVALID_VALUE, "set_weights: the selected pointwise kernel needs the bf16 planes");
+                const int rc = pw_prepare(op);
+                if (rc) return rc;
+            }
         }
         std::vector<float> b(K_pad, 0.f);
         if (bias) std::memcpy(b.data(), bias, sizeof(float) * K);

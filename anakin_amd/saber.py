@@ -116,6 +116,17 @@ class SaberConv2D:
         self.ws = torch.empty(max(nbytes, 16), dtype=torch.uint8, device="cuda") if nbytes else None
         return self
 
+    def set_weights(self, weight, bias=None, w_scale=None, in_scale=1.0, out_scale=1.0):
+        """New weights / bias on the live op (saber_hip_conv2d_set_weights a second time): same shapes, the kernel selection stays."""
+        w_np = np.ascontiguousarray(weight)
+        assert w_np.shape == (self.desc.k, self.desc.c // self.desc.group, self.desc.kh, self.desc.kw), w_np.shape
+        w_dt = L.F32 if w_np.dtype == np.float32 else L.S8
+        ws = None if w_scale is None else np.ascontiguousarray(w_scale, np.float32)
+        b = None if bias is None else np.ascontiguousarray(bias, np.float32)
+        L.check(L.load().saber_hip_conv2d_set_weights(self.h, _np_ptr(w_np), w_dt, _np_ptr(ws), _np_ptr(b),
+                                                      float(in_scale), float(out_scale)))
+        return self
+
     def out_shape(self):
         """Logical output shape in the op's output layout."""
         d = self.desc

@@ -19,7 +19,11 @@
  *
  * Call protocol (mirrors init-once / dispatch-many):
  *   *_create           once per operator ("init"/"create": shapes, algorithm choice)
- *   *_set_weights      once ("init": quantise + repack weights, pre-scale bias — HOST pointers, cold path)
+ *   *_set_weights      at "init" (quantise + repack weights, pre-scale bias — HOST pointers, cold path); saber_hip_conv2d_set_weights
+ *                      may be called again on a live op: every packing of the op follows the new weights and bias (the FP32 stem
+ *                      launch's and the pointwise kernels' planes included) and the kernel selection stays. It synchronises the
+ *                      device. Pairs, chains and stages COPY their members' weights when they are created: they keep the weights
+ *                      their members had then.
  *   *_run              every inference ("dispatch"): enqueues on the given hipStream_t, never syncs.
  * All tensor pointers given to *_run are DEVICE pointers owned by the caller. Returns 0 on success
  * or a negative saber_hip_status; the adaptor maps 0 -> SaberSuccess(-1, saber_types.h:224) and
