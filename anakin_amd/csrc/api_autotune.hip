@@ -12,7 +12,7 @@ thread_local std::vector<unsigned long long>* g_used_kernels = nullptr;
 // launches accumulate into y (the caller re-initialises it). On error the entry selection is restored.
 int saber_hip_conv2d_autotune(saber_hip_conv_t* op, const void* x, void* y, const void* res, void* workspace,
                                          saber_hip_stream_t stream, int iters) {
-    if (op->algo > ALGO_IGEMM_F32 || op->pool_fused || op->gpool) return SABER_HIP_OK;   // (one fused conv+pooling kernel)
+    if ((op->algo > ALGO_IGEMM_F32 && !dw_ok(op)) || op->pool_fused || op->gpool) return SABER_HIP_OK;   // (one fused conv+pooling kernel)
     if (op->pair_k2) return fail(SABER_HIP_INVALID_VALUE, "sibling pair: use saber_hip_conv2d_autotune_pair");
     hipStream_t s = (hipStream_t)stream;
     EventPair ev;
@@ -59,6 +59,22 @@ int saber_hip_conv2d_autotune(saber_hip_conv_t* op, const void* x, void* y, cons
         }
     };
     ConvChoice c = {op->tile, op->ks, 0, 0, 0, 0, 0, 4, 0, 0};
+    if (dw_ok(op)) {      // depthwise 3x3: the direct kernel (form 0) and every form of conv_dw3x3.hip
+        for (int f = 0; f <= DW3X3_FORMS; ++f) {
+            ConvChoice cd = entry;
+            cd.dw = f;
+            set_choice(op, cd);
+            time_current();
+        }
+        if (best >= 1e30f) {
+            set_choice(op, entry);
+            name_algo(op);
+            return err ? err : fail(SABER_HIP_RUNTIME_ERROR, "autotune: no variant ran");
+        }
+        set_choice(op, best_c);
+        name_algo(op);
+        return saber_hip_conv2d_run(op, x, y, res, workspace, s);
+    }
     if (op->fc_small && fc_small_ok(op)) return SABER_HIP_OK;   // small-batch fc: one launch at the latency floor, nothing to tune
     const int ks_list[3] = {1, 2, 4};
     const int dma_list[4] = {0, 1, 2, 4};

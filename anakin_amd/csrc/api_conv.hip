@@ -173,6 +173,7 @@ void name_algo(saber_hip_conv* op) {
     else if (op->img1) snprintf(buf, sizeof buf, "imgres%dx%d_i8_%dch%s", op->d.kh, op->d.kw, 16 * ((op->d.k / 16 + 31) / 32), op->gpool ? "+gpool" : "");
     else if (op->img_rb) snprintf(buf, sizeof buf, "img3x3_i8_%dimg_x_%drows_k16_w%d", op->img_ib, op->img_rb, op->img_nw);
     else if (op->halo) snprintf(buf, sizeof buf, "halo3x3_i8_%dx16", op->halo);
+    else if (op->dw) snprintf(buf, sizeof buf, "dw3x3_%s_%s", op->is_i8 ? "i8" : "f32", conv_dw3x3_form_name(op->dw, !op->is_i8));
     else if (op->algo <= ALGO_IGEMM_F32)
         snprintf(buf, sizeof buf, "%s_%dx%d_k%d%s%s%s%s", op->b3 ? "igemm_f32_bf16x3" : an[op->algo], bmk, bnp, op->ks,
                  op->b3 && op->tile >= TILE_W8_64x64 ? "_w8" : "",
@@ -291,6 +292,7 @@ int saber_hip_conv2d_create(const saber_hip_conv_desc* desc, saber_hip_conv_t** 
         op->Kg_pad = round_up(op->Kg, 256);    // f32 elements: 1024 B
     }
     op->stem = stem_ok(op) ? 1 : 0;
+    op->dw = dw_ok(op) ? dw_static_form(op) : 0;
     choose_tile(op);
     {   // stage depth: as many 64-byte k-steps per barrier as the reduction has (max 4)
         const int kbytes = op->Kg * (op->algo == ALGO_IGEMM_F32 ? 4 : 1);
@@ -358,12 +360,19 @@ int saber_hip_conv2d_set_pooling(saber_hip_conv_t* op, int pool_type, int kh, in
 size_t saber_hip_conv2d_workspace_bytes(const saber_hip_conv_t* op) { return op->ws_bytes; }
 const char* saber_hip_conv2d_algo(const saber_hip_conv_t* op) { return op->algo_name.c_str(); }
 
+// STATIC form of an eligible depthwise op, from the measured table (profiles/dw3x3/README.md): the strip form where the launch has
+// enough lanes to fill the device with it, the one-pixel-per-lane form below that. 0 would be the direct kernel.
+int dw_static_form(const saber_hip_conv* op) {
+    const long lanes = (long)op->d.n * op->oh * op->ow * (op->d.c / (op->is_i8 ? 16 : 4));
+    return lanes >= DW_STRIP_MIN_LANES ? 1 : 2;
+}
+
 static inline bool tile_arg_ks(int ks) { return ks == 1 || ks == 2 || ks == 4; }
 // every specialised-kernel selector off (run / get_tile test img1 and b3h FIRST): a set_tile that selects one kernel family
 // starts from here, so a selection made by an earlier autotune / set_tile cannot keep running under the new one's name
 static void clear_selectors(saber_hip_conv* op) {
     if (!op->gpool) op->img1 = 0;      // (conv + fused global pooling exists only as the image-resident kernel)
-    op->b3h = 0; op->b3 = 0; op->ksplit = 0; op->halo = 0; op->stem = 0; op->img_ib = op->img_rb = 0; op->fc_small = 0; op->pw = 0;
+    op->b3h = 0; op->b3 = 0; op->ksplit = 0; op->halo = 0; op->stem = 0; op->img_ib = op->img_rb = 0; op->fc_small = 0; op->pw = 0; op->dw = 0;
 }
 
 int saber_hip_conv2d_set_tile(saber_hip_conv_t* op, int tile) {
@@ -400,6 +409,15 @@ int saber_hip_conv2d_set_tile(saber_hip_conv_t* op, int tile) {
         }
         clear_selectors(op);
         op->b3 = 1; op->dma = 0; op->ks = ksd ? ksd : 1; op->tile = tile; op->ksplit = sh;
+        name_algo(op);
+        return SABER_HIP_OK;
+    }
+    if (var == 16) {   // depthwise 3x3: low byte 0 = the direct kernel, 1 .. DW3X3_FORMS = the forms of conv_dw3x3.hip
+        if (!dw_ok(op) || tile > DW3X3_FORMS)
+            return fail(SABER_HIP_INVALID_VALUE, "depthwise 3x3 kernels: group == c == k, 3x3, dilation 1, stride 1 | 2, pad 0 | 1, NHWC 8-bit (C % 16 == 0) "
+                                                 "or f32 (C % 4 == 0) tensors, no residual; low byte 0 (direct kernel) .. 2");
+        clear_selectors(op);
+        op->dw = tile;
         name_algo(op);
         return SABER_HIP_OK;
     }
@@ -465,6 +483,7 @@ int saber_hip_conv2d_set_tile(saber_hip_conv_t* op, int tile) {
     return SABER_HIP_OK;
 }
 int saber_hip_conv2d_get_tile(const saber_hip_conv_t* op) {
+    if (dw_ok(op)) return (16 << 16) | op->dw;      // (form 0 included: an eligible op always answers in this encoding)
     if (op->pw) return (14 << 16) | (op->pw - 1);
     if (op->b3h) return op->b3h | (13 << 16);
     if (op->img1) return 12 << 16;
@@ -558,6 +577,12 @@ int saber_hip_conv2d_set_weights(saber_hip_conv_t* op, const void* w, int w_dtyp
                             wr[(((size_t)k * kh + i) * kw + j) * Cg + c] =
                                 (uint8_t)q[(((size_t)k * Cg + c) * kh + i) * kw + j];
         }
+        if (dw_ok(op)) {      // depthwise 3x3: [tap][C] for the 16-byte channel vectors of conv_dw3x3.hip
+            std::vector<uint8_t> wd((size_t)9 * K);
+            for (int k = 0; k < K; ++k)
+                for (int t = 0; t < 9; ++t) wd[(size_t)t * K + k] = (uint8_t)q[(size_t)k * 9 + t];
+            HIP_TRY(op->d_wdw.upload(wd));
+        }
         bias_p.resize(K_pad, 0.f);
         scale.resize(K_pad, 0.f);
         op->bias_p_host = bias_p;
@@ -593,6 +618,13 @@ int saber_hip_conv2d_set_weights(saber_hip_conv_t* op, const void* w, int w_dtyp
         }
         std::vector<uint8_t> raw((const uint8_t*)wr.data(), (const uint8_t*)wr.data() + wr.size() * sizeof(float));
         HIP_TRY(op->d_w.upload(raw));
+        if (dw_ok(op)) {      // depthwise 3x3: [tap][C] for the 16-byte channel vectors of conv_dw3x3.hip
+            std::vector<uint8_t> wd((size_t)9 * K * sizeof(float));
+            float* wdf = (float*)wd.data();
+            for (int k = 0; k < K; ++k)
+                for (int t = 0; t < 9; ++t) wdf[(size_t)t * K + k] = wf[(size_t)k * 9 + t];
+            HIP_TRY(op->d_wdw.upload(wd));
+        }
         // an fc with few output tiles: scratch of the split-K kernel (fc_f32_splitk.hip) - OPT-IN (SABER_HIP_FC_F32_SPLITK=1): measured no
         // faster than the one-workgroup-per-tile fc + the softmax launch (18.3 vs 16.7 us at batch 8, 12.6 vs 13.2 at batch 1,
         // profiles/r06/fc_tail.txt): the split adds two round trips through the device's coherence point to a tail that is a latency chain
@@ -925,10 +957,16 @@ int saber_hip_conv2d_run(saber_hip_conv_t* op, const void* x, void* y, const voi
         else HIP_TRY(op->dma ? launch_conv_igemm_dma(2, op->tile, op->ks, op->dma, a, s) : launch_conv_igemm(2, op->tile, op->ks, a, s));
         break;
     case ALGO_DIRECT_I8:
+    case ALGO_DIRECT_F32:
+        if (op->dw) {
+            if (!dw_ok(op) || !op->d_wdw.p) return fail(SABER_HIP_INVALID_VALUE, "depthwise kernel selected on an op without its [tap][C] weights");
+            a.w = op->d_wdw.p;
+            HIP_TRY(launch_conv_dw3x3(op->dw, !op->is_i8, a, s));
+            break;
+        }
         a.comp = nullptr;
-        HIP_TRY(launch_conv_direct(0, a, d.group, s));
+        HIP_TRY(launch_conv_direct(op->is_i8 ? 0 : 1, a, d.group, s));
         break;
-    case ALGO_DIRECT_F32: HIP_TRY(launch_conv_direct(1, a, d.group, s)); break;
     default: return fail(SABER_HIP_UNIMPL, "no algorithm");
     }
     return SABER_HIP_OK;

@@ -110,6 +110,8 @@ struct saber_hip_conv {
     int pw = 0;              // FP32 1x1 / stride 1: 1 = persistent register-weights kernel (C = 64 / 128, conv1x1_pw.hip), 2 .. 5 = the
                              // reduction-split kernel's variants 1 .. 4 (C = 128 .. 2048, conv1x1_pwk.hip), 0: not used
     DevBuf<uint8_t> d_wpw;   // its weight planes in that kernel's fragment order
+    int dw = 0;              // depthwise 3x3 (dw_ok; algo stays ALGO_DIRECT_*): 1 .. DW3X3_FORMS = that form of conv_dw3x3.hip, 0: the direct kernel
+    DevBuf<uint8_t> d_wdw;   // its weights as [tap][C] (s8 / f32), packed by set_weights
     DevBuf<float> d_fcpart;  // FP32 fc at <= 16 rows and <= 2048 outputs: the split-K kernel's partial sums + arrival counters (fc_f32_splitk.hip;
     DevBuf<unsigned> d_fcctr; // allocated by set_weights when the shape is eligible AND SABER_HIP_FC_F32_SPLITK=1: opt-in, measured no faster - profiles/r06/fc_tail.txt)
     DevBuf<float> d_wfc;     // FP32 fc at <= 16 rows: the weights fragment-major for the streaming kernel (fc_small.hip: fc_f32_stream_kernel PACKED)
@@ -214,14 +216,23 @@ struct saber_hip_fc {
 namespace saber_api {
 // one selection of kernel variant for an op (what the autotuner saves / restores)
 struct ConvChoice {
-    int tile, ks, dma, stem, halo, img_ib, img_rb, img_nw, fc_small, b3, ksplit, img1, b3h, pw;
+    int tile, ks, dma, stem, halo, img_ib, img_rb, img_nw, fc_small, b3, ksplit, img1, b3h, pw, dw;
 };
 inline ConvChoice get_choice(const saber_hip_conv* op) {
-    return {op->tile, op->ks, op->dma, op->stem, op->halo, op->img_ib, op->img_rb, op->img_nw, op->fc_small, op->b3, op->ksplit, op->img1, op->b3h, op->pw};
+    return {op->tile, op->ks, op->dma, op->stem, op->halo, op->img_ib, op->img_rb, op->img_nw, op->fc_small, op->b3, op->ksplit, op->img1, op->b3h, op->pw, op->dw};
 }
 inline void set_choice(saber_hip_conv* op, const ConvChoice& c) {
     op->tile = c.tile; op->ks = c.ks; op->dma = c.dma; op->stem = c.stem; op->halo = c.halo;
-    op->img_ib = c.img_ib; op->img_rb = c.img_rb; op->img_nw = c.img_nw; op->fc_small = c.fc_small; op->b3 = c.b3; op->ksplit = c.ksplit; op->img1 = c.img1 || op->gpool; op->b3h = c.b3h; op->pw = c.pw;
+    op->img_ib = c.img_ib; op->img_rb = c.img_rb; op->img_nw = c.img_nw; op->fc_small = c.fc_small; op->b3 = c.b3; op->ksplit = c.ksplit; op->img1 = c.img1 || op->gpool; op->b3h = c.b3h; op->pw = c.pw; op->dw = c.dw;
+}
+// the depthwise 3x3 kernels exist for this op (conv_dw3x3.hip): group == c == k, 3x3, dilation 1, stride 1 | 2, pad 0 | 1, 8-bit NHWC in /
+// NHWC out with C % 16 == 0 or f32 NHWC in / out with C % 4 == 0, no residual. A property of the descriptor: known at create
+inline bool dw_ok(const saber_hip_conv* op) {
+    const saber_hip_conv_desc& d = op->d;
+    if (op->algo != ALGO_DIRECT_I8 && op->algo != ALGO_DIRECT_F32) return false;
+    if (d.res_mode != SABER_HIP_RES_NONE || op->pre_quant || op->pre_pad || op->pre_transpose || d.out_layout != SABER_HIP_NHWC) return false;
+    if (op->is_i8 && op->epi != EPI_I8_CONV) return false;
+    return conv_dw3x3_ok(!op->is_i8, d.n, d.c, d.k, d.group, d.kh, d.kw, d.stride_h, d.stride_w, d.pad_h, d.pad_w, d.dil_h, d.dil_w, op->oh, op->ow);
 }
 inline bool pw_ok(const saber_hip_conv* op) {      // the persistent pointwise kernel exists for this op (planes packed by pw_prepare)
     return op->algo == ALGO_IGEMM_F32 && op->d_wpw.p != nullptr && !op->pair_k2 && !op->pool2 && conv1x1_pw_ok(op->c_eff, op->d.k);
@@ -333,6 +344,7 @@ inline unsigned long long kernel_key(const saber_hip_conv* op, const ConvChoice&
     else if (op->algo != ALGO_IGEMM_F32 && op->epi == EPI_I8_CONV && d.res_mode != SABER_HIP_RES_SUM_INPLACE && d.k % 16 == 0)
         ek = d.res_mode == SABER_HIP_RES_ELTWISE ? 2 : (d.out_dtype == SABER_HIP_U8 ? 1 : (d.out_dtype == SABER_HIP_S8 ? 0 : 3));
     unsigned long long k = (unsigned long long)op->algo | ((unsigned long long)ek << 4);
+    if (c.dw) return k | (11ull << 8) | ((unsigned long long)c.dw << 16) | ((unsigned long long)(d.stride_h == 2) << 24) | ((unsigned long long)(d.in_dtype == SABER_HIP_U8) << 25);
     if (c.pw > 1) return k | (10ull << 8) | ((unsigned long long)c.pw << 16) | ((unsigned long long)(d.res_mode == SABER_HIP_RES_SUM_INPLACE) << 32);
     if (c.pw) return k | (9ull << 8) | ((unsigned long long)op->c_eff << 16) | ((unsigned long long)(d.res_mode == SABER_HIP_RES_SUM_INPLACE) << 32);
     if (c.b3h) return k | (8ull << 8) | ((unsigned long long)c.b3h << 16);
@@ -459,6 +471,8 @@ int capture_stream_op(OpKind kind, const char* name, const int* p, int np, const
 bool halo_ok(const saber_hip_conv* op);      // api_conv.hip
 bool img_ok(const saber_hip_conv* op, int nw, int ib, int rb);      // api_conv.hip
 bool stem_ok(const saber_hip_conv* op);      // api_conv.hip
+int dw_static_form(const saber_hip_conv* op);      // api_conv.hip: create's choice among the depthwise forms
+constexpr long DW_STRIP_MIN_LANES = 150000;     // (lanes = channel vectors x output pixels. Measured, profiles/dw3x3/README.md: at 200 704 lanes and above the strip form is the faster one for both element types, at 100 352 and below the one-pixel form)
 void name_algo(saber_hip_conv* op);      // api_conv.hip
 std::string stem_pair_name(const saber_api::NetOp& o);      // api_net_optimize.hip
 void conv_fill_args(const saber_hip_conv* op, saber_mi355x::ConvKArgs& a, const void* x, void* y, const void* res);   // api_conv.hip

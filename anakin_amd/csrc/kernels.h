@@ -308,6 +308,14 @@ hipError_t launch_conv_stem_pool(int f32_in, const ConvKArgs& a, hipStream_t s);
 hipError_t launch_conv_stem_pool_pair(int f32_in, const StemPairKArgs& a, hipStream_t s);
 // Generic fallback: any C / group. w is OIHW-like repack [K][kh][kw][Cg]. mode 0 int8, 2 f32
 hipError_t launch_conv_direct(int is_f32, const ConvKArgs& a, int group, hipStream_t s);
+// Depthwise 3x3 (group == C == K, dilation 1, stride 1 | 2, pad 0 | 1, NHWC in / out, no residual; conv_dw3x3.hip): a lane owns a
+// 16-byte channel vector (C % 16 == 0 for INT8, C % 4 == 0 for FP32). a.w = the weights as [tap][C]; form 1 = strips of 4 (FP32, "rows4") / 2 (INT8,
+// "rows2") output rows per lane, form 2 = one output pixel per lane ("px"). Same bits as launch_conv_direct on these ops.
+constexpr int DW3X3_FORMS = 2;
+const char* conv_dw3x3_form_name(int form, bool f32);
+bool conv_dw3x3_ok(bool f32, int n, int c, int k, int group, int kh, int kw, int stride_h, int stride_w, int pad_h, int pad_w, int dil_h,
+                   int dil_w, int oh, int ow);
+hipError_t launch_conv_dw3x3(int form, bool f32, const ConvKArgs& a, hipStream_t s);
 
 // reads `bytes` of device memory through every XCD (autotuning: the timed launch then finds none of its operands in
 // an L2, which is how it runs inside the op list)

@@ -73,6 +73,23 @@ def vgg16_spec():
     return L
 
 
+def mobilenet_v1_spec():
+    """MobileNet v1 (width 1.0, 224 x 224): conv1 3x3 / 2, then 13 pairs of a depthwise 3x3 (`group` == channels) and a pointwise 1x1
+    convolution, every one followed by relu; global average pooling, fc, softmax. Conv dicts carry an optional `group` (absent: 1)."""
+    L = [dict(kind="conv", name="conv1", src="data", cin=3, cout=32, k=3, stride=2, pad=1, relu=True)]
+    prev, cin = "conv1", 32
+    pairs = [(1, 64), (2, 128), (1, 128), (2, 256), (1, 256), (2, 512)] + [(1, 512)] * 5 + [(2, 1024), (1, 1024)]
+    for i, (stride, cout) in enumerate(pairs):
+        dw, sep = "conv%d_dw" % (i + 2), "conv%d_sep" % (i + 2)
+        L.append(dict(kind="conv", name=dw, src=prev, cin=cin, cout=cin, k=3, stride=stride, pad=1, relu=True, group=cin))
+        L.append(dict(kind="conv", name=sep, src=dw, cin=cin, cout=cout, k=1, stride=1, pad=0, relu=True))
+        prev, cin = sep, cout
+    L.append(dict(kind="gpool", name="pool6", src=prev))
+    L.append(dict(kind="fc", name="fc7", src="pool6", cin=cin, cout=1000))
+    L.append(dict(kind="softmax", name="prob", src="fc7"))
+    return L
+
+
 def conv_macs(spec, hw=224):
     """Algorithmic MACs per image of the conv + fc layers."""
     sizes, total = {"data": hw}, 0
@@ -80,7 +97,7 @@ def conv_macs(spec, hw=224):
         if l["kind"] == "conv":
             o = (sizes[l["src"]] + 2 * l["pad"] - l["k"]) // l["stride"] + 1
             sizes[l["name"]] = o
-            total += l["cin"] * l["cout"] * l["k"] ** 2 * o * o
+            total += l["cin"] // l.get("group", 1) * l["cout"] * l["k"] ** 2 * o * o
         elif l["kind"] == "pool":
             s = sizes[l["src"]]
             rnd = np.floor if l.get("floor") else np.ceil
@@ -191,12 +208,13 @@ def fold_bn(w, bias, bn_scale, eps, mean, var, scale_w, scale_b):
 
 def build_model(name="resnet50", seed=42):
     """Seeded weights: conv ~ N(0, sqrt(2/(C*k*k))), BN gamma U(.5,1.5), beta/mean U(-.1,.1), var U(.5,1.5)."""
-    spec = {"resnet50": lambda: resnet_spec(50), "resnet101": lambda: resnet_spec(101), "vgg16": vgg16_spec}[name]()
+    spec = {"resnet50": lambda: resnet_spec(50), "resnet101": lambda: resnet_spec(101), "vgg16": vgg16_spec,
+            "mobilenet_v1": mobilenet_v1_spec}[name]()
     params, raw = {}, {}          # raw: the BatchNorm / Scale blobs before folding (what a model file holds)
     for idx, l in enumerate(spec):
         rng = np.random.default_rng(seed + idx)
         if l["kind"] == "conv":
-            c, k, ks = l["cin"], l["cout"], l["k"]
+            c, k, ks = l["cin"] // l.get("group", 1), l["cout"], l["k"]      # (a depthwise weight is [C, 1, 3, 3], std sqrt(2 / 9))
             w = (rng.standard_normal((k, c, ks, ks)) * np.sqrt(2.0 / (c * ks * ks))).astype(np.float32)
             if name == "vgg16":
                 b = (rng.uniform(-0.1, 0.1, k)).astype(np.float32)
@@ -232,7 +250,7 @@ def calibrate(model, x):
             kd = l["kind"]
             if kd == "conv":
                 w, b = model["params"][l["name"]]
-                y = Fn.conv2d(t[l["src"]], torch.from_numpy(w), torch.from_numpy(b), l["stride"], l["pad"])
+                y = Fn.conv2d(t[l["src"]], torch.from_numpy(w), torch.from_numpy(b), l["stride"], l["pad"], 1, l.get("group", 1))
                 if l["relu"]:
                     y = torch.relu(y)
             elif kd == "pool":
@@ -296,7 +314,7 @@ def build_int8_net(model, scales, batch, hw=224, fuse=True, chain=2, stage=True,
             ho = _out_hw(hin, l["k"], l["stride"], l["pad"])
             w, b = model["params"][nm]
             odt = l.get("odt", U8 if l["relu"] else S8)   # framework_spec: conv1's output dtype follows its consumer
-            p = S.ConvParam(w, b, 1, (l["pad"],) * 2, (l["stride"],) * 2, (1, 1), l["relu"])
+            p = S.ConvParam(w, b, l.get("group", 1), (l["pad"],) * 2, (l["stride"],) * 2, (1, 1), l["relu"])
             shape[nm], dtype[nm] = (ho, l["cout"]), odt
             conv = S.SaberConv2D(True).init((B, cin, hin, hin), p, dtype[l["src"]], odt, scales[l["src"]], scales[nm],
                                             in_layout=L.NCHW if dtype[l["src"]] == F32 else L.NHWC)
@@ -421,9 +439,9 @@ def build_fp32_net(model, batch, hw=224, pair_siblings=True, fuse_pool=True, sha
             hin, cin = shape[T(l["src"])]
             ho = _out_hw(hin, l["k"], l["stride"], l["pad"])
             w, b = model["params"][nm]
-            if cin != w.shape[1]:   # first layer: channels padded 3 -> 4
+            if cin != w.shape[1] * l.get("group", 1):   # first layer: channels padded 3 -> 4
                 w = np.concatenate([w, np.zeros((w.shape[0], cin - w.shape[1]) + w.shape[2:], np.float32)], 1)
-            p = S.ConvParam(w, b, 1, (l["pad"],) * 2, (l["stride"],) * 2, (1, 1), l["relu"])
+            p = S.ConvParam(w, b, l.get("group", 1), (l["pad"],) * 2, (l["stride"],) * 2, (1, 1), l["relu"])
             if "eltwise" in l:
                 # fused: accumulate onto the shortcut tensor, relu of the eltwise
                 el = next(e for e in model["spec"] if e["kind"] == "eltwise" and e["name"] == l["eltwise"])

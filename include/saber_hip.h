@@ -159,7 +159,11 @@ const char* saber_hip_conv2d_algo(const saber_hip_conv_t* op);
  *   14 FP32 pointwise (1x1 / stride 1, NHWC, K % 64 == 0) kernels without LDS staging: low byte 0 = persistent waves with their
  *      weight planes in registers (C = 64 / 128), 1..4 = the reduction split over the four waves of a workgroup (C % 128 == 0;
  *      output channels x pixels per workgroup, 32-deep slabs in flight per wave: 64x32 d1 two workgroups per CU, 32x32 d3, 64x32 d2,
- *      64x64 d2; a variant that keeps more slabs in flight than a wave has - C / 128 - is refused). */
+ *      64x64 d2; a variant that keeps more slabs in flight than a wave has - C / 128 - is refused);
+ *   16 depthwise 3x3 (group == c == k, dilation 1, stride 1 | 2, pad 0 | 1, no residual; 8-bit NHWC tensors with C % 16 == 0 or f32
+ *      NHWC tensors with C % 4 == 0): low byte 0 = the direct one-output-per-thread kernel, 1 = a strip of output rows per lane (2 rows
+ *      INT8, 4 rows FP32), 2 = one output pixel per lane. All three compute the same bits. get_tile of an eligible op always answers
+ *      in this encoding; on any other op, or for a larger low byte, set_tile returns SABER_HIP_INVALID_VALUE. */
 int saber_hip_conv2d_set_tile(saber_hip_conv_t* op, int tile);
 int saber_hip_conv2d_get_tile(const saber_hip_conv_t* op);
 int saber_hip_conv2d_autotune(saber_hip_conv_t* op, const void* x, void* y, const void* res, void* workspace,
