@@ -45,39 +45,23 @@ int saber_hip_device_ok(void) {   // the CURRENT device of the calling thread mu
 // ================================================================================================
 // convolution
 // ================================================================================================
-static void choose_tile(saber_hip_conv* op) {
+static int choose_tile(const saber_hip_conv* op) {
     // Largest tile that still yields >= ~1.5 workgroups per CU (256 CUs); otherwise the smallest.
     const long M = (long)op->d.n * op->oh * op->ow;
     const int order[] = {TILE_128x128, TILE_128x64, TILE_64x128, TILE_64x64, TILE_64x32, TILE_32x32};
-    op->tile = TILE_32x32;
     for (int t : order) {
         int bmk, bnp;
         tile_dims(t, &bmk, &bnp);
         if (bmk > round_up(op->d.k, 32) && t != TILE_32x32) continue;
         const long blocks = ((M + bnp - 1) / bnp) * ((op->d.k + bmk - 1) / bmk);
-        if (blocks >= 384) {
-            op->tile = t;
-            break;
-        }
+        if (blocks >= 384) return t;
     }
+    return TILE_32x32;
 }
-
-bool halo_ok(const saber_hip_conv* op) {
-    const saber_hip_conv_desc& d = op->d;
-    return op->algo == ALGO_IGEMM_I8 && op->epi == EPI_I8_CONV && d.kh == 3 && d.kw == 3 && d.stride_h == 1 &&
-           d.stride_w == 1 && d.dil_h == 1 && d.dil_w == 1 && d.group == 1 && op->c_eff % 64 == 0 && d.pad_h <= 1 &&
-           d.pad_w <= 1;
-}
-
-
-bool img_ok(const saber_hip_conv* op, int nw, int ib, int rb) {
-    return halo_ok(op) && !op->pair_k2 && conv3x3_img_feasible(op->c_eff, op->ow, op->oh, op->d.n, nw, ib, rb);
-}
-
-bool stem_ok(const saber_hip_conv* op) {
-    const saber_hip_conv_desc& d = op->d;
-    return op->algo == ALGO_IGEMM_I8_C4 && op->epi == EPI_I8_CONV && d.kh == 7 && d.kw == 7 && d.stride_h == 2 &&
-           d.stride_w == 2 && d.dil_h == 1 && d.dil_w == 1 && d.group == 1;
+// stage depth: as many 64-byte k-steps per barrier as the reduction has (max 4)
+static int choose_depth(const saber_hip_conv* op) {
+    const int kbytes = op->Kg * (op->algo == ALGO_IGEMM_F32 ? 4 : 1);
+    return kbytes >= 256 ? 4 : (kbytes >= 128 ? 2 : 1);
 }
 
 // STATIC default of the bf16-plane FP32 kernel: on for MFMA-bound layers (a 3x3 or larger filter over >= 64 channels and
@@ -117,16 +101,6 @@ bool xcd_round_robin() {
     state[dev] = 1;
     return true;
 }
-bool split_ok(const saber_hip_conv* op, int tile, int ks, int sh) {
-    if (sh == 0) return true;
-    if (sh < 0 || sh > 3 || !b3_tile_ok(op, tile, ks)) return false;
-    if (op->no_placement) return false;      // a net that shares its device: the splits' common XCD is a dispatch property of an idle GPU
-    const int steps = (op->Kg + 32 * ks - 1) / (32 * ks);
-    if ((steps >> sh) < 2) return false;
-    const size_t m = (size_t)op->d.n * op->oh * op->ow;
-    if ((m + 127) * ((size_t)op->d.k + 127) * 4 * 8 > ((size_t)96 << 20)) return false;   // partial buffer: <= 96 MB
-    return xcd_round_robin();
-}
 int split_prepare(saber_hip_conv* op) {
     if (op->d_part.p) return SABER_HIP_OK;
     const size_t m = (size_t)op->d.n * op->oh * op->ow;
@@ -138,52 +112,6 @@ int split_prepare(saber_hip_conv* op) {
     }
     return SABER_HIP_OK;
 }
-// A split-K launch of this operator found its splits on different XCDs (the kernel poisoned that output with NaN and counted
-// itself in the pinned word): report it as an error status NOW and run without split-K from here on.
-static int split_check(saber_hip_conv* op) {
-    if (!op->ksplit || !op->h_part_err || !*(volatile unsigned*)op->h_part_err) return SABER_HIP_OK;
-    *(volatile unsigned*)op->h_part_err = 0u;
-    op->ksplit = 0;
-    name_algo(op);
-    return fail(SABER_HIP_RUNTIME_ERROR, "FP32 split-K: in an earlier launch of this operator the splits of a tile ran on different XCDs "
-                "(that output was poisoned with NaN); split-K is now off for it");
-}
-void name_algo(saber_hip_conv* op) {
-    static const char* an[] = {"igemm_i8", "igemm_i8_c4", "igemm_f32", "direct_i8", "direct_f32"};
-    int bmk = 0, bnp = 0;
-    tile_dims(op->tile, &bmk, &bnp);
-    char buf[96];
-    if (op->stem32) snprintf(buf, sizeof buf, "stem7x7s2_maxpool3x3s2_f32_bf16x3_nchw_in");
-    else if (op->pool_fused) snprintf(buf, sizeof buf, "stem7x7s2_maxpool3x3s2_i8_4x8%s", op->pre_quant ? "_fusedquant" : "");
-    else if (op->stem) snprintf(buf, sizeof buf, "stem7x7s2_i8_8x16%s", op->pre_quant ? "_fusedquant" : "");
-    else if (op->fc_small) snprintf(buf, sizeof buf, op->algo == ALGO_IGEMM_F32 ? ((op->d_fcpart.p && !op->d_wfc.p) ? "fc_f32_splitk_16xk4" : "fc_f32_small_16xk4") : "fc_i8_small_16xk4");
-    else if (op->pw > 1) {
-        int ptm = 0, pp = 0, pd = 0, pmb = 0;
-        (void)conv1x1_pwk_variant(op->pw - 1, &ptm, &pp, &pd, &pmb);
-        snprintf(buf, sizeof buf, "pw1x1_f32_bf16x3_ksplit4_%dch_%dpx_d%d%s%s", ptm * 16, pp * 16, pd, pmb > 1 ? "_2wg" : "",
-                 op->d.res_mode == SABER_HIP_RES_SUM_INPLACE ? "+sum" : "");
-    } else if (op->pw) snprintf(buf, sizeof buf, "pw1x1_f32_bf16x3_regs_c%d_%dch_per_wave%s", op->c_eff, op->c_eff == 64 ? 64 : 32,
-                              op->d.res_mode == SABER_HIP_RES_SUM_INPLACE ? "+sum" : "");
-    else if (op->b3h) {
-        int hb, ht, htm, hthr;
-        (void)conv3x3_b3h_variant(op->b3h, &hb, &ht, &htm, &hthr);
-        if (op->b3h >= 6) snprintf(buf, sizeof buf, "pw1x1_f32_bf16x3_%dch_%dpx_w%d", hb, ht * 16, hthr / 64);
-        else snprintf(buf, sizeof buf, "halo3x3_f32_bf16x3_%dch_%dx16_w%d%s", hb, ht, hthr / 64, op->pool2 ? "+maxpool2x2" : "");
-    }
-    else if (op->img1) snprintf(buf, sizeof buf, "imgres%dx%d_i8_%dch%s", op->d.kh, op->d.kw, 16 * ((op->d.k / 16 + 31) / 32), op->gpool ? "+gpool" : "");
-    else if (op->img_rb) snprintf(buf, sizeof buf, "img3x3_i8_%dimg_x_%drows_k16_w%d", op->img_ib, op->img_rb, op->img_nw);
-    else if (op->halo) snprintf(buf, sizeof buf, "halo3x3_i8_%dx16", op->halo);
-    else if (op->dw) snprintf(buf, sizeof buf, "dw3x3_%s_%s", op->is_i8 ? "i8" : "f32", conv_dw3x3_form_name(op->dw, !op->is_i8));
-    else if (op->algo <= ALGO_IGEMM_F32)
-        snprintf(buf, sizeof buf, "%s_%dx%d_k%d%s%s%s%s", op->b3 ? "igemm_f32_bf16x3" : an[op->algo], bmk, bnp, op->ks,
-                 op->b3 && op->tile >= TILE_W8_64x64 ? "_w8" : "",
-                 op->b3 && op->ksplit ? (op->ksplit == 1 ? "_split2" : (op->ksplit == 2 ? "_split4" : "_split8")) : "",
-                 op->dma == 0 ? "" : (op->dma == 1 ? "_dma" : (op->dma == 2 ? "_dma_wg2" : "_dma_wg4")),
-                 op->pool2 ? "+maxpool2x2" : "");
-    else snprintf(buf, sizeof buf, "%s", an[op->algo]);
-    op->algo_name = std::string(op->pair_k2 ? "pair_" : "") + buf;
-}
-
 int saber_hip_conv2d_create(const saber_hip_conv_desc* desc, saber_hip_conv_t** out) {
     if (!desc || !out) return fail(SABER_HIP_INVALID_VALUE, "null argument");
     const saber_hip_conv_desc& d = *desc;
@@ -291,14 +219,15 @@ int saber_hip_conv2d_create(const saber_hip_conv_desc* desc, saber_hip_conv_t** 
         op->Kg = d.kh * d.kw * op->c_eff;
         op->Kg_pad = round_up(op->Kg, 256);    // f32 elements: 1024 B
     }
-    op->stem = stem_ok(op) ? 1 : 0;
-    op->dw = dw_ok(op) ? dw_static_form(op) : 0;
-    choose_tile(op);
-    {   // stage depth: as many 64-byte k-steps per barrier as the reduction has (max 4)
-        const int kbytes = op->Kg * (op->algo == ALGO_IGEMM_F32 ? 4 : 1);
-        op->ks = kbytes >= 256 ? 4 : (kbytes >= 128 ? 2 : 1);
+    ConvSel sel = sel_igemm(ConvSel(), choose_tile(op), choose_depth(op), 0);
+    if (op->algo > ALGO_IGEMM_F32) sel = sel_direct(sel);      // (keeps the parameters: see sel_valid)
+    if (stem_ok(op)) sel = sel_stem(sel);
+    if (dw_ok(op)) sel = sel_dw(sel, dw_static_form(op));
+    const int rc = sel_set(op, sel);
+    if (rc) {
+        delete op;
+        return rc;
     }
-    name_algo(op);
     *out = op;
     return SABER_HIP_OK;
 }
@@ -320,7 +249,7 @@ int saber_hip_conv2d_set_pooling(saber_hip_conv_t* op, int pool_type, int kh, in
         op->pool_oh = op->oh / 2;
         op->pool_ow = op->ow / 2;
         op->pool2 = 1;
-        name_algo(op);
+        sel_name(op);
         return SABER_HIP_OK;
     }
     // FP32 stem: NCHW f32 image -> 7x7 / 2 / pad 3 conv (3 -> 64) + relu -> 3x3 / 2 max pooling -> NHWC f32 as ONE launch (conv_stem_f32.hip)
@@ -339,7 +268,7 @@ int saber_hip_conv2d_set_pooling(saber_hip_conv_t* op, int pool_type, int kh, in
             op->pool_fused = 1;
             op->stem32 = 1;
             op->ws_bytes = 0;      // (no NHWC4 copy of the image any more)
-            name_algo(op);
+            sel_name(op);
             return SABER_HIP_OK;
         }
     }
@@ -354,7 +283,7 @@ int saber_hip_conv2d_set_pooling(saber_hip_conv_t* op, int pool_type, int kh, in
     if ((op->pool_oh - 1) * 2 >= op->oh || (op->pool_ow - 1) * 2 >= op->ow)
         return fail(SABER_HIP_UNIMPL, "conv+pooling: pooled shape outside the conv image");
     op->pool_fused = 1;
-    name_algo(op);
+    sel_name(op);
     return SABER_HIP_OK;
 }
 size_t saber_hip_conv2d_workspace_bytes(const saber_hip_conv_t* op) { return op->ws_bytes; }
@@ -365,135 +294,6 @@ const char* saber_hip_conv2d_algo(const saber_hip_conv_t* op) { return op->algo_
 int dw_static_form(const saber_hip_conv* op) {
     const long lanes = (long)op->d.n * op->oh * op->ow * (op->d.c / (op->is_i8 ? 16 : 4));
     return lanes >= DW_STRIP_MIN_LANES ? 1 : 2;
-}
-
-static inline bool tile_arg_ks(int ks) { return ks == 1 || ks == 2 || ks == 4; }
-// every specialised-kernel selector off (run / get_tile test img1 and b3h FIRST): a set_tile that selects one kernel family
-// starts from here, so a selection made by an earlier autotune / set_tile cannot keep running under the new one's name
-static void clear_selectors(saber_hip_conv* op) {
-    if (!op->gpool) op->img1 = 0;      // (conv + fused global pooling exists only as the image-resident kernel)
-    op->b3h = 0; op->b3 = 0; op->ksplit = 0; op->halo = 0; op->stem = 0; op->img_ib = op->img_rb = 0; op->fc_small = 0; op->pw = 0; op->dw = 0;
-}
-
-int saber_hip_conv2d_set_tile(saber_hip_conv_t* op, int tile) {
-    // tile id in the low byte, optional stage depth (k-steps per stage: 1, 2, 4) in bits 8..15,
-    // optional staging variant in bits 16..23 (1 = register-staged, 2 = LDS-DMA ring, 3 / 4 = LDS-DMA ring
-    // with 2 / 4 wave groups: needs stage depth 4 and a 32x32, 64x32 or 64x64 tile)
-    if (op->stem32) {      // FP32 stem launch: variant 15, low byte 0 = tile by launch size, 1 = 8 x 8 pooled pixels per workgroup, 2 = 4 x 8, 3 = 4 x 4
-        if (((tile >> 16) & 0xff) != 15 || (tile & 0xff) > 3) return fail(SABER_HIP_INVALID_VALUE, "FP32 stem launch: (15 << 16) | 0..3");
-        op->stem32 = 1 + (tile & 0xff);
-        return SABER_HIP_OK;
-    }
-    if (op->pool_fused) return fail(SABER_HIP_INVALID_VALUE, "fused conv+pooling has a single kernel");
-    const int ks = (tile >> 8) & 0xff;
-    const int var = (tile >> 16) & 0xff;
-    tile &= 0xff;
-    if (var == 7 || var == 8) {   // stem kernel on / off (first-layer path)
-        if (var == 7 && !stem_ok(op)) return fail(SABER_HIP_INVALID_VALUE, "stem kernel needs an INT8 7x7 stride-2 conv with <= 4 channels");
-        op->stem = var == 7;
-        tile &= 0xff;
-        if (var == 8 && tile < TILE_COUNT) op->tile = tile;
-        if (var == 8 && ((tile_arg_ks(ks)))) op->ks = ks;
-        name_algo(op);
-        return SABER_HIP_OK;
-    }
-    if (var == 11) {   // FP32 implicit GEMM on three bf16 planes (register-staged, one 32-deep slab per stage)
-        if (!b3_ok(op)) return fail(SABER_HIP_INVALID_VALUE, "bf16x3 variant: FP32 implicit-GEMM conv with C % 8 == 0 (not a sibling pair, not an fc)");
-        const int sh = ks >> 4, ksd = ks & 15;      // bits 12..15 of the code: log2 of the split-K factor
-        if (!b3_tile_ok(op, tile, ksd ? ksd : 1))     // tiles 6..9: the 8-wave forms
-            return fail(SABER_HIP_INVALID_VALUE, "bf16x3: tile 0..9, stage depth 1 (or 2 below 128x128), 256x128 only for k padded to a multiple of 256");
-        if (!split_ok(op, tile, ksd ? ksd : 1, sh)) return fail(SABER_HIP_INVALID_VALUE, "bf16x3 split-K: 2 / 4 / 8 splits with >= 2 stages each, bounded output, 8 x 32 CU device");
-        if (sh) {
-            const int rc = split_prepare(op);
-            if (rc) return rc;
-        }
-        clear_selectors(op);
-        op->b3 = 1; op->dma = 0; op->ks = ksd ? ksd : 1; op->tile = tile; op->ksplit = sh;
-        name_algo(op);
-        return SABER_HIP_OK;
-    }
-    if (var == 16) {   // depthwise 3x3: low byte 0 = the direct kernel, 1 .. DW3X3_FORMS = the forms of conv_dw3x3.hip
-        if (!dw_ok(op) || tile > DW3X3_FORMS)
-            return fail(SABER_HIP_INVALID_VALUE, "depthwise 3x3 kernels: group == c == k, 3x3, dilation 1, stride 1 | 2, pad 0 | 1, NHWC 8-bit (C % 16 == 0) "
-                                                 "or f32 (C % 4 == 0) tensors, no residual; low byte 0 (direct kernel) .. 2");
-        clear_selectors(op);
-        op->dw = tile;
-        name_algo(op);
-        return SABER_HIP_OK;
-    }
-    if (var == 14) {   // FP32 pointwise conv, C = 64 / 128: persistent waves with their weight planes in registers (conv1x1_pw.hip)
-        // low byte 0: the register-weights kernel (C = 64 / 128); 1 .. 4: the reduction-split kernel's variants (C = 128 .. 2048)
-        if (pw_prepare(op) != SABER_HIP_OK || (tile == 0 ? !pw_ok(op) : !pwk_ok(op, tile)))
-            return fail(SABER_HIP_INVALID_VALUE, "pointwise kernels: FP32 NHWC 1x1 / stride-1 conv, K % 64 == 0, C in {64, 128} (variant 0) or C % 128 == 0 (1..4)");
-        clear_selectors(op);
-        op->pw = 1 + tile; op->dma = 0;
-        name_algo(op);
-        return SABER_HIP_OK;
-    }
-    if (var == 13) {   // FP32 3x3 LDS-halo kernel on the bf16 planes, variant 1..5 in the low byte
-        if (!b3h_ok(op, tile)) return fail(SABER_HIP_INVALID_VALUE, "bf16x3 halo kernel: FP32 NHWC stride-1 conv, 3x3 pad 1 with C % 32 == 0 (variant 1..5) or 1x1 with C % 64 == 0 (6..8)");
-        clear_selectors(op);
-        op->b3h = tile; op->dma = 0;
-        name_algo(op);
-        return SABER_HIP_OK;
-    }
-    if (var == 12) {   // image-resident kernel (<= 64 pixels per image: one workgroup = one image x a channel group)
-        const int rc = img_conv_prepare(op);
-        if (rc) return rc;
-        clear_selectors(op);
-        op->img1 = 1;
-        name_algo(op);
-        return SABER_HIP_OK;
-    }
-    if (op->gpool) return fail(SABER_HIP_INVALID_VALUE, "conv + fused global pooling has a single kernel");
-    if (var == 10) {   // small-batch fc kernel
-        if (!fc_small_ok(op)) return fail(SABER_HIP_INVALID_VALUE, "small-batch fc kernel: INT8 fc with <= 16 rows and k <= 4096");
-        clear_selectors(op);
-        op->fc_small = 1;
-        name_algo(op);
-        return SABER_HIP_OK;
-    }
-    if (var == 9) {   // small-image 3x3 kernel: output rows per slab in the low byte, images per slab in bits 8..15
-        const int rb = tile, ib = ks & 0x7f, nw = (ks & 0x80) ? 8 : 4;   // bit 15: 8 waves per workgroup
-        if (!img_ok(op, nw, ib, rb))
-            return fail(SABER_HIP_INVALID_VALUE, "small-image 3x3 kernel: needs an INT8 3x3 stride-1 conv with C in {64,128,256,512} "
-                                                 "and a slab (images x rows) that fits its LDS / accumulator budget");
-        clear_selectors(op);
-        op->img_ib = ib; op->img_rb = rb; op->img_nw = nw;
-        name_algo(op);
-        return SABER_HIP_OK;
-    }
-    if (var == 5 || var == 6) {   // LDS-halo 3x3 kernel, 4 / 8 tile rows
-        if (!halo_ok(op) || op->pair_k2) return fail(SABER_HIP_INVALID_VALUE, "halo kernel needs an INT8 3x3 stride-1 conv with C % 64 == 0");
-        clear_selectors(op);
-        op->halo = var == 5 ? 4 : 8;
-        name_algo(op);
-        return SABER_HIP_OK;
-    }
-    if (var) clear_selectors(op);   // an explicit implicit-GEMM variant switches the specialised kernels off
-    if (var > 4 || (var >= 2 && op->algo == ALGO_IGEMM_I8_C4)) return fail(SABER_HIP_INVALID_VALUE, "bad staging variant");
-    if ((var >= 3 && ((ks ? ks : op->ks) != 4 || tile > TILE_64x64)) || (var == 4 && tile != TILE_32x32))
-        return fail(SABER_HIP_INVALID_VALUE, "wave groups need stage depth 4 and a tile <= 64x64 (32x32 for 4 groups)");
-    if (var) op->dma = var == 1 ? 0 : (var == 2 ? 1 : (var == 3 ? 2 : 4));
-    if (tile < 0 || tile >= TILE_COUNT || !(ks == 0 || ks == 1 || ks == 2 || ks == 4))
-        return fail(SABER_HIP_INVALID_VALUE, "bad tile id");
-    if (ks) op->ks = ks;
-    op->tile = tile;
-    name_algo(op);
-    return SABER_HIP_OK;
-}
-int saber_hip_conv2d_get_tile(const saber_hip_conv_t* op) {
-    if (dw_ok(op)) return (16 << 16) | op->dw;      // (form 0 included: an eligible op always answers in this encoding)
-    if (op->pw) return (14 << 16) | (op->pw - 1);
-    if (op->b3h) return op->b3h | (13 << 16);
-    if (op->img1) return 12 << 16;
-    if (op->fc_small) return 10 << 16;
-    if (op->b3) return op->tile | ((op->ks | (op->ksplit << 4)) << 8) | (11 << 16);
-    if (op->stem) return 7 << 16;
-    if (op->img_rb) return op->img_rb | ((op->img_ib | (op->img_nw == 8 ? 0x80 : 0)) << 8) | (9 << 16);
-    if (op->halo) return op->tile | (op->ks << 8) | ((op->halo == 4 ? 5 : 6) << 16);
-    const int var = op->dma == 0 ? 1 : (op->dma == 1 ? 2 : (op->dma == 2 ? 3 : 4));
-    return op->tile | (op->ks << 8) | (var << 16);
 }
 
 int saber_hip_conv2d_set_weights(saber_hip_conv_t* op, const void* w, int w_dtype, const float* w_scale,
@@ -635,7 +435,7 @@ int saber_hip_conv2d_set_weights(saber_hip_conv_t* op, const void* w, int w_dtyp
                 fc_f32_splitk_ok(d.n, op->c_eff, op->Kg_pad, K, false)) {
                 HIP_TRY(op->d_fcpart.alloc_zero(fc_f32_splitk_part_floats(op->c_eff, K)));
                 HIP_TRY(op->d_fcctr.alloc_zero(fc_f32_splitk_counters(K)));
-                if (op->fc_small) name_algo(op);
+                if (op->sel.fam == FAM_FC_SMALL) sel_name(op);
             }
         }
         // an fc at <= 16 batch rows is ONE pass over its weights. SABER_HIP_FC_F32_PACKED=1 (A/B): the same matrix once more
@@ -717,7 +517,10 @@ int saber_hip_conv2d_set_weights(saber_hip_conv_t* op, const void* w, int w_dtyp
             // eligible FP32 convolution (0 keeps the f32-MFMA kernels); unset: see f32_static_b3()
             const char* e = getenv("SABER_HIP_F32_BF16X3");
             const bool want = e ? (e[0] == '1') : f32_static_b3(op);
-            if (!op->weights_set && want && !op->pair_k2) { op->b3 = 1; op->ks = 1; op->dma = 0; name_algo(op); }      // (a later set_weights keeps the selection the op has)
+            if (!op->weights_set && want && !op->pair_k2) {      // (a later set_weights keeps the selection the op has)
+                const int rc = sel_set(op, sel_b3(op->sel, op->sel.tile, 1, 0));
+                if (rc) return rc;
+            }
         }
         // weights set again on a live op: the packings that are NOT made above follow the new weights too - the FP32 stem launch's planes
         // (packed by set_pooling) and the pointwise kernels' fragment-ordered planes (packed on demand from d_w3 by pw_prepare)
@@ -728,7 +531,7 @@ int saber_hip_conv2d_set_weights(saber_hip_conv_t* op, const void* w, int w_dtyp
         }
         if (op->d_wpw.p) {
             op->d_wpw.release();
-            if (op->pw) {
+            if (op->sel.fam == FAM_PW) {
                 if (!weights_b3) return fail(SABER_HIP_INVALID_VALUE, "set_weights: the selected pointwise kernel needs the bf16 planes");
                 const int rc = pw_prepare(op);
                 if (rc) return rc;
@@ -807,11 +610,13 @@ static void fill_args(const saber_hip_conv* op, ConvKArgs& a, const void* x, voi
     a.stride_h = d.stride_h; a.stride_w = d.stride_w; a.dil_h = d.dil_h; a.dil_w = d.dil_w;
     a.M = d.n * op->oh * op->ow;
     a.Kg = op->Kg; a.Kg_pad = op->Kg_pad; a.kw_pad = op->kw_pad;
-    const int estage = op->b3 ? 32 * op->ks : (op->algo == ALGO_IGEMM_F32 ? 16 : 64) * op->ks * (op->dma > 1 ? op->dma : 1);   // elements per stage
-    if (op->b3) {
+    const ConvSel& sel = op->sel;
+    const bool b3 = sel.fam == FAM_B3;
+    const int estage = b3 ? 32 * sel.ks : (op->algo == ALGO_IGEMM_F32 ? 16 : 64) * sel.ks * (sel.dma > 1 ? sel.dma : 1);   // elements per stage
+    if (b3) {
         a.w = op->d_w3.p;
         a.w_plane_chunks = (int)((size_t)round_up(d.k, 128) * op->Kg_pad / 8);
-        a.ksplit_sh = op->ksplit;
+        a.ksplit_sh = sel.ksplit;
         a.part = op->d_part.p;
         a.part_ctr = op->d_part_ctr.p;
         a.part_err = op->h_part_err;      // (unified addressing: the pinned word's host pointer is its device pointer)
@@ -870,7 +675,7 @@ int saber_hip_conv2d_run(saber_hip_conv_t* op, const void* x, void* y, const voi
     const saber_hip_conv_desc& d = op->d;
     const void* xin = x;
     if (op->gpool) return fail(SABER_HIP_INVALID_VALUE, "conv + fused global pooling: use saber_hip_conv2d_run_gpool");
-    if (op->img1) return img_conv_run(op, x, y, res, nullptr, s);
+    if (op->sel.fam == FAM_IMG1) return img_conv_run(op, x, y, res, nullptr, s);      // (no argument block: its stage descriptor holds everything)
     if (op->stem32) {
         HIP_TRY(launch_conv_stem_f32_pool_raw((const float*)x, op->d_wstem32.p, op->has_bias ? op->d_bias.p : nullptr, (float*)y, d.n, d.h, d.w, op->oh,
                                               op->ow, op->pool_oh, op->pool_ow, op->stem32 - 1, s));
@@ -883,7 +688,7 @@ int saber_hip_conv2d_run(saber_hip_conv_t* op, const void* x, void* y, const voi
         HIP_TRY(launch_conv_stem_pool(op->pre_quant ? 1 : 0, a, s));
         return SABER_HIP_OK;
     }
-    if (op->stem && op->pre_quant) {
+    if (op->sel.fam == FAM_STEM && op->pre_quant) {
         // fused: the stem kernel reads the f32 NCHW image and quantises while staging its LDS patch
         ConvKArgs a;
         fill_args(op, a, x, y, res);
@@ -905,71 +710,7 @@ int saber_hip_conv2d_run(saber_hip_conv_t* op, const void* x, void* y, const voi
     }
     ConvKArgs a;
     fill_args(op, a, xin, y, res);
-    switch (op->algo) {
-    case ALGO_IGEMM_I8:
-        if (op->fc_small) {
-            HIP_TRY(launch_fc_i8_small(a, s));
-            break;
-        }
-        if (op->img_rb) {
-            HIP_TRY(launch_conv3x3_img(a, op->img_nw, op->img_ib, op->img_rb, s));
-            break;
-        }
-        if (op->halo) {
-            HIP_TRY(launch_conv3x3_halo(op->halo, a, s));
-            break;
-        }
-        HIP_TRY(op->dma ? launch_conv_igemm_dma(0, op->tile, op->ks, op->dma, a, s) : launch_conv_igemm(0, op->tile, op->ks, a, s));
-        break;
-    case ALGO_IGEMM_I8_C4:
-        if (op->stem) HIP_TRY(launch_conv_stem(0, a, s));
-        else HIP_TRY(launch_conv_igemm(1, op->tile, op->ks, a, s));
-        break;
-    case ALGO_IGEMM_F32:
-        if (op->fc_small) {
-            if (op->d_fcpart.p && !op->d_wfc.p) {      // few output tiles: the reduction split over workgroups (fc_f32_splitk.hip)
-                HIP_TRY(launch_fc_f32_splitk(a, op->d_fcpart.p, op->d_fcctr.p, nullptr, s));
-                break;
-            }
-            if (op->d_wfc.p) a.w = op->d_wfc.p;
-            HIP_TRY(launch_fc_f32_small(a, op->d_wfc.p != nullptr, s));
-            break;
-        }
-        if (op->pw) {
-            a.w = op->d_wpw.p;
-            if (op->pw > 1) HIP_TRY(launch_conv1x1_pwk(op->pw - 1, a, s));
-            else HIP_TRY(launch_conv1x1_pw(a, s));
-            break;
-        }
-        if (op->b3h) {
-            int hb, ht, htm, hthr;
-            (void)conv3x3_b3h_variant(op->b3h, &hb, &ht, &htm, &hthr);
-            a.w = htm == 1 ? op->d_w3h1.p : op->d_w3h2.p;
-            HIP_TRY(launch_conv3x3_b3h(op->b3h, a, s));
-            break;
-        }
-        if (op->b3 && op->ksplit && !op->d_part.p) return fail(SABER_HIP_INVALID_VALUE, "split-K selected without its buffers (saber_hip_conv2d_set_tile / autotune allocate them)");
-        if (op->b3 && op->ksplit) {
-            const int rs = split_check(op);
-            if (rs) return rs;
-        }
-        if (op->b3) HIP_TRY(launch_conv_igemm(3, op->tile, op->ks, a, s));
-        else HIP_TRY(op->dma ? launch_conv_igemm_dma(2, op->tile, op->ks, op->dma, a, s) : launch_conv_igemm(2, op->tile, op->ks, a, s));
-        break;
-    case ALGO_DIRECT_I8:
-    case ALGO_DIRECT_F32:
-        if (op->dw) {
-            if (!dw_ok(op) || !op->d_wdw.p) return fail(SABER_HIP_INVALID_VALUE, "depthwise kernel selected on an op without its [tap][C] weights");
-            a.w = op->d_wdw.p;
-            HIP_TRY(launch_conv_dw3x3(op->dw, !op->is_i8, a, s));
-            break;
-        }
-        a.comp = nullptr;
-        HIP_TRY(launch_conv_direct(op->is_i8 ? 0 : 1, a, d.group, s));
-        break;
-    default: return fail(SABER_HIP_UNIMPL, "no algorithm");
-    }
-    return SABER_HIP_OK;
+    return sel_launch(op, a, s);
 }
 
 
@@ -1038,12 +779,11 @@ int saber_hip_conv2d_create_pair(const saber_hip_conv_t* a, const saber_hip_conv
         return hip_fail(e, "pair: device copies");
     }
     op->weights_set = true;
-    choose_tile(op);
-    {
-        const int kbytes = op->Kg * (op->is_i8 ? 1 : 4);
-        op->ks = kbytes >= 256 ? 4 : (kbytes >= 128 ? 2 : 1);
+    const int rc = sel_set(op, sel_igemm(ConvSel(), choose_tile(op), choose_depth(op), 0));
+    if (rc) {
+        delete op;
+        return rc;
     }
-    name_algo(op);
     *out = op;
     return SABER_HIP_OK;
 }
@@ -1054,102 +794,17 @@ int saber_hip_conv2d_run_pair(saber_hip_conv_t* op, const void* x, void* y_a, vo
     if (!op->pair_k2) return fail(SABER_HIP_INVALID_VALUE, "not a sibling pair");
     ConvKArgs a;
     fill_args(op, a, x, y_a, nullptr, y_b);
-    hipStream_t s = (hipStream_t)stream;
-    const int mode = op->is_i8 ? 0 : (op->b3 ? 3 : 2);
-    if (op->b3 && op->ksplit && !op->d_part.p) return fail(SABER_HIP_INVALID_VALUE, "split-K selected without its buffers (autotune / set_tile allocate them)");
-    if (op->b3 && op->ksplit) {
-        const int rs = split_check(op);
-        if (rs) return rs;
-    }
-    HIP_TRY(op->dma && !op->b3 ? launch_conv_igemm_dma(mode, op->tile, op->ks, op->dma, a, s) : launch_conv_igemm(mode, op->tile, op->ks, a, s));
-    return SABER_HIP_OK;
-}
-
-int saber_hip_conv2d_autotune_pair(saber_hip_conv_t* op, const void* x, void* y_a, void* y_b, saber_hip_stream_t stream,
-                                   int iters) {
-    if (!op || !op->pair_k2) return fail(SABER_HIP_INVALID_VALUE, "not a sibling pair");
-    hipStream_t s = (hipStream_t)stream;
-    EventPair ev;
-    HIP_TRY(ev.init());
-    ColdScope scope;
-    HIP_TRY(scope.enter(7));
-    std::vector<std::pair<float, ConvChoice>> pcands;
-    float best = 1e30f;
-    ConvChoice best_c = get_choice(op);   // the entry selection stays if nothing runs
-    auto time_current = [&]() {
-        if (g_cold) {
-            const float us = g_cold->run(s, [&] { return saber_hip_conv2d_run_pair(op, x, y_a, y_b, s); });
-            if (us >= 0.f) pcands.emplace_back(us, get_choice(op));
-            if (us >= 0.f && us < best) { best = us; best_c = get_choice(op); }
-            return;
-        }
-        int rc = saber_hip_conv2d_run_pair(op, x, y_a, y_b, s);
-        if (rc) return;   // a variant that does not launch is skipped
-        float ms = 0;
-        if (hipEventRecord(ev.e0, s) != hipSuccess) return;
-        for (int i = 0; i < iters; ++i) rc |= saber_hip_conv2d_run_pair(op, x, y_a, y_b, s);
-        if (rc || hipEventRecord(ev.e1, s) != hipSuccess || hipEventSynchronize(ev.e1) != hipSuccess ||
-            hipEventElapsedTime(&ms, ev.e0, ev.e1) != hipSuccess)
-            return;
-        if (ms < best) { best = ms; best_c = get_choice(op); }
-    };
-    const int ks_list[3] = {1, 2, 4};
-    const int dma_list[4] = {0, 1, 2, 4};
-    for (int vi = 0; vi < 4; ++vi)
-        for (int t = 0; t < TILE_COUNT; ++t)
-            for (int ki = 0; ki < 3; ++ki) {
-                if (dma_list[vi] > 1 && (ks_list[ki] != 4 || t > TILE_64x64)) continue;
-                if (dma_list[vi] == 4 && t != TILE_32x32) continue;
-                ConvChoice c = {t, ks_list[ki], dma_list[vi], 0, 0, 0, 0, 4, 0, 0, 0};
-                set_choice(op, c);
-                time_current();
-            }
-    if (b3_ok(op))      // FP32 pair on the bf16 matrix cores, with split-K where the reduction is deep and the pixels few
-        for (int kd = 1; kd <= 2; ++kd)
-            for (int t = 0; t < TILE_COUNT_B3; ++t) {
-                if (!b3_tile_ok(op, t, kd)) continue;
-                for (int sh = 0; sh <= 3; ++sh) {
-                    if (sh && (!split_ok(op, t, kd, sh) || split_prepare(op) != SABER_HIP_OK)) continue;
-                    int bmk, bnp;
-                    tile_dims(t, &bmk, &bnp);
-                    const long tiles = (long)((op->d.n * op->oh * op->ow + bnp - 1) / bnp) * ((op->d.k + bmk - 1) / bmk);
-                    if (sh && (tiles << sh) > 2048) continue;
-                    ConvChoice c = {t, kd, 0, 0, 0, 0, 0, 4, 0, 1, sh};
-                    set_choice(op, c);
-                    time_current();
-                }
-            }
-    set_choice(op, best_c);
-    if (g_used_kernels && best < 1e30f) {   // kernel reuse across the net's sibling pairs (see kernel_key)
-        float reuse_best = best * (1.f + g_reuse_tol);
-        for (const auto& cd : pcands) {
-            const unsigned long long key = kernel_key(op, cd.second);
-            if (cd.first <= reuse_best && std::find(g_used_kernels->begin(), g_used_kernels->end(), key) != g_used_kernels->end()) {
-                reuse_best = cd.first;
-                set_choice(op, cd.second);
-            }
-        }
-        g_used_kernels->push_back(kernel_key(op, get_choice(op)));
-    }
-    name_algo(op);
-    if (!op->ksplit) {
-        op->d_part.release();
-        op->d_part_ctr.release();
-    }
-    return saber_hip_conv2d_run_pair(op, x, y_a, y_b, s);   // both outputs hold the selected kernel's result
+    return sel_launch(op, a, (hipStream_t)stream);
 }
 
 int saber_hip_conv2d_set_global_pooling(saber_hip_conv_t* op) {
     if (!op || !op->weights_set) return fail(SABER_HIP_INVALID_VALUE, "set_weights first");
     if (op->img_stage) img_conv_release(op);
     op->gpool = 1;
-    const int rc = img_conv_prepare(op);
-    if (rc) {
+    if (sel_set(op, sel_img1(op->sel)) != SABER_HIP_OK) {
         op->gpool = 0;
         return fail(SABER_HIP_UNIMPL, "conv + global average pooling: no fused kernel for this op (run the two ops)");
     }
-    op->img1 = 1; op->halo = 0; op->img_ib = op->img_rb = 0; op->stem = 0; op->fc_small = 0;
-    name_algo(op);
     return SABER_HIP_OK;
 }
 int saber_hip_conv2d_run_gpool(saber_hip_conv_t* op, const void* x, void* y, const void* res, void* y_pool, saber_hip_stream_t stream) {

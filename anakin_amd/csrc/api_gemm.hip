@@ -187,9 +187,8 @@ int build_plan(GemmPlan* p) {
     HIP_TRY(op->d_bias.alloc_zero(K_pad));
     op->has_bias = false;
     op->weights_set = true;
-    op->b3 = 1; op->ks = 1; op->dma = 0; op->ksplit = 0;
-    op->tile = pick_tile(op, p->m, p->n);
-    name_algo(op);
+    rc = sel_set(op, sel_b3(op->sel, pick_tile(op, p->m, p->n), 1, 0));
+    if (rc) return rc;
     if (p->ta) HIP_TRY(p->a_t.alloc_zero((size_t)p->m * p->k));
     return SABER_HIP_OK;
 }

@@ -1,8 +1,9 @@
 // anakin_amd/csrc/api_internal.h - what the translation units behind include/saber_hip.h share: error reporting, device
-// buffers, the operator structs behind the opaque handles, the autotuner's kernel-selection record and timing loop, and the
+// buffers, the operator structs behind the opaque handles, the kernel-selection record, the autotuners' timing loop, and the
 // op-list executor's structs. Nothing here is part of the ABI (the entry points get their C linkage from saber_hip.h).
-//   api_conv.hip          convolution: create / set_tile / set_weights (quantise + repack) / run, sibling pairs
-//   api_autotune.hip      per-op autotuner (cold-L2 timing loop, kernel-reuse preference)
+//   api_conv.hip          convolution: create / set_weights (quantise + repack) / run, sibling pairs
+//   api_select.hip        kernel selection of a convolution: eligibility, set_tile / get_tile codes, name, launch, autotune candidates
+//   api_autotune.hip      per-op and per-pair autotuner (cold-L2 timing loop, kernel-reuse preference)
 //   api_ops.hip           fc, INT8 / FP32 GEMM, the streaming operators' wrappers
 //   api_chain.hip         conv1x1 chains (two / three convs in one launch): stream repacking, create / run
 //   api_net.hip           op-list executor: arena, lanes, hipGraph capture / replay, in-pass timing
@@ -86,6 +87,61 @@ void* zero_page();      // api_conv.hip
 
 enum Algo { ALGO_IGEMM_I8 = 0, ALGO_IGEMM_I8_C4 = 1, ALGO_IGEMM_F32 = 2, ALGO_DIRECT_I8 = 3, ALGO_DIRECT_F32 = 4 };
 
+// Which kernel a convolution launches: exactly ONE family, its parameters, and the implicit-GEMM parameters underneath. Everything that
+// interprets it is in api_select.hip; values are made by the sel_* constructors below and reach an op through sel_set alone.
+enum ConvFamily {
+    FAM_DIRECT,      // direct kernel (grouped convs, channel counts off the implicit-GEMM path)
+    FAM_IGEMM,       // implicit GEMM on the i8 / f32 matrix cores: tile, ks, dma
+    FAM_B3,          // FP32 implicit GEMM on three bf16 operand planes (conv_igemm_impl.h MODE 3, planes d_w3): tile 0..9, ks 1 | 2, ksplit
+    FAM_STEM,        // INT8 first layer: LDS-patch stem kernel (conv_stem.h) instead of the NHWC4 implicit GEMM
+    FAM_HALO,        // INT8 3x3: LDS-halo kernel (conv3x3_halo.h), variant = tile rows (4 / 8)
+    FAM_IMG,         // INT8 3x3 on small images (conv3x3_img.h): img_ib images x img_rb output rows per workgroup slab, img_nw waves (4 / 8)
+    FAM_IMG1,        // INT8, <= 64 pixels per image: image-resident kernel (stage_xcd.hip: img_conv_kernel), workgroup = one image x 16 NT channels
+    FAM_FC_SMALL,    // small-batch fc kernel (fc_small.hip)
+    FAM_B3H,         // FP32: LDS-halo bf16-plane kernel (conv3x3_b3h.hip, planes d_w3h1 / d_w3h2), variant 1..5 = 3x3 forms, 6..8 = pointwise
+    FAM_PW,          // FP32 1x1 / stride 1 (planes d_wpw): variant 0 = persistent register-weights kernel (C = 64 / 128, conv1x1_pw.hip),
+                     // 1 .. 4 = the reduction-split kernel's variants (C = 128 .. 2048, conv1x1_pwk.hip)
+    FAM_DW           // depthwise 3x3 (dw_ok): variant 1 .. DW3X3_FORMS = that form of conv_dw3x3.hip (weights d_wdw)
+};
+struct ConvSel {
+    ConvFamily fam = FAM_DIRECT;
+    // the implicit-GEMM parameters. They survive while another family is selected: get_tile reports them for a halo op, set_tile variant 8
+    // returns to them, the net-level consolidation pass swaps them
+    int tile = TILE_64x64;
+    int ks = 1;              // 64-byte k-steps per pipeline stage (1, 2, 4)
+    int dma = 0;             // 0: register-staged kernel; 1/2/4: LDS-DMA ring kernel with that many wave groups
+    int variant = 0;         // family-specific, see ConvFamily
+    int ksplit = 0;          // FAM_B3: log2 of the split-K factor (conv_igemm_impl.h: splits of one tile share an XCD), 0: none
+    int img_ib = 0, img_rb = 0, img_nw = 4;   // FAM_IMG
+};
+inline ConvSel sel_family(ConvSel base, ConvFamily fam, int variant = 0) {      // `base`: where the implicit-GEMM parameters come from
+    base.fam = fam; base.variant = variant; base.ksplit = 0; base.img_ib = base.img_rb = 0; base.img_nw = 4;
+    return base;
+}
+inline ConvSel sel_direct(const ConvSel& base) { return sel_family(base, FAM_DIRECT); }
+inline ConvSel sel_igemm(const ConvSel& base, int tile, int ks, int dma) {
+    ConvSel s = sel_family(base, FAM_IGEMM);
+    s.tile = tile; s.ks = ks; s.dma = dma;
+    return s;
+}
+inline ConvSel sel_b3(const ConvSel& base, int tile, int ks, int ksplit) {      // (register-staged, one 32-deep slab per k-step)
+    ConvSel s = sel_family(base, FAM_B3);
+    s.tile = tile; s.ks = ks; s.dma = 0; s.ksplit = ksplit;
+    return s;
+}
+inline ConvSel sel_stem(const ConvSel& base) { return sel_family(base, FAM_STEM); }
+inline ConvSel sel_halo(const ConvSel& base, int rows) { return sel_family(base, FAM_HALO, rows); }
+inline ConvSel sel_img(const ConvSel& base, int nw, int ib, int rb) {
+    ConvSel s = sel_family(base, FAM_IMG);
+    s.img_nw = nw; s.img_ib = ib; s.img_rb = rb;
+    return s;
+}
+inline ConvSel sel_img1(const ConvSel& base) { return sel_family(base, FAM_IMG1); }
+inline ConvSel sel_fc_small(const ConvSel& base) { return sel_family(base, FAM_FC_SMALL); }
+inline ConvSel sel_b3h(ConvSel base, int variant) { base.dma = 0; return sel_family(base, FAM_B3H, variant); }
+inline ConvSel sel_pw(ConvSel base, int variant) { base.dma = 0; return sel_family(base, FAM_PW, variant); }
+inline ConvSel sel_dw(const ConvSel& base, int form) { return sel_family(base, FAM_DW, form); }
+
 }  // namespace saber_api
 using namespace saber_api;
 
@@ -93,37 +149,22 @@ struct saber_hip_conv {
     saber_hip_conv_desc d;
     int oh = 0, ow = 0;
     int algo = ALGO_DIRECT_I8;
-    int tile = TILE_64x64;
-    int ks = 1;              // 64-byte k-steps per pipeline stage (1, 2, 4)
-    int dma = 0;             // 0: register-staged kernel; 1/2/4: LDS-DMA ring kernel with that many wave groups
-    int stem = 0;            // 1: LDS-patch stem kernel (conv_stem.h) instead of the NHWC4 implicit GEMM
+    ConvSel sel;             // the selected kernel (written by sel_set only)
     int pool_fused = 0, pool_oh = 0, pool_ow = 0;   // SaberConv2DPooling: fused stem conv + 3x3/2 max pooling
     int pool2 = 0;           // SaberConv2DPooling, FP32: relu'd implicit-GEMM conv + 2x2/2 max pooling in the epilogue
     int stem32 = 0;          // SaberConv2DPooling, FP32 stem (with pool_fused): NCHW image -> 7x7/2 conv + relu + 3x3/2 max pooling in ONE launch
                              // (conv_stem_f32.hip); d_wstem32 = its weight planes in MFMA fragment order, packed by set_pooling from w_stem_host
     DevBuf<uint8_t> d_wstem32;
     std::vector<float> w_stem_host;   // the OIHW f32 weights of a 3 -> 64 7x7 FP32 conv as handed to set_weights (9.4 K floats)
-    int halo = 0;            // 4 / 8: LDS-halo 3x3 kernel with that many tile rows (conv3x3_halo.h); 0: not used
-    int fc_small = 0;        // 1: small-batch fc kernel (fc_small.hip) instead of the implicit-GEMM conv kernel
-    int b3h = 0;             // FP32 3x3: 1..5 = LDS-halo bf16-plane kernel variant (conv3x3_b3h.hip), 0: not used
-    DevBuf<uint8_t> d_w3h1, d_w3h2;   // its weight planes in MFMA fragment order for 1 / 2 row tiles per wave
-    int pw = 0;              // FP32 1x1 / stride 1: 1 = persistent register-weights kernel (C = 64 / 128, conv1x1_pw.hip), 2 .. 5 = the
-                             // reduction-split kernel's variants 1 .. 4 (C = 128 .. 2048, conv1x1_pwk.hip), 0: not used
-    DevBuf<uint8_t> d_wpw;   // its weight planes in that kernel's fragment order
-    int dw = 0;              // depthwise 3x3 (dw_ok; algo stays ALGO_DIRECT_*): 1 .. DW3X3_FORMS = that form of conv_dw3x3.hip, 0: the direct kernel
-    DevBuf<uint8_t> d_wdw;   // its weights as [tap][C] (s8 / f32), packed by set_weights
+    DevBuf<uint8_t> d_w3h1, d_w3h2;   // FAM_B3H: the weight planes in MFMA fragment order for 1 / 2 row tiles per wave
+    DevBuf<uint8_t> d_wpw;   // FAM_PW: the weight planes in that kernel's fragment order
+    DevBuf<uint8_t> d_wdw;   // FAM_DW: the weights as [tap][C] (s8 / f32), packed by set_weights
     DevBuf<float> d_fcpart;  // FP32 fc at <= 16 rows and <= 2048 outputs: the split-K kernel's partial sums + arrival counters (fc_f32_splitk.hip;
     DevBuf<unsigned> d_fcctr; // allocated by set_weights when the shape is eligible AND SABER_HIP_FC_F32_SPLITK=1: opt-in, measured no faster - profiles/r06/fc_tail.txt)
     DevBuf<float> d_wfc;     // FP32 fc at <= 16 rows: the weights fragment-major for the streaming kernel (fc_small.hip: fc_f32_stream_kernel PACKED)
-    int img1 = 0;            // INT8: 1 = image-resident kernel (stage_xcd.hip: img_conv_kernel): workgroup = one image x 16 NT channels
-    int gpool = 0;           // ... with the global average pooling of its output fused (saber_hip_net_optimize flag 128): img1 only
-    struct saber_hip_stage* img_stage = nullptr;   // the single-phase descriptor + repacked weights of that kernel (img_conv_prepare)
-    int ksplit = 0;          // b3 only: log2 of the split-K factor (conv_igemm_impl.h: splits of one tile share an XCD), 0: none
+    int gpool = 0;           // the global average pooling of the output fused (saber_hip_net_optimize flag 128): pins FAM_IMG1
+    struct saber_hip_stage* img_stage = nullptr;   // FAM_IMG1: the single-phase descriptor + repacked weights of that kernel (img_conv_prepare)
     bool no_placement = false;   // the op belongs to a net that does NOT own the device (saber_hip_net_optimize flag 2048): no split-K through one XCD's L2
-    int b3 = 0;              // FP32: 1 = the implicit GEMM runs on the bf16 matrix cores (three bf16 operand planes, conv_igemm_impl.h
-                             // MODE 3): needs c_eff % 8 == 0 and the pre-split weight planes d_w3
-    int img_ib = 0, img_rb = 0, img_nw = 4;   // img_rb > 0: small-image 3x3 kernel (conv3x3_img.h): images / output rows
-                                              // per workgroup slab, waves per workgroup (4 or 8)
     int epi = EPI_I8_CONV;
     bool is_i8 = false;
     int x_dtype = DT_S8;     // dtype of the tensor the conv kernel itself reads
@@ -144,7 +185,7 @@ struct saber_hip_conv {
     DevBuf<float> d_part;    // split-K: partial accumulators [tile][split] and the tiles' arrival counters (split_prepare)
     DevBuf<unsigned> d_part_ctr;
     unsigned* h_part_err = nullptr;   // pinned, device-mapped word the split-K kernels count placement violations in (split_prepare)
-    DevBuf<uint8_t> d_w3;    // FP32 convs: the repacked weights split into three bf16 planes [3][K_pad][Kg_pad] (b3 variant)
+    DevBuf<uint8_t> d_w3;    // FP32 convs: the repacked weights split into three bf16 planes [3][K_pad][Kg_pad] (FAM_B3; needs c_eff % 8 == 0)
     DevBuf<float> d_bias, d_scale;
     DevBuf<int> d_comp;
     DevBuf<unsigned> d_sm_ctr;   // INT8 fc + softmax in one launch (fc_small.hip): the arrival counter, zero between launches
@@ -214,60 +255,6 @@ struct saber_hip_fc {
 };
 
 namespace saber_api {
-// one selection of kernel variant for an op (what the autotuner saves / restores)
-struct ConvChoice {
-    int tile, ks, dma, stem, halo, img_ib, img_rb, img_nw, fc_small, b3, ksplit, img1, b3h, pw, dw;
-};
-inline ConvChoice get_choice(const saber_hip_conv* op) {
-    return {op->tile, op->ks, op->dma, op->stem, op->halo, op->img_ib, op->img_rb, op->img_nw, op->fc_small, op->b3, op->ksplit, op->img1, op->b3h, op->pw, op->dw};
-}
-inline void set_choice(saber_hip_conv* op, const ConvChoice& c) {
-    op->tile = c.tile; op->ks = c.ks; op->dma = c.dma; op->stem = c.stem; op->halo = c.halo;
-    op->img_ib = c.img_ib; op->img_rb = c.img_rb; op->img_nw = c.img_nw; op->fc_small = c.fc_small; op->b3 = c.b3; op->ksplit = c.ksplit; op->img1 = c.img1 || op->gpool; op->b3h = c.b3h; op->pw = c.pw; op->dw = c.dw;
-}
-// the depthwise 3x3 kernels exist for this op (conv_dw3x3.hip): group == c == k, 3x3, dilation 1, stride 1 | 2, pad 0 | 1, 8-bit NHWC in /
-// NHWC out with C % 16 == 0 or f32 NHWC in / out with C % 4 == 0, no residual. A property of the descriptor: known at create
-inline bool dw_ok(const saber_hip_conv* op) {
-    const saber_hip_conv_desc& d = op->d;
-    if (op->algo != ALGO_DIRECT_I8 && op->algo != ALGO_DIRECT_F32) return false;
-    if (d.res_mode != SABER_HIP_RES_NONE || op->pre_quant || op->pre_pad || op->pre_transpose || d.out_layout != SABER_HIP_NHWC) return false;
-    if (op->is_i8 && op->epi != EPI_I8_CONV) return false;
-    return conv_dw3x3_ok(!op->is_i8, d.n, d.c, d.k, d.group, d.kh, d.kw, d.stride_h, d.stride_w, d.pad_h, d.pad_w, d.dil_h, d.dil_w, op->oh, op->ow);
-}
-inline bool pw_ok(const saber_hip_conv* op) {      // the persistent pointwise kernel exists for this op (planes packed by pw_prepare)
-    return op->algo == ALGO_IGEMM_F32 && op->d_wpw.p != nullptr && !op->pair_k2 && !op->pool2 && conv1x1_pw_ok(op->c_eff, op->d.k);
-}
-inline bool pwk_ok(const saber_hip_conv* op, int variant) {      // ... the reduction-split pointwise kernel, variant 1 .. 4
-    int tm, p, dd, mb;
-    return conv1x1_pwk_variant(variant, &tm, &p, &dd, &mb) && op->algo == ALGO_IGEMM_F32 && op->d_wpw.p != nullptr && !op->pair_k2 &&
-           !op->pool2 && conv1x1_pwk_ok(op->d.n * op->d.h * op->d.w, op->c_eff, op->d.k) && (op->c_eff >> 7) >= dd;      // (slabs in flight <= slabs per wave)
-}
-inline bool b3_ok(const saber_hip_conv* op) {   // the bf16-plane variant exists for this op (planes uploaded by set_weights)
-    return op->algo == ALGO_IGEMM_F32 && op->d_w3.p != nullptr;
-}
-// (tile, stage depth) combinations of the bf16-plane kernels: depth 2 below 128 x 128; the 256-row tile reads 256 weight rows per
-// workgroup without a row predicate, the planes are padded to multiples of 128 rows
-inline bool b3_tile_ok(const saber_hip_conv* op, int tile, int ks) {
-    if (!b3_ok(op) || tile < 0 || tile >= TILE_COUNT_B3 || (ks != 1 && ks != 2)) return false;
-    if (ks == 2 && (tile == TILE_128x128 || tile >= TILE_W8_128x128)) return false;
-    if (tile == TILE_W8_256x128 && ((op->d.k + 127) / 128) % 2 != 0) return false;
-    return true;
-}
-inline bool b3h_ok(const saber_hip_conv* op, int variant) {      // the halo variant exists for this op (planes packed by set_weights)
-    int bmk, th, tm, thr;
-    if (!conv3x3_b3h_variant(variant, &bmk, &th, &tm, &thr)) return false;
-    if ((variant >= 6) != (op->d.kh == 1)) return false;       // 1..5: the 3x3 forms, 6..8: pointwise
-    if (variant >= 6 && op->pool2) return false;
-    return op->algo == ALGO_IGEMM_F32 && (tm == 1 ? op->d_w3h1.p : op->d_w3h2.p) != nullptr && !op->pair_k2;
-}
-inline bool fc_small_ok(const saber_hip_conv* op) {
-    if (op->algo == ALGO_IGEMM_F32)   // FP32 fc: a 1x1 "conv" on a [m, 1, 1, k] NHWC tensor, plain f32 epilogue, no residual
-        return op->epi == EPI_F32 && op->d.h == 1 && op->d.w == 1 && op->d.kh == 1 && op->d.kw == 1 && !op->pre_transpose &&
-               op->d.out_layout == SABER_HIP_NHWC && op->d.res_mode == SABER_HIP_RES_NONE && !op->pair_k2 && !op->pool2 &&
-               fc_f32_small_ok(op->d.n, op->c_eff, op->Kg_pad);
-    return op->algo == ALGO_IGEMM_I8 && (op->epi == EPI_I8_FC_S8 || op->epi == EPI_I8_FC_U8) && op->d.h == 1 && op->d.w == 1 &&
-           fc_i8_small_ok(op->d.n, op->c_eff, op->Kg_pad);
-}
 struct EventPair {   // RAII: destroyed on every exit path
     hipEvent_t e0 = nullptr, e1 = nullptr;
     hipError_t init() {
@@ -331,32 +318,15 @@ struct ColdBench {
 // One ColdBench per top-level autotune call: nested calls (saber_hip_net_autotune -> saber_hip_conv2d_autotune) share it.
 // SABER_HIP_AUTOTUNE_WARM=1 in the environment restores the back-to-back timing loop (kept for A/B measurements).
 extern thread_local ColdBench* g_cold;      // api_autotune.hip
+// times whatever fn() enqueues on s: *t = the cold-L2 median in microseconds, or - warm loop - the milliseconds of warm_iters back-to-back
+// calls after one warm-up. A status; nothing is timed when fn() fails.
+int time_enqueued(hipStream_t s, const std::function<int()>& fn, int warm_iters, float* t);      // api_autotune.hip
 // Kernel reuse across the ops of one net: the FIRST launch of a given kernel function in a forward pass pays for its cold
 // code (0.3-0.6 us on most boxes of the pool, 3-9 us on some: profiles/r02/slow_box/ - repeats of the same function
 // later in the pass run at full speed), so among candidates within g_reuse_tol of the fastest the tuner prefers a
 // function another op of the net already uses. Set by saber_hip_net_autotune for the duration of its run.
 extern thread_local std::vector<unsigned long long>* g_used_kernels;      // api_autotune.hip
 constexpr float g_reuse_tol = 0.03f;
-inline unsigned long long kernel_key(const saber_hip_conv* op, const ConvChoice& c) {
-    const saber_hip_conv_desc& d = op->d;
-    int ek = 3;   // conv_igemm.hip: epilogue_kind
-    if (op->pair_k2) ek = 4;
-    else if (op->algo != ALGO_IGEMM_F32 && op->epi == EPI_I8_CONV && d.res_mode != SABER_HIP_RES_SUM_INPLACE && d.k % 16 == 0)
-        ek = d.res_mode == SABER_HIP_RES_ELTWISE ? 2 : (d.out_dtype == SABER_HIP_U8 ? 1 : (d.out_dtype == SABER_HIP_S8 ? 0 : 3));
-    unsigned long long k = (unsigned long long)op->algo | ((unsigned long long)ek << 4);
-    if (c.dw) return k | (11ull << 8) | ((unsigned long long)c.dw << 16) | ((unsigned long long)(d.stride_h == 2) << 24) | ((unsigned long long)(d.in_dtype == SABER_HIP_U8) << 25);
-    if (c.pw > 1) return k | (10ull << 8) | ((unsigned long long)c.pw << 16) | ((unsigned long long)(d.res_mode == SABER_HIP_RES_SUM_INPLACE) << 32);
-    if (c.pw) return k | (9ull << 8) | ((unsigned long long)op->c_eff << 16) | ((unsigned long long)(d.res_mode == SABER_HIP_RES_SUM_INPLACE) << 32);
-    if (c.b3h) return k | (8ull << 8) | ((unsigned long long)c.b3h << 16);
-    if (c.img1) return k | (7ull << 8) | ((unsigned long long)(op->d.kh == 3) << 16);      // one function for all image-resident shapes
-    if (c.fc_small) return k | (1ull << 8) | ((unsigned long long)((op->c_eff + 255) / 256) << 16);
-    if (c.stem) return k | (2ull << 8);
-    if (c.img_rb)   // <EK, NW, CW, NCH, GPW>: channel count and pixel groups per wave
-        return k | (3ull << 8) | ((unsigned long long)op->c_eff << 16) |
-               ((unsigned long long)((c.img_ib * c.img_rb * op->ow + 15) / 16) << 32);
-    if (c.halo) return k | (4ull << 8) | ((unsigned long long)c.halo << 16) | ((unsigned long long)(op->c_eff % 128 == 0) << 24);
-    return k | ((c.b3 ? 6ull : 5ull) << 8) | ((unsigned long long)c.tile << 16) | ((unsigned long long)c.ks << 24) | ((unsigned long long)c.dma << 32);
-}
 struct ColdScope {
     ColdBench local;
     bool owner = false;
@@ -468,20 +438,25 @@ int capture_stream_op(OpKind kind, const char* name, const int* p, int np, const
 }  // namespace saber_api
 
 // helpers one translation unit defines and another uses
-bool halo_ok(const saber_hip_conv* op);      // api_conv.hip
-bool img_ok(const saber_hip_conv* op, int nw, int ib, int rb);      // api_conv.hip
-bool stem_ok(const saber_hip_conv* op);      // api_conv.hip
+// kernel selection (api_select.hip)
+bool sel_valid(const saber_hip_conv* op, const saber_api::ConvSel& s);      // the family and its parameters exist for this op
+int sel_set(saber_hip_conv* op, const saber_api::ConvSel& s);      // the one writer of op->sel: validates, makes the family's on-demand buffers, names
+void sel_release_unused(saber_hip_conv* op);      // the buffers only a family other than the selected one reads
+void sel_name(saber_hip_conv* op);      // op->algo_name of the current selection and fused-pooling properties
+unsigned long long sel_kernel_key(const saber_hip_conv* op, const saber_api::ConvSel& s);
+int sel_launch(saber_hip_conv* op, saber_mi355x::ConvKArgs& a, hipStream_t s);
+void for_each_candidate(const saber_hip_conv* op, const saber_api::ConvSel* best, const std::function<void(const saber_api::ConvSel&)>& fn);
+bool dw_ok(const saber_hip_conv* op);
+bool stem_ok(const saber_hip_conv* op);
+bool fc_small_ok(const saber_hip_conv* op);
+bool b3_tile_ok(const saber_hip_conv* op, int tile, int ks);
 int dw_static_form(const saber_hip_conv* op);      // api_conv.hip: create's choice among the depthwise forms
 constexpr long DW_STRIP_MIN_LANES = 150000;     // (lanes = channel vectors x output pixels. Measured, profiles/dw3x3/README.md: at 200 704 lanes and above the strip form is the faster one for both element types, at 100 352 and below the one-pixel form)
-void name_algo(saber_hip_conv* op);      // api_conv.hip
 std::string stem_pair_name(const saber_api::NetOp& o);      // api_net_optimize.hip
 void conv_fill_args(const saber_hip_conv* op, saber_mi355x::ConvKArgs& a, const void* x, void* y, const void* res);   // api_conv.hip
 int stem_pool_args(const saber_hip_conv* op, const void* x, void* y, void* workspace, hipStream_t s, saber_mi355x::ConvKArgs* a);   // api_conv.hip
-// FP32 split-K (b3 kernels): 2^sh workgroups per tile; needs >= 2 stages per split, a bounded partial buffer, and the
-// workgroup -> XCD placement the hand-off relies on (checked once per device). split_prepare allocates the buffers.
-bool split_ok(const saber_hip_conv* op, int tile, int ks, int sh);      // api_conv.hip
 bool xcd_round_robin();      // api_conv.hip: workgroups 8 apart in a 1-D grid share an XCD on the current device (probed once)
-int split_prepare(saber_hip_conv* op);      // api_conv.hip
+int split_prepare(saber_hip_conv* op);      // api_conv.hip: the FP32 split-K partial buffers, arrival counters and error word
 // image-resident kernel variant of an INT8 conv on <= 64-pixel images (api_stage.hip)
 bool img_conv_ok(const saber_hip_conv* op);
 int img_conv_prepare(saber_hip_conv* op);

@@ -74,7 +74,7 @@ static int net_consolidate_kernels(saber_hip_net* net, hipStream_t s) {
     if (net->has_side) return SABER_HIP_OK;
     if (const char* e = std::getenv("SABER_HIP_NO_CONSOLIDATE"))
         if (e[0] == '1') return SABER_HIP_OK;
-    struct Site { int op; unsigned long long key; ConvChoice choice; };
+    struct Site { int op; unsigned long long key; ConvSel choice; };
     auto conv_of = [&](const NetOp& o) -> saber_hip_conv* {
         if (o.skip || (o.chain && o.use_chain) || (o.chain3 && o.use_chain3) || (o.stage && o.use_stage)) return nullptr;
         if (o.kind != OP_CONV && o.kind != OP_CONV_PAIR) return nullptr;
@@ -84,7 +84,7 @@ static int net_consolidate_kernels(saber_hip_net* net, hipStream_t s) {
     auto collect = [&]() {
         std::vector<Site> v;
         for (int i = 0; i < (int)net->ops.size(); ++i)
-            if (saber_hip_conv* c = conv_of(net->ops[i])) v.push_back({i, kernel_key(c, get_choice(c)), get_choice(c)});
+            if (saber_hip_conv* c = conv_of(net->ops[i])) v.push_back({i, sel_kernel_key(c, c->sel), c->sel});
         return v;
     };
     EventPair ev;
@@ -120,23 +120,21 @@ static int net_consolidate_kernels(saber_hip_net* net, hipStream_t s) {
         float base = 0.f, base2 = 0.f;
         int rc = forward_ms(&base);
         if (rc) return rc;
-        ConvChoice best_c = cur.choice;
+        ConvSel best_c = cur.choice;
         float best = base;
         for (const Site& a : alts) {
-            ConvChoice cc = cur.choice;
-            cc.tile = a.choice.tile; cc.ks = a.choice.ks; cc.dma = a.choice.dma;
-            set_choice(c, cc);
+            const ConvSel cc = sel_igemm(cur.choice, a.choice.tile, a.choice.ks, a.choice.dma);
             float ms = 0.f;
+            if (sel_set(c, cc) != SABER_HIP_OK) continue;
             if (forward_ms(&ms) != SABER_HIP_OK) { (void)hipGetLastError(); continue; }   // not launchable for this shape
             if (ms < best) { best = ms; best_c = cc; }
         }
-        set_choice(c, cur.choice);
+        (void)sel_set(c, cur.choice);
         if (best < base * 0.996f) {                                    // confirm against a second look at the incumbent
             rc = forward_ms(&base2);
             if (rc) return rc;
             if (best < base2 * 0.996f) {
-                set_choice(c, best_c);
-                name_algo(c);
+                (void)sel_set(c, best_c);
                 net->ops[cur.op].name = std::string("conv:") + c->algo_name;
                 sites = collect();
             }
@@ -208,22 +206,7 @@ int saber_hip_net_autotune(saber_hip_net_t* net, saber_hip_stream_t stream, int 
             for (int k = first; k <= last; ++k) rc |= net_launch(net, net->ops[k], s);
             return rc;
         };
-        auto timed = [&](float* us) -> int {
-            if (g_cold) {
-                *us = g_cold->run(s, run_all);
-                return *us < 0.f ? SABER_HIP_RUNTIME_ERROR : SABER_HIP_OK;
-            }
-            EventPair ev;                 // SABER_HIP_AUTOTUNE_WARM: 20 back-to-back repetitions
-            HIP_TRY(ev.init());
-            int rc = run_all();
-            if (rc) return rc;
-            HIP_TRY(hipEventRecord(ev.e0, s));
-            for (int it = 0; it < 20; ++it) rc |= run_all();
-            HIP_TRY(hipEventRecord(ev.e1, s));
-            HIP_TRY(hipEventSynchronize(ev.e1));
-            HIP_TRY(hipEventElapsedTime(us, ev.e0, ev.e1));
-            return rc;
-        };
+        auto timed = [&](float* t) { return time_enqueued(s, run_all, 20, t); };      // (SABER_HIP_AUTOTUNE_WARM: 20 back-to-back repetitions)
         float best = 0.f;
         int best_mode = 0, best_tn = 0;
         net_set_chain_mode(net, ia, 0);
@@ -262,22 +245,7 @@ int saber_hip_net_autotune(saber_hip_net_t* net, saber_hip_stream_t stream, int 
             for (int k = first; k <= last; ++k) rc |= net_launch(net, net->ops[k], s);
             return rc;
         };
-        auto timed = [&](float* us) -> int {
-            if (g_cold) {
-                *us = g_cold->run(s, run_all);
-                return *us < 0.f ? SABER_HIP_RUNTIME_ERROR : SABER_HIP_OK;
-            }
-            EventPair ev;
-            HIP_TRY(ev.init());
-            int rc = run_all();
-            if (rc) return rc;
-            HIP_TRY(hipEventRecord(ev.e0, s));
-            for (int it = 0; it < 20; ++it) rc |= run_all();
-            HIP_TRY(hipEventRecord(ev.e1, s));
-            HIP_TRY(hipEventSynchronize(ev.e1));
-            HIP_TRY(hipEventElapsedTime(us, ev.e0, ev.e1));
-            return rc;
-        };
+        auto timed = [&](float* t) { return time_enqueued(s, run_all, 20, t); };
         std::vector<int> modes(H0.stage_n), tns(H0.stage_n);
         for (int k = 0; k < H0.stage_n; ++k) {
             modes[k] = net_chain_mode(net, first + 3 * k + 1);

@@ -482,7 +482,7 @@ int saber_hip_net_optimize(saber_hip_net_t* net, int flags) {
             saber_hip_conv* c = (o.kind == OP_FC || o.kind == OP_FC_Q) ? (o.fc ? o.fc->conv : nullptr) : o.conv;
             if (c) {
                 c->no_placement = true;
-                if (c->ksplit) { c->ksplit = 0; name_algo(c); }
+                if (c->sel.fam == FAM_B3 && c->sel.ksplit) (void)sel_set(c, sel_b3(c->sel, c->sel.tile, c->sel.ks, 0));
             }
             for (saber_hip_chain* ch : {o.chain, o.chain3})
                 if (ch && (ch->tn == 7 || ch->tn == 15)) (void)saber_hip_conv2d_chain_set_tile(ch, 3);

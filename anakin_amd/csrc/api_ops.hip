@@ -37,14 +37,9 @@ int saber_hip_fc_create(const saber_hip_fc_desc* desc, saber_hip_fc_t** out) {
             return fail(SABER_HIP_UNIMPL, "INT8 fc needs k % 16 == 0");
         }
         fc->conv->epi = c.in_dtype == SABER_HIP_U8 ? EPI_I8_FC_U8 : EPI_I8_FC_S8;
-        if (fc_small_ok(fc->conv)) {   // STATIC choice for inference batches (<= 16 rows): the weight-streaming kernel
-            fc->conv->fc_small = 1;
-            name_algo(fc->conv);
-        }
-    } else if (fc_small_ok(fc->conv)) {   // FP32: likewise
-        fc->conv->fc_small = 1;
-        name_algo(fc->conv);
     }
+    if (fc_small_ok(fc->conv))   // STATIC choice for inference batches (<= 16 rows), INT8 and FP32: the weight-streaming kernel
+        (void)sel_set(fc->conv, sel_fc_small(fc->conv->sel));
     *out = fc;
     return SABER_HIP_OK;
 }
@@ -128,10 +123,10 @@ int saber_hip_fc_run_q(saber_hip_fc_t* fc, const int8_t* xq, float* y, saber_hip
 bool fc_softmax_ok(const saber_hip_fc* fc, bool quantised_input) {
     if (!fc || !fc->conv || (fc->pre_quant && !quantised_input)) return false;
     const saber_hip_conv* c = fc->conv;
-    if (c->fc_small && c->algo == ALGO_IGEMM_F32)      // FP32: the split-K kernel's last tile normalises the rows (fc_f32_splitk.hip)
+    if (c->sel.fam == FAM_FC_SMALL && c->algo == ALGO_IGEMM_F32)      // FP32: the split-K kernel's last tile normalises the rows (fc_f32_splitk.hip)
         return c->d_fcpart.p && !c->d_wfc.p && fc_f32_splitk_ok(c->d.n, c->c_eff, c->Kg_pad, c->d.k, true);
     const int ksw = (c->c_eff + 255) / 256;
-    return c->fc_small && c->algo == ALGO_IGEMM_I8 && (ksw == 2 || ksw == 4 || ksw == 8 || ksw == 16) &&
+    return c->sel.fam == FAM_FC_SMALL && c->algo == ALGO_IGEMM_I8 && (ksw == 2 || ksw == 4 || ksw == 8 || ksw == 16) &&
            fc_i8_small_softmax_ok(c->d.n, c->c_eff, c->Kg_pad, c->d.k);
 }
 int fc_softmax_prepare(saber_hip_fc* fc) {

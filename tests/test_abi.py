@@ -109,3 +109,37 @@ def test_descriptors_and_selection_codes_fuzzed_without_gpu(built):
     assert "plausible convs: created" in r.stdout
     created = int(r.stdout.split("plausible convs: created")[1].split(",")[0])
     assert created > 500, r.stdout[-500:]
+
+
+def test_every_accepted_selection_code_names_one_kernel_and_round_trips(built):
+    """tests/selection_dump.py --roundtrip in a subprocess (it loads the mock HIP runtime globally, which would shadow the real one for the rest
+    of this process): fourteen operators that between them reach every kernel family, 2 592 selection codes each, applied in order to one op.
+    For every code set_tile accepts, set_tile(get_tile(op)) on a FRESH op of the same descriptor is accepted and gives the same kernel name and
+    the same get_tile - a selection always names a kernel that exists, and the two directions of the code table agree. And every candidate
+    the autotuner times is a kernel some accepted code selects: the enumerator and the decoder agree on what is eligible. The candidate
+    counts are those of the hand-written loops this enumerator replaced."""
+    import subprocess
+    import sys
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "tests", "selection_dump.py"), "--roundtrip"], capture_output=True, text=True, cwd=ROOT, timeout=1200)
+    assert r.returncode == 0, r.stdout[-1500:] + r.stderr[-3000:]
+    ops, accepted, names, cands, last = [], 0, {}, {}, None
+    for ln in r.stdout.splitlines():
+        p = ln.split()
+        if p[0] == "create":
+            ops.append(p[1])
+            names[p[1]], cands[p[1]] = {p[2]}, []
+        elif p[0] == "code":
+            last = p
+            if p[3] == "rc=0":
+                names[p[1]].add(p[4])
+        elif p[0] == "roundtrip":      # follows the accepted code it belongs to
+            accepted += 1
+            assert p[1:3] == last[1:3] and last[3] == "rc=0", (last, p)
+            assert p[3:] == last[3:], "set_tile(%s) on %s gave %s; set_tile(get_tile()) on a fresh op gives %s" % (last[2], last[1], last[4:], p[3:])
+        elif p[0] == "cand":
+            cands[p[1]].append(p[2])
+    assert len(ops) == 14 and accepted > 4000, (ops, accepted)
+    for op in ops:
+        assert len(set(cands[op])) == len(cands[op]), (op, "a candidate is timed twice")
+        assert set(cands[op]) <= names[op], (op, sorted(set(cands[op]) - names[op]))
+    assert [len(cands[op]) for op in ops] == [51, 40, 47, 41, 56, 19, 61, 61, 62, 63, 41, 3, 3, 0]
