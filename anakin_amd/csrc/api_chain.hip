@@ -2,6 +2,58 @@
 #include "api_internal.h"
 
 // ------------------------------------------------------------------------------------------------
+// chain forms: THE table of what a set_tile code means. A row holds for one C and the kinds of chain in `kinds` (1X1: conv1x1 + eltwise ->
+// conv1x1 | 3X3: led by the block's conv3x3 | HEAD: conv3x3, stride 1 | 2, -> conv1x1 + eltwise | PAIR: strided head -> sibling pair). Per C the
+// rows are in the autotuner's candidate order; a chain's first row is create's default; its placement-dependent rows come last and fall back
+// to the row in front of them.
+// ------------------------------------------------------------------------------------------------
+enum : unsigned { CK_1X1 = 1, CK_3X3 = 2, CK_HEAD = 4, CK_PAIR = 8, CK_LED = CK_3X3 | CK_HEAD, CK_ANY = 15 };
+static unsigned chain_kind(const saber_hip_chain* ch) { return !ch->c3 ? CK_1X1 : (ch->b2 ? CK_PAIR : (ch->b ? CK_3X3 : CK_HEAD)); }
+static const struct { int c1; unsigned kinds; ChainForm f; } chain_forms[] = {
+    // C, kinds             code rows waves split coop stream  placement
+    {64, CK_ANY,            {4, 4, 4, 1, 1, CS_BASE, false}},
+    {64, CK_ANY,            {2, 2, 4, 1, 1, CS_BASE, false}},
+    {128, CK_1X1 | CK_LED,  {2, 2, 4, 1, 1, CS_BASE, false}},
+    {128, CK_1X1 | CK_LED,  {1, 1, 4, 1, 1, CS_BASE, false}},
+    {128, CK_1X1 | CK_LED,  {6, 2, 8, 1, 1, CS_W8, false}},
+    {128, CK_1X1 | CK_LED,  {5, 1, 8, 1, 1, CS_W8, false}},
+    {256, CK_1X1 | CK_LED,  {1, 1, 4, 1, 1, CS_BASE, false}},
+    {256, CK_1X1,           {9, 1, 4, 2, 1, CS_SPLIT, false}},
+    {256, CK_1X1,           {11, 1, 8, 2, 1, CS_SPLIT8, false}},
+    {256, CK_LED,           {3, 1, 8, 1, 1, CS_W8, false}},
+    {256, CK_3X3,           {7, 1, 8, 1, 2, CS_COOP2, true}},
+    {256, CK_3X3,           {15, 2, 8, 1, 4, CS_COOP4, true}},
+    {512, CK_1X1,           {1, 1, 4, 1, 1, CS_BASE, false}},
+    {512, CK_1X1,           {9, 1, 4, 2, 1, CS_SPLIT, false}},
+};
+static void for_each_chain_form(const saber_hip_chain* ch, const std::function<void(const ChainForm&)>& fn) {
+    for (const auto& r : chain_forms)
+        if (r.c1 == ch->c1 && (r.kinds & chain_kind(ch))) fn(r.f);
+}
+static ChainForm chain_form_where(const saber_hip_chain* ch, const std::function<bool(const ChainForm& row, const ChainForm& found)>& take) {
+    ChainForm f;
+    for_each_chain_form(ch, [&](const ChainForm& c) { if (take(c, f)) f = c; });
+    return f;
+}
+ChainForm chain_form(const saber_hip_chain* ch, int code) { return chain_form_where(ch, [&](const ChainForm& c, const ChainForm&) { return c.code == code; }); }
+ChainForm chain_form_default(const saber_hip_chain* ch) { return chain_form_where(ch, [](const ChainForm&, const ChainForm& f) { return !f.code; }); }
+ChainForm chain_form_plain(const saber_hip_chain* ch) { return chain_form_where(ch, [](const ChainForm& c, const ChainForm&) { return !c.placement; }); }
+bool chain_form_valid(const saber_hip_chain* ch, int code) {
+    const ChainForm f = chain_form(ch, code);
+    return f.code && ch->d_stream[f.stream].p && (f.coop != 4 || ch->stage1);
+}
+std::string chain_form_name(const saber_hip_chain* ch) {
+    const ChainForm& f = ch->form;
+    const std::string c = std::to_string(ch->c1), w8 = f.waves == 8 && f.coop == 1 ? "_w8" : "";
+    if (!ch->c3) return "chain1x1_c" + c + "_px" + std::to_string(16 * f.rows) + (f.split == 2 ? "_split2" : "") + w8;
+    return std::string("conv3x3+") + (ch->b2 ? "conv1x1+pair1x1_c" : (ch->b ? "chain1x1_c" : "conv1x1_c")) + c + "_" + std::to_string(f.rows) + "x16" + w8 +
+           (f.coop == 2 ? "_coop2" : "") + (f.coop == 4 ? "_coop4" : "");
+}
+void for_each_chain_candidate(const saber_hip_chain* ch, bool shared_device, const std::function<void(const ChainForm&)>& fn) {
+    for_each_chain_form(ch, [&](const ChainForm& c) { if (!(shared_device && c.placement) && chain_form_valid(ch, c.code)) fn(c); });
+}
+
+// ------------------------------------------------------------------------------------------------
 // conv1x1 chain: `a` (1x1, fused SaberEltwise epilogue, s8 out) feeding `b` (1x1, s8 / u8 out) in one launch
 // ------------------------------------------------------------------------------------------------
 static bool chain_1x1(const saber_hip_conv* o, bool sub_res_ok = false) {
@@ -176,7 +228,8 @@ saber_hip_chain::~saber_hip_chain() {
 // ------------------------------------------------------------------------------------------------
 // stage: a run of 3x3-led C = 256 chains in ONE persistent launch (conv_stage_coop.hip)
 // ------------------------------------------------------------------------------------------------
-static unsigned stage_magic(int d) { return d >= 2 ? (unsigned)((0x100000000ull + (unsigned)d - 1) / (unsigned)d) : 0u; }
+// ceil(2^32 / d) for the kernels' __umulhi divisions by a tile count; 0 for d == 1 (they then skip the division)
+static unsigned div_magic(int d) { return d >= 2 ? (unsigned)((0x100000000ull + (unsigned)d - 1) / (unsigned)d) : 0u; }
 static int stage_build(saber_hip_chain* const* chains, int n, bool per_image, saber_hip_chain_stage** out) {
     if (!chains || n <= 0 || n > saber_mi355x::STAGE4_LONG || !out) return fail(SABER_HIP_INVALID_VALUE, "stage: 1..24 chains");
     if (n > 1 && !per_image) return fail(SABER_HIP_INVALID_VALUE, "stage: several blocks need an image per XCD");
@@ -185,7 +238,7 @@ static int stage_build(saber_hip_chain* const* chains, int n, bool per_image, sa
     std::vector<saber_mi355x::StageBlk> blk;
     for (int k = 0; k < n; ++k) {
         const saber_hip_chain* ch = chains[k];
-        const uint8_t* stream = !ch ? nullptr : (ch->c1 == 256 ? ch->d_stream_coop4.p : (ch->c1 == 128 ? ch->d_stream_stage1.p : nullptr));
+        const uint8_t* stream = !ch ? nullptr : (ch->c1 == 256 ? ch->d_stream[CS_COOP4].p : (ch->c1 == 128 ? ch->d_stream_stage1.p : nullptr));
         if (!ch || ch->c1 != c0->c1 || !ch->c3 || !ch->b || !stream || ch->c3->d.stride_h != 1)
             return fail(SABER_HIP_INVALID_VALUE, "stage: every block must be a conv3x3 (stride 1) + conv1x1 + conv1x1 chain at C = 256 (or all at C = 128)");
         const saber_hip_conv_desc& da = ch->a->d;
@@ -243,7 +296,7 @@ static int stage_launch(saber_hip_chain_stage* st, const void* x, const void* re
     k.blk = st->d_blk.p; k.grp_ctr = st->d_grp_ctr.p; k.img_ctr = st->d_img_ctr.p; k.xch = st->d_xch.p; k.xcc = st->d_xcc.p; k.err = st->h_err;
     k.nblk = (int)st->chains.size(); k.N = st->n; k.H = st->h; k.W = st->w;
     k.tiles_x = st->tiles_x; k.tiles_per_img = st->tiles_per_img;
-    k.mg_tiles_x = stage_magic(st->tiles_x); k.mg_tpi = stage_magic(st->tiles_per_img); k.mg_wpi = stage_magic(st->tiles_per_img * 4);
+    k.mg_tiles_x = div_magic(st->tiles_x); k.mg_tpi = div_magic(st->tiles_per_img); k.mg_wpi = div_magic(st->tiles_per_img * 4);
     k.per_image = st->per_image;
     for (int i = 0; i < k.nblk; ++i) { k.y1[i] = y1[i]; k.y2[i] = y2[i]; }
     HIP_TRY(st->c1 == 256 ? saber_mi355x::launch_conv_stage4(k, s) : saber_mi355x::launch_conv_stage1_c128(k, s));
@@ -269,6 +322,46 @@ int saber_hip_conv2d_stage_run(saber_hip_chain_stage_t* st, const void* x, const
     for (size_t i = 0; i < st->chains.size(); ++i)
         if (!y1[i] || !y2[i]) return fail(SABER_HIP_INVALID_VALUE, "stage: an output pointer per block");
     return stage_run(st, x, res, y1, y2, (hipStream_t)stream);
+}
+// the weight stream of one layout, in the order the waves of the forms that read it consume it (conv1x1_chain.hip, conv_chain_coop.hip)
+static void pack_chain_stream(const saber_hip_chain* ch, ChainStream layout, std::vector<uint8_t>& out) {
+    const saber_hip_conv *c3 = ch->c3, *a = ch->a, *b = ch->b;
+    const int c = ch->c1, k1 = ch->k1, k2 = ch->k2, c2 = b ? b->d.c : 0, k2w = k2 / 2;
+    const int nw = layout == CS_BASE || layout == CS_SPLIT ? 4 : 8;      // waves per workgroup
+    const int8_t *w3 = c3 ? c3->wq_oihw.data() : nullptr, *wa = a->wq_oihw.data(), *wb = b ? b->wq_oihw.data() : nullptr;
+    std::vector<int8_t> wcat;       // the pair's rows one after the other
+    if (ch->b2) {
+        wcat.assign(b->wq_oihw.begin(), b->wq_oihw.end());
+        wcat.insert(wcat.end(), ch->b2->wq_oihw.begin(), ch->b2->wq_oihw.end());
+        wb = wcat.data();
+    }
+    // accumulators per channel group of the second conv: its channels per wave / 16, at most 4 (pair: 160 channels per wave = 5 groups of 32)
+    auto mfg = [&](int k) { return ch->b2 ? 2 : std::min(4, k / nw / 16); };
+    switch (layout) {
+    case CS_BASE: case CS_W8:        // per wave [3x3][1x1 + eltwise][1x1]
+        for (int w = 0; w < nw; ++w) {
+            if (c3) pack_chain_weights3(w3, c, w, out, nw);
+            pack_chain_weights(wa, k1, c, 4, w, out, 0, nw);
+            if (b) pack_chain_weights(wb, k2, c2, mfg(k2), w, out, 0, nw);
+        }
+        break;
+    case CS_SPLIT: case CS_SPLIT8:   // [half][wave]: the whole first conv, half of the second conv's channels
+        for (int half = 0; half < 2; ++half)
+            for (int w = 0; w < nw; ++w) {
+                pack_chain_weights(wa, k1, c, 4, w, out, 0, nw);
+                pack_chain_weights(wb, k2w, c2, mfg(k2w), w, out, half * k2w, nw);
+            }
+        break;
+    case CS_COOP2:      // per (half, wave) [3x3: 16 channels][1x1: 64 channels][1x1: 16 channels], each half's own k-steps first
+        for (int half = 0; half < 2; ++half)
+            for (int w = 0; w < nw; ++w) {
+                pack_chain_weights3(w3, c, w, out, nw, half * (c / 2), c / 2);
+                pack_chain_weights(wa, k1 / 2, c, 4, w, out, half * (k1 / 2), nw, half * (c / 128));
+                pack_chain_weights(wb, k2w, c2, 1, w, out, half * k2w, nw, half * (c2 / 128));
+            }
+        break;
+    default: pack_coop4_stream(c3, a, b, out);      // CS_COOP4
+    }
 }
 static int chain_build(saber_hip_conv* c3, saber_hip_conv* a, saber_hip_conv* b, saber_hip_chain_t** out, saber_hip_conv* b2 = nullptr) {
     // b == nullptr (with c3): conv3x3 + first 1x1 conv only; b2 (with c3 / stride 2 and b): b and b2 are the sibling pair that reads a's output
@@ -312,84 +405,31 @@ static int chain_build(saber_hip_conv* c3, saber_hip_conv* a, saber_hip_conv* b,
         if (!ok) return fail(SABER_HIP_INVALID_VALUE, "chain: the head must be the 3x3 pad-1 INT8 conv (C -> C, C <= 256; stride 1, or 2 in front of a lone 1x1 conv) whose 8-bit output the first 1x1 conv reads");
     }
     saber_hip_chain* ch = new saber_hip_chain();
-    const int k2 = b ? b->d.k + (pair2 ? b2->d.k : 0) : 0, c2 = b ? b->d.c : 0;
+    const int k2 = b ? b->d.k + (pair2 ? b2->d.k : 0) : 0;
     ch->c3 = c3; ch->a = a; ch->b = b; ch->b2 = b2; ch->c1 = da.c; ch->k1 = da.k; ch->k2 = k2;
-    ch->tn = conv1x1_chain_tn(da.c, da.n * a->oh * a->ow);
-    const int mfg2 = pair2 ? 2 : ((k2 / 4) / 16 >= 4 ? 4 : (k2 / 4) / 16);      // (pair: 160 channels per wave = 5 groups of 32)
-    std::vector<int8_t> wcat;       // the pair's rows one after the other
-    if (pair2) {
-        wcat.assign(b->wq_oihw.begin(), b->wq_oihw.end());
-        wcat.insert(wcat.end(), b2->wq_oihw.begin(), b2->wq_oihw.end());
-    }
-    std::vector<uint8_t> stream, p0, p1, p2;
-    stream.reserve((size_t)da.k * da.c + (size_t)k2 * c2 + (c3 ? (size_t)9 * da.c * da.c : 0));
-    for (int w = 0; w < 4; ++w) {
-        if (c3) pack_chain_weights3(c3->wq_oihw.data(), da.c, w, stream);
-        pack_chain_weights(a->wq_oihw.data(), da.k, da.c, 4, w, stream);
-        if (b) pack_chain_weights(pair2 ? wcat.data() : b->wq_oihw.data(), k2, c2, mfg2, w, stream);
+    ch->form = chain_form_default(ch);
+    // one stream per layout that some form of this chain reads; the placement-dependent ones only where the device places workgroups the
+    // way their hand-off relies on (probed once per device)
+    std::vector<uint8_t> p0, p1, p2;
+    hipError_t e = hipSuccess;
+    for (int l = 0; l < CS_COUNT && e == hipSuccess; ++l) {
+        bool needed = false;
+        for_each_chain_form(ch, [&](const ChainForm& f) { needed = needed || (f.stream == l && (!f.placement || xcd_round_robin())); });
+        if (!needed) continue;
+        std::vector<uint8_t> stream;
+        pack_chain_stream(ch, (ChainStream)l, stream);
+        e = ch->d_stream[l].upload(stream);
     }
     pack_chain_params(a, (size_t)da.k / 4 * 3, p1);
-    if (b) pack_chain_params(b, ((size_t)k2 / 4 * 3 + 63) / 64 * 64 + 64, p2);      // (+ 64 chunks of slack: the cooperative kernel
-                                                                                     // DMAs whole 64-chunk blocks from a half's offset)
+    if (b) pack_chain_params(b, ((size_t)k2 / 4 * 3 + 63) / 64 * 64 + 64, p2);      // (+ 64 chunks of slack: the cooperative kernel DMAs whole 64-chunk blocks)
     if (pair2) {                    // b2's constants behind b's (48 bytes per 4 channels)
         std::vector<uint8_t> pb2;
         pack_chain_params(b2, (size_t)b2->d.k / 4 * 3, pb2);
         std::memcpy(p2.data() + (size_t)b->d.k / 4 * 48, pb2.data(), pb2.size());
     }
-    hipError_t e = ch->d_stream.upload(stream);
-    if (e == hipSuccess && !c3 && da.c >= 256) {
-        std::vector<uint8_t> sp;
-        sp.reserve(2 * (size_t)da.k * da.c + (size_t)k2 * c2);
-        const int k2w = k2 / 2, mfgw = (k2w / 4) / 16 >= 4 ? 4 : (k2w / 4) / 16;
-        for (int half = 0; half < 2; ++half)
-            for (int w = 0; w < 4; ++w) {
-                pack_chain_weights(a->wq_oihw.data(), da.k, da.c, 4, w, sp);
-                pack_chain_weights(b->wq_oihw.data(), k2w, c2, mfgw, w, sp, half * k2w);
-            }
-        e = ch->d_stream_split.upload(sp);
-        if (e == hipSuccess && da.c == 256) {   // 8 waves: 128 first-conv channels (2 groups) and 16 second-conv channels per wave
-            std::vector<uint8_t> s8;
-            s8.reserve(sp.size());
-            for (int half = 0; half < 2; ++half)
-                for (int w = 0; w < 8; ++w) {
-                    pack_chain_weights(a->wq_oihw.data(), da.k, da.c, 4, w, s8, 0, 8);
-                    pack_chain_weights(b->wq_oihw.data(), k2w, c2, 1, w, s8, half * k2w, 8);
-                }
-            e = ch->d_stream_split8.upload(s8);
-        }
-    }
-    if (e == hipSuccess && (da.c == 128 || (da.c == 256 && c3))) {
-        // 8 waves: C = 128: 16 channels of the 3x3 / 64 of the first / 16 of the second 1x1 conv per wave; C = 256 (3x3-led forms only):
-        // 32 / 128 / 32 (two accumulators per group of the second conv)
-        std::vector<uint8_t> s8;
-        s8.reserve(stream.size());
-        for (int w = 0; w < 8; ++w) {
-            if (c3) pack_chain_weights3(c3->wq_oihw.data(), da.c, w, s8, 8);
-            pack_chain_weights(a->wq_oihw.data(), da.k, da.c, 4, w, s8, 0, 8);
-            if (b) pack_chain_weights(b->wq_oihw.data(), k2, c2, da.c == 128 ? 1 : 2, w, s8, 0, 8);
-        }
-        e = ch->d_stream_w8.upload(s8);
-    }
-    if (e == hipSuccess && da.c == 256 && c3 && b && c3->d.stride_h == 1 && xcd_round_robin()) {
-        // cooperative form (conv_chain_coop.hip): per (half, wave) [3x3: 16 channels][1x1: 64 channels][1x1: 16 channels]; tiles of one
-        // row x 16 columns; needs the workgroup -> XCD placement the hand-off relies on (probed once per device)
-        std::vector<uint8_t> sc;
-        sc.reserve(stream.size());
-        for (int half = 0; half < 2; ++half)
-            for (int w = 0; w < 8; ++w) {
-                pack_chain_weights3(c3->wq_oihw.data(), da.c, w, sc, 8, half * (da.c / 2), da.c / 2);
-                pack_chain_weights(a->wq_oihw.data(), da.k / 2, da.c, 4, w, sc, half * (da.k / 2), 8, half * (da.c / 128));
-                pack_chain_weights(b->wq_oihw.data(), k2 / 2, c2, 1, w, sc, half * (k2 / 2), 8, half * (c2 / 128));
-            }
+    if (e == hipSuccess && ch->d_stream[CS_COOP2].p) {      // tiles of one row x 16 columns
         ch->coop_tiles = da.n * da.h * ((da.w + 15) / 16);
-        e = ch->d_stream_coop.upload(sc);
-        if (e == hipSuccess) {
-            std::vector<uint8_t> s4;
-            s4.reserve(stream.size());
-            pack_coop4_stream(c3, a, b, s4);
-            e = ch->d_stream_coop4.upload(s4);
-        }
-        if (e == hipSuccess) e = ch->d_coop_ctr.alloc_zero((size_t)ch->coop_tiles * 32);      // a 128-byte line per (tile, barrier)
+        e = ch->d_coop_ctr.alloc_zero((size_t)ch->coop_tiles * 32);      // a 128-byte line per (tile, barrier)
         if (e == hipSuccess) e = ch->d_coop_xcc.alloc_zero((size_t)ch->coop_tiles * 32);
         if (e == hipSuccess) e = ch->d_coop_xch.alloc_zero((size_t)ch->coop_tiles * 16 * da.c);
         if (e == hipSuccess) e = hipHostMalloc((void**)&ch->h_coop_err, sizeof(unsigned), hipHostMallocMapped);
@@ -397,7 +437,6 @@ static int chain_build(saber_hip_conv* c3, saber_hip_conv* a, saber_hip_conv* b,
     }
     if (e == hipSuccess && da.c == 128 && c3 && b && c3->d.stride_h == 1 && xcd_round_robin()) {
         std::vector<uint8_t> s1;
-        s1.reserve(stream.size());
         pack_stage1_c128_stream(c3, a, b, s1);
         e = ch->d_stream_stage1.upload(s1);
     }
@@ -411,9 +450,8 @@ static int chain_build(saber_hip_conv* c3, saber_hip_conv* a, saber_hip_conv* b,
         delete ch;
         return hip_fail(e, "chain: device copies");
     }
-    if (ch->d_stream_coop4.p) {      // tile 15: the four-workgroup form = a one-block stage, tiles spread over all XCDs
-        saber_hip_chain* one[1] = {ch};
-        int rc = stage_build(one, 1, false, &ch->stage1);
+    if (ch->d_stream[CS_COOP4].p) {      // the four-workgroup form = a one-block stage, tiles spread over all XCDs
+        const int rc = stage_build(&ch, 1, false, &ch->stage1);
         if (rc != SABER_HIP_OK) {
             delete ch;
             return rc;
@@ -438,16 +476,11 @@ int saber_hip_conv2d_chain_create3_pair(saber_hip_conv_t* conv3x3, saber_hip_con
 void saber_hip_conv2d_chain_destroy(saber_hip_chain_t* ch) { delete ch; }
 int saber_hip_conv2d_chain_set_tile(saber_hip_chain_t* ch, int tn) {
     if (!ch) return fail(SABER_HIP_INVALID_VALUE, "null argument");
-    if (ch->b2 && tn != 4 && tn != 2) return fail(SABER_HIP_INVALID_VALUE, "chain: the strided head + pair form has 2 or 4 tile rows");
-    const bool ok = (ch->c1 == 64 && (tn == 4 || tn == 2)) || (ch->c1 == 128 && (tn == 2 || tn == 1)) || (ch->c1 >= 256 && tn == 1) ||
-                    (ch->c1 == 128 && (tn == 6 || tn == 5) && ch->d_stream_w8.p) || (ch->c1 == 256 && tn == 3 && ch->c3 && ch->d_stream_w8.p) ||
-                    (ch->c1 >= 256 && tn == 9 && ch->d_stream_split.p && ch->b) || (tn == 11 && ch->d_stream_split8.p && ch->b) ||
-                    (ch->c1 == 256 && tn == 7 && ch->d_stream_coop.p) || (ch->c1 == 256 && tn == 15 && ch->stage1);
-    if (!ok) return fail(SABER_HIP_INVALID_VALUE, "chain: no kernel with that many pixel fragments");
-    ch->tn = tn;
+    if (!chain_form_valid(ch, tn)) return fail(SABER_HIP_INVALID_VALUE, "chain: no kernel form with that code for this chain");
+    ch->form = chain_form(ch, tn);
     return SABER_HIP_OK;
 }
-int saber_hip_conv2d_chain_get_tile(const saber_hip_chain_t* ch) { return ch ? ch->tn : 0; }
+int saber_hip_conv2d_chain_get_tile(const saber_hip_chain_t* ch) { return ch ? ch->form.code : 0; }
 int saber_hip_conv2d_chain_run(saber_hip_chain_t* ch, const void* x, const void* res, void* y_a, void* y_b,
                                saber_hip_stream_t stream) {
     return saber_hip_conv2d_chain_run3(ch, x, res, y_a, y_b, nullptr, stream);
@@ -456,13 +489,12 @@ int saber_hip_conv2d_chain_run3(saber_hip_chain_t* ch, const void* x, const void
                                 saber_hip_stream_t stream) {
     if (g_capture) return capture_unsupported("saber_hip_conv2d_chain_run (saber_hip_net_optimize forms chains itself)");
     if (!ch || !x || !res || !y_a || (ch->b && !y_b) || (ch->b2 && !y_c)) return fail(SABER_HIP_INVALID_VALUE, "null argument");
-    const saber_hip_conv* a = ch->a;
-    const saber_hip_conv* b = ch->b;
+    const saber_hip_conv *a = ch->a, *b = ch->b;
     ChainKArgs k;
     std::memset(&k, 0, sizeof k);
     k.x = x; k.res = res;
-    k.wstream = ch->tn == 11 ? ch->d_stream_split8.p : ((ch->tn & 8) ? ch->d_stream_split.p : ch->d_stream.p);
-    if ((ch->c1 == 128 && (ch->tn & 4)) || (ch->c1 == 256 && ch->tn == 3)) k.wstream = ch->d_stream_w8.p;
+    const ChainForm f = ch->form;
+    k.wstream = ch->d_stream[f.stream].p;
     k.prm1 = ch->d_prm1.p;
     k.prm2 = ch->d_prm2.p;
     k.y1 = y_a; k.y2 = y_b;
@@ -481,50 +513,38 @@ int saber_hip_conv2d_chain_run3(saber_hip_chain_t* ch, const void* x, const void
         k.relu2b = ch->b2->d.act == SABER_HIP_ACT_RELU;
         k.out_u8_2b = ch->b2->d.out_dtype == SABER_HIP_U8;
     }
-    if (ch->c3) {   // x is the 3x3 conv's input; tiles of tn rows x 16 columns
-        auto magic = [](int d) { return d >= 2 ? (unsigned)((0x100000000ull + (unsigned)d - 1) / (unsigned)d) : 0u; };
+    if (ch->c3) {   // x is the 3x3 conv's input; tiles of f.rows rows x 16 columns
         k.prm0 = ch->d_prm0.p;
         k.zero = zero_page();
         if (!k.zero) return fail(SABER_HIP_RUNTIME_ERROR, "chain: zero page");
         k.N = a->d.n; k.H = a->d.h; k.W = a->d.w;
         k.tiles_x = (k.W + 15) / 16;
-        // tile rows (C = 128: bit 2 of the code = 8 waves; C = 256: one row, code 3 = 8 waves, 7 = two cooperating workgroups; 15 = four, two rows)
-        const int rows = ch->c1 == 128 ? ch->tn & 3 : (ch->c1 == 256 ? (ch->tn == 15 ? 2 : 1) : ch->tn & 7);
-        k.tiles_per_img = k.tiles_x * ((k.H + rows - 1) / rows);
-        k.mg_tiles_x = magic(k.tiles_x);
-        k.mg_tpi = magic(k.tiles_per_img);
+        k.tiles_per_img = k.tiles_x * ((k.H + f.rows - 1) / f.rows);
+        k.mg_tiles_x = div_magic(k.tiles_x);
+        k.mg_tpi = div_magic(k.tiles_per_img);
         k.in0_u8 = ch->c3->x_dtype == DT_U8;
         k.relu0 = ch->c3->d.act == SABER_HIP_ACT_RELU;
         k.s0 = ch->c3->d.stride_h;
         k.H0 = ch->c3->d.h; k.W0 = ch->c3->d.w;
         if (a->d.res_stride > 1) { k.res_sub = a->d.res_stride; k.res_H = a->d.res_h; k.res_W = a->d.res_w; }
     }
-    if (ch->c1 == 256 && ch->tn == 15) {      // four cooperating workgroups per tile of 2 x 16 pixels: a one-block stage
-        void* y1s[1] = {y_a};
-        void* y2s[1] = {y_b};
-        const int rc = stage_run(ch->stage1, x, res, y1s, y2s, (hipStream_t)stream);
-        if (rc != SABER_HIP_OK) ch->tn = 3;
+    if (f.coop == 4) {      // four cooperating workgroups per tile of 2 x 16 pixels: a one-block stage
+        const int rc = stage_run(ch->stage1, x, res, &y_a, &y_b, (hipStream_t)stream);
+        if (rc != SABER_HIP_OK) ch->form = chain_form_plain(ch);
         return rc;
     }
-    if (ch->c1 == 256 && ch->tn == 7) {      // two cooperating workgroups per pixel tile
+    if (f.coop == 2) {      // two cooperating workgroups per pixel tile
         if (*(volatile unsigned*)ch->h_coop_err) {      // an earlier launch found its halves on different XCDs or timed out in a barrier
             *(volatile unsigned*)ch->h_coop_err = 0u;
-            ch->tn = 3;
+            ch->form = chain_form_plain(ch);
             return fail(SABER_HIP_RUNTIME_ERROR, "cooperative chain: an earlier launch's workgroup pairs did not share an XCD or timed out at their "
                         "barrier (its outputs are not valid); the chain now runs the single-workgroup form");
         }
-        CoopKArgs ck;
-        ck.c = k;
-        ck.c.wstream = ch->d_stream_coop.p;
-        ck.coop_ctr = ch->d_coop_ctr.p;
-        ck.coop_xch = ch->d_coop_xch.p;
-        ck.coop_xcc = ch->d_coop_xcc.p;
-        ck.coop_err = ch->h_coop_err;
-        ck.n_tiles = ch->coop_tiles;
+        const CoopKArgs ck{k, ch->d_coop_ctr.p, ch->d_coop_xch.p, ch->d_coop_xcc.p, ch->h_coop_err, ch->coop_tiles};
         HIP_TRY(launch_conv_chain_coop(ck, (hipStream_t)stream));
         return SABER_HIP_OK;
     }
-    HIP_TRY(launch_conv1x1_chain(k, ch->c1, ch->k1, ch->k2, ch->tn, ch->c3 ? 1 : 0, (hipStream_t)stream));
+    HIP_TRY(launch_conv1x1_chain(k, ch->c1, ch->k1, ch->k2, f.rows, f.waves, f.split, ch->c3 ? 1 : 0, (hipStream_t)stream));
     return SABER_HIP_OK;
 }
 

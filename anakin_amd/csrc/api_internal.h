@@ -5,7 +5,7 @@
 //   api_select.hip        kernel selection of a convolution: eligibility, set_tile / get_tile codes, name, launch, autotune candidates
 //   api_autotune.hip      per-op and per-pair autotuner (cold-L2 timing loop, kernel-reuse preference)
 //   api_ops.hip           fc, INT8 / FP32 GEMM, the streaming operators' wrappers
-//   api_chain.hip         conv1x1 chains (two / three convs in one launch): stream repacking, create / run
+//   api_chain.hip         conv1x1 chains (two / three convs in one launch): the table of launch forms, stream repacking, create / run
 //   api_net.hip           op-list executor: arena, lanes, hipGraph capture / replay, in-pass timing
 //   api_net_optimize.hip  executor-level fusions (saber_hip_net_optimize)
 //   api_net_autotune.hip  whole-net autotuner, selection save / restore
@@ -206,22 +206,31 @@ struct saber_hip_stem_pair {
     DevBuf<uint8_t> d_w, d_prm;
 };
 
-// two 1x1 INT8 convs in one launch (conv1x1_chain.hip); refers to the two ops, owns the repacked stream
+// Which kernel a chain launches: the decoded meaning of a saber_hip_conv2d_chain_set_tile code FOR ONE CHAIN (the same code names different forms
+// at different C). The one table from (C, kind of chain, code) to a form is chain_forms in api_chain.hip; everything else reads these fields.
+enum ChainStream { CS_BASE, CS_SPLIT, CS_SPLIT8, CS_W8, CS_COOP2, CS_COOP4, CS_COUNT };      // weight-stream layouts (api_chain.hip: pack_chain_stream)
+struct ChainForm {
+    int code = 0;            // the public code (bits 24..27 of saber_hip_net_get_choice); 0: no such form
+    int rows = 0;            // 3x3-led: rows of the 16-column pixel tile; 1x1 chain: 16-pixel fragments per workgroup
+    int waves = 4;           // per workgroup (4 | 8)
+    int split = 1;           // workgroups the second conv's output channels are split over (1 | 2)
+    int coop = 1;            // cooperating workgroups per tile (1 | 2: conv_chain_coop.hip | 4: a one-block stage, conv_stage_coop.hip)
+    ChainStream stream = CS_BASE;
+    bool placement = false;  // relies on where the hardware places workgroups: never on a shared device, falls back to chain_form_plain
+};
+
+// two 1x1 INT8 convs in one launch (conv1x1_chain.hip); refers to the two ops, owns the repacked streams
 struct saber_hip_chain {
     saber_hip_conv* c3 = nullptr;   // the block's 3x3 conv in front of `a` (saber_hip_conv2d_chain_create3), or null
     saber_hip_conv* a = nullptr;
     saber_hip_conv* b = nullptr;
     saber_hip_conv* b2 = nullptr;   // strided head + sibling pair (saber_hip_conv2d_chain_create3_pair): b and b2 both read a's output
-    int c1 = 0, k1 = 0, k2 = 0, tn = 0;
-    DevBuf<uint8_t> d_stream, d_prm0, d_prm1, d_prm2;
-    DevBuf<uint8_t> d_stream_split;   // 1x1 chains with C >= 256: [half][wave] streams for the split second conv (tile | 8)
-    DevBuf<uint8_t> d_stream_split8;  // C == 256: the same for 8 waves per workgroup (tile 11)
-    DevBuf<uint8_t> d_stream_w8;      // C == 128: the whole stream for 8 waves per workgroup (tile | 4)
-    // C == 256, 3x3-led, tile 7: two cooperating workgroups per pixel tile (conv_chain_coop.hip): [half][wave] streams, the pairs'
-    // arrival counters, the exchange buffer of the 3x3 conv's tile, the halves' XCC ids, and the pinned error word
-    // tile 15: FOUR cooperating workgroups per tile of 2 rows x 16 columns (conv_stage_coop.hip with one block): [quarter][wave]
-    // streams here, everything else in `stage1`
-    DevBuf<uint8_t> d_stream_coop, d_stream_coop4, d_coop_xch;
+    int c1 = 0, k1 = 0, k2 = 0;
+    ChainForm form;                 // the selected form (written by chain_build, set_tile and the fall-back from a placement-dependent form)
+    DevBuf<uint8_t> d_stream[CS_COUNT];   // one stream per layout that some form of this chain reads (chain_build)
+    DevBuf<uint8_t> d_prm0, d_prm1, d_prm2;
+    // CS_COOP2: the pairs' arrival counters, the 3x3 conv's exchange tile, the halves' XCC ids, the pinned error word; CS_COOP4: all but the streams is in `stage1`
+    DevBuf<uint8_t> d_coop_xch;
     DevBuf<uint8_t> d_stream_stage1;  // C == 128, 3x3-led with a second 1x1 conv: per-wave streams of the one-workgroup-per-tile stage kernel
     DevBuf<unsigned long long> d_coop_ctr;
     DevBuf<unsigned> d_coop_xcc;
@@ -472,4 +481,11 @@ void net_set_chain_mode(saber_hip_net* net, int ia, int mode);      // api_net_o
 int net_chain_mode(const saber_hip_net* net, int ia);      // api_net_optimize.hip
 // the stage headed by ops[i0] (NetOp::stage) on / off: on forces every block's 3x3-led chain form and makes ops[i0] launch them all
 void net_set_stage(saber_hip_net* net, int i0, bool on);   // api_net_optimize.hip
+// chain forms (api_chain.hip)
+ChainForm chain_form(const saber_hip_chain* ch, int code);      // the table: what `code` means for this chain, code 0 if nothing
+bool chain_form_valid(const saber_hip_chain* ch, int code);      // the form exists for this chain and its stream is packed
+ChainForm chain_form_default(const saber_hip_chain* ch);      // create's choice
+ChainForm chain_form_plain(const saber_hip_chain* ch);      // what a placement-dependent form falls back to
+std::string chain_form_name(const saber_hip_chain* ch);      // of the selected form
+void for_each_chain_candidate(const saber_hip_chain* ch, bool shared_device, const std::function<void(const ChainForm&)>& fn);
 int stage_run(saber_hip_chain_stage* st, const void* x, const void* res, void* const* y1, void* const* y2, hipStream_t s);   // api_chain.hip

@@ -704,7 +704,7 @@ int saber_hip_net_status(saber_hip_net_t* net) {
             for (unsigned* w : words)
                 if (w && *(volatile unsigned*)w) {
                     *(volatile unsigned*)w = 0u;
-                    if (ch->tn == 7 || ch->tn == 15) (void)saber_hip_conv2d_chain_set_tile(ch, 3);
+                    if (ch->form.placement) ch->form = chain_form_plain(ch);
                     ++bad;
                 }
         }

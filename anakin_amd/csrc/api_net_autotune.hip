@@ -16,8 +16,8 @@ static saber_hip_conv* net_op_conv(saber_hip_net* net, int index) {
 int saber_hip_net_get_choice(saber_hip_net_t* net, int index) {
     saber_hip_conv* c = net_op_conv(net, index);
     int choice = (c && !c->pool_fused && (c->algo <= ALGO_IGEMM_F32 || dw_ok(c))) ? saber_hip_conv2d_get_tile(c) : 0;
-    if (c && net->ops[index].chain) choice |= (1 << 28) | ((net->ops[index].use_chain ? net->ops[index].chain->tn : 0) << 24);
-    if (c && net->ops[index].chain3) choice |= (1 << 29) | ((net->ops[index].use_chain3 ? net->ops[index].chain3->tn : 0) << 24);
+    if (c && net->ops[index].chain) choice |= (1 << 28) | ((net->ops[index].use_chain ? net->ops[index].chain->form.code : 0) << 24);
+    if (c && net->ops[index].chain3) choice |= (1 << 29) | ((net->ops[index].use_chain3 ? net->ops[index].chain3->form.code : 0) << 24);
     if (c && net->ops[index].stage && net->ops[index].use_stage) choice |= 1 << 30;      // this op launches its whole stage
     return choice;
 }
@@ -30,28 +30,25 @@ int saber_hip_net_set_choice(saber_hip_net_t* net, int index, int choice) {
     if (!c || !choice || c->pool_fused || (c->algo > ALGO_IGEMM_F32 && !dw_ok(c))) return SABER_HIP_OK;
     if (net->reproducible_fp32 && !c->is_i8) return SABER_HIP_OK;      // flag 8192: a restored selection does not move FP32 ops either
     if (net->ops[index].kind == OP_CONV_PAIR && index > 0 && net->ops[index - 1].stem_pair) return SABER_HIP_OK;      // no kernel of its own (flag 512)
-    int chain_bits = (choice >> 24) & 63;
+    const int chain_bits = (choice >> 24) & 63;
     const bool stage_on = ((choice >> 30) & 1) && !net->shared_device;
     choice &= 0xffffff;
-    if (net->shared_device) {      // a selection tuned on a net that owned its device: placement-dependent variants are mapped to their plain forms
-        if (((choice >> 16) & 0xff) == 11) choice &= ~(0xf << 12);                           // bf16-plane kernel: split-K off
-        if ((chain_bits & 15) == 7 || (chain_bits & 15) == 15) chain_bits = (chain_bits & ~15) | 3;   // cooperating chains -> one workgroup per tile, 8 waves
-    }
+    // a selection tuned on a net that owned its device: placement-dependent variants are mapped to their plain forms (bf16-plane kernel: split-K off)
+    if (net->shared_device && ((choice >> 16) & 0xff) == 11) choice &= ~(0xf << 12);
+    NetOp& o = net->ops[index];
+    // the chain decision this choice carries: a 3x3 head (bit 29) is restored before its chain head (bit 28, the next op): set_choices runs in
+    // op order. A code with no form for that chain is refused before anything changes.
+    saber_hip_chain* ch = index + 1 >= (int)net->ops.size() ? nullptr : ((o.chain3 && (chain_bits & 32)) ? o.chain3 : ((o.chain && (chain_bits & 16)) ? o.chain : nullptr));
+    int tn = chain_bits & 15;      // 0: the chain off
+    if (ch && net->shared_device && chain_form(ch, tn).placement) tn = chain_form_plain(ch).code;
+    if (ch && tn && !chain_form_valid(ch, tn)) return saber_hip_conv2d_chain_set_tile(ch, tn);      // (its status and message)
     int rc = choice ? saber_hip_conv2d_set_tile(c, choice) : SABER_HIP_OK;
     if (rc) return rc;
-    NetOp& o = net->ops[index];
     o.name = std::string(o.kind == OP_FC || o.kind == OP_FC_Q ? "fc:" : "conv:") + c->algo_name;
     if ((o.kind == OP_FC || o.kind == OP_FC_Q) && o.out2 >= 0) o.name += fc_softmax_ok(o.fc, o.kind == OP_FC_Q) ? "+softmax" : " | softmax_f32";
-    // chain decisions: a 3x3 head (bit 29) is restored before its chain head (bit 28, the next op): set_choices runs in op order
-    if (o.chain3 && (chain_bits & 32) && index + 1 < (int)net->ops.size()) {
-        const int tn = chain_bits & 15;
-        if (tn && (rc = saber_hip_conv2d_chain_set_tile(o.chain3, tn)) != SABER_HIP_OK) return rc;
-        net_set_chain_mode(net, index + 1, tn ? 2 : net_chain_mode(net, index + 1) == 2 ? 1 : net_chain_mode(net, index + 1));
-    } else if (o.chain && (chain_bits & 16) && index + 1 < (int)net->ops.size()) {
-        const int tn = chain_bits & 15;
-        if (tn && (rc = saber_hip_conv2d_chain_set_tile(o.chain, tn)) != SABER_HIP_OK) return rc;
-        net_set_chain_mode(net, index, net_chain_mode(net, index) == 2 ? 2 : (tn ? 1 : 0));   // (also restores the names)
-    }
+    if (ch && tn) (void)saber_hip_conv2d_chain_set_tile(ch, tn);
+    if (ch && ch == o.chain3) net_set_chain_mode(net, index + 1, tn ? 2 : net_chain_mode(net, index + 1) == 2 ? 1 : net_chain_mode(net, index + 1));
+    else if (ch) net_set_chain_mode(net, index, net_chain_mode(net, index) == 2 ? 2 : (tn ? 1 : 0));   // (also restores the names)
     if (o.stage) net_set_stage(net, index, stage_on);      // (a stage head comes before its blocks: set_choices runs in op order)
     if (o.skip) o.name = (o.chain3 && o.use_chain3) ? "conv:(in the stage launch)" : "conv:(in the chain launch)";
     if (o.skip && o.kind == OP_CONV_PAIR) o.name = (index > 0 && net->ops[index - 1].stem_pair) ? "conv:(in the stem launch)" : "conv:(in the chain launch)";
@@ -189,6 +186,11 @@ int saber_hip_net_autotune(saber_hip_net_t* net, saber_hip_stream_t stream, int 
         if ((o.kind == OP_FC || o.kind == OP_FC_Q) && o.out2 >= 0) o.name += fc_softmax_ok(o.fc, o.kind == OP_FC_Q) ? "+softmax" : " | softmax_f32";
         if (o.stem_pair) o.name = stem_pair_name(o);
     }
+    const char* log_env = std::getenv("SABER_HIP_AUTOTUNE_LOG");
+    const bool log_cands = g_cold && log_env && log_env[0] == '1';      // every timed chain / stage candidate, in the per-op tuner's format
+    auto log_cand = [&](const saber_hip_conv* c, const std::string& name, float t) {
+        if (log_cands) std::fprintf(stderr, "autotune [%dx%dx%d c%d k%d %dx%d] %-40s %8.2f us\n", c->d.n, c->d.h, c->d.w, c->d.c, c->d.k, c->d.kh, c->d.kw, name.c_str(), t);
+    };
     // conv1x1 chains: the tuned separate launches against the chain launch (every pixel-tile size) and, where the block's
     // 3x3 conv can lead the chain, against that single launch too - on the real tensors
     for (size_t i = 0; i < net->ops.size(); ++i)
@@ -212,22 +214,17 @@ int saber_hip_net_autotune(saber_hip_net_t* net, saber_hip_stream_t stream, int 
         net_set_chain_mode(net, ia, 0);
         int rc = timed(&best);
         if (rc) return rc;
-        const int c1 = A.chain ? A.chain->c1 : H->chain3->c1;
-        const int tns[6] = {c1 == 64 ? 4 : (c1 == 128 ? 2 : 1), c1 == 64 ? 2 : (c1 == 128 ? 1 : 9), c1 == 256 ? 11 : (c1 == 128 ? 6 : 0),
-                            c1 == 128 ? 5 : (c1 == 256 ? 3 : 0),       // (C = 256, code 3: the 3x3-led forms with 8 waves; refused elsewhere)
-                            c1 == 256 ? 7 : 0,                         // (code 7: two cooperating workgroups per tile, 3x3-led with a second 1x1 conv)
-                            c1 == 256 ? 15 : 0};                       // (code 15: four per tile of two rows)
+        log_cand(A.conv, "separate", best);
         for (int mode = A.chain ? 1 : 2; mode <= (H ? 2 : 1); ++mode) {
             saber_hip_chain* ch = mode == 2 ? H->chain3 : A.chain;
-            for (int tn : tns) {
-                if (!tn) continue;
-                if (net->shared_device && (tn == 7 || tn == 15)) continue;      // cooperating workgroups: not on a shared device
-                float ms = 0.f;
-                if (saber_hip_conv2d_chain_set_tile(ch, tn) != SABER_HIP_OK) continue;
+            for_each_chain_candidate(ch, net->shared_device, [&](const ChainForm& f) {
+                float ms = -1.f;
+                if (saber_hip_conv2d_chain_set_tile(ch, f.code) != SABER_HIP_OK) return;
                 net_set_chain_mode(net, ia, mode);
-                if (timed(&ms) != SABER_HIP_OK) continue;
-                if (ms < best) { best = ms; best_mode = mode; best_tn = tn; }
-            }
+                const int rt = timed(&ms);
+                log_cand(A.conv, (mode == 2 ? H->name : A.name).substr(5), ms);
+                if (rt == SABER_HIP_OK && ms < best) { best = ms; best_mode = mode; best_tn = f.code; }
+            });
         }
         if (best_mode) (void)saber_hip_conv2d_chain_set_tile(best_mode == 2 ? H->chain3 : A.chain, best_tn);
         net_set_chain_mode(net, ia, best_mode);
@@ -249,13 +246,15 @@ int saber_hip_net_autotune(saber_hip_net_t* net, saber_hip_stream_t stream, int 
         std::vector<int> modes(H0.stage_n), tns(H0.stage_n);
         for (int k = 0; k < H0.stage_n; ++k) {
             modes[k] = net_chain_mode(net, first + 3 * k + 1);
-            tns[k] = net->ops[first + 3 * k].chain3->tn;
+            tns[k] = net->ops[first + 3 * k].chain3->form.code;
         }
         float sep = 0.f, one = 0.f;
         int rc = timed(&sep);
         if (rc) return rc;
+        log_cand(H0.conv, "separate", sep);
         net_set_stage(net, first, true);
         const bool ok = timed(&one) == SABER_HIP_OK && hipStreamSynchronize(s) == hipSuccess && !*(volatile unsigned*)H0.stage->h_err;
+        log_cand(H0.conv, H0.name.substr(5), ok ? one : -1.f);
         if (!ok || one >= sep) {
             *(volatile unsigned*)H0.stage->h_err = 0u;
             net_set_stage(net, first, false);

@@ -20,10 +20,7 @@ static void net_name_chain(NetOp& A, NetOp& B) {
     if (A.skip) {
         A.name = B.name = "conv:(in the chain launch)";
     } else if (A.use_chain) {
-        const int t = A.chain->tn, c = A.chain->c1;
-        const bool w8 = t == 11 || (c == 128 && (t & 4));
-        A.name = "conv:chain1x1_c" + std::to_string(c) + "_px" + std::to_string(t == 11 ? 16 : 16 * (c == 128 ? t & 3 : t & 7)) +
-                 ((t & 8) ? "_split2" : "") + (w8 ? "_w8" : "");
+        A.name = "conv:" + chain_form_name(A.chain);
         B.name = "conv:(in the chain launch)";
     } else {
         A.name = std::string("conv:") + A.conv->algo_name;
@@ -51,11 +48,7 @@ void net_set_chain_mode(saber_hip_net* net, int ia, int mode) {
     }
     if (H) {
         H->use_chain3 = mode == 2;
-        H->name = mode == 2 ? std::string("conv:conv3x3+") + (H->chain3->b2 ? "conv1x1+pair1x1_c" : (H->chain3->b ? "chain1x1_c" : "conv1x1_c")) + std::to_string(H->chain3->c1) +
-                                  "_" + std::to_string(H->chain3->c1 == 128 ? H->chain3->tn & 3 : (H->chain3->c1 == 256 ? (H->chain3->tn == 15 ? 2 : 1) : H->chain3->tn)) + "x16" +
-                                  ((H->chain3->c1 == 128 && (H->chain3->tn & 4)) || (H->chain3->c1 == 256 && H->chain3->tn == 3) ? "_w8" : "") +
-                                  (H->chain3->c1 == 256 && H->chain3->tn == 7 ? "_coop2" : "") + (H->chain3->c1 == 256 && H->chain3->tn == 15 ? "_coop4" : "")
-                            : std::string("conv:") + H->conv->algo_name;
+        H->name = "conv:" + (mode == 2 ? chain_form_name(H->chain3) : std::string(H->conv->algo_name));
     }
     if (B) net_name_chain(A, *B);
     else A.name = A.skip ? "conv:(in the chain launch)" : std::string("conv:") + A.conv->algo_name;
@@ -485,7 +478,7 @@ int saber_hip_net_optimize(saber_hip_net_t* net, int flags) {
                 if (c->sel.fam == FAM_B3 && c->sel.ksplit) (void)sel_set(c, sel_b3(c->sel, c->sel.tile, c->sel.ks, 0));
             }
             for (saber_hip_chain* ch : {o.chain, o.chain3})
-                if (ch && (ch->tn == 7 || ch->tn == 15)) (void)saber_hip_conv2d_chain_set_tile(ch, 3);
+                if (ch && ch->form.placement) ch->form = chain_form_plain(ch);
         }
     }
     // the shared workspace only has to cover the surviving ops

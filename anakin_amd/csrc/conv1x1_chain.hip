@@ -363,93 +363,59 @@ bool conv1x1_chain_ok(int c1, int k1, int k2) {
     return (c1 == 64 || c1 == 128 || c1 == 256 || c1 == 512) && k1 == 4 * c1 && k2 == c1;
 }
 
-int conv1x1_chain_tn(int c1, int m) {
-    (void)m;
-    switch (c1) {
-    case 64: return 4;
-    case 128: return 2;
-    case 256: case 512: return 1;
-    default: return 0;
-    }
-}
-
-// with3x3: a.x is the 3x3 conv's input and the grid is tiles of tn rows x 16 columns (a.H, a.W, a.tiles_* set by api.hip)
-// tile: pixel fragments per workgroup (1x1 chain: 16-pixel runs; with3x3: rows of a 16-column tile) | 8 when the second
-// conv's output channels are split over two workgroups (wstream then holds [half][wave] streams, api.hip)
-hipError_t launch_conv1x1_chain(const ChainKArgs& a, int c1, int k1, int k2, int tile, int with3x3, hipStream_t s) {
+// with3x3: a.x is the 3x3 conv's input and the grid is tiles of `rows` rows x 16 columns (a.H, a.W, a.tiles_* set by api_chain.hip);
+// otherwise `rows` 16-pixel runs per workgroup. split == 2: wstream holds [half][wave] streams. Which (rows, waves, split) exist for which
+// chain is api_chain.hip's table (chain_forms); the switch below is the list of instantiations behind it.
+hipError_t launch_conv1x1_chain(const ChainKArgs& a, int c1, int k1, int k2, int rows, int waves, int split, int with3x3, hipStream_t s) {
     const bool has2 = k2 != 0;          // k2 == 0: conv3x3 + first 1x1 conv only (with3x3 required)
     const bool pair2 = has2 && a.k2_split > 0;      // the strided head followed by the next stage's sibling pair: 64 -> 256 (+ sum) -> 512 | 128
     if (pair2 && !(a.s0 == 2 && with3x3 && c1 == 64 && k1 == 256 && k2 == 640 && a.k2_split % 32 == 0 && a.k2_split < 640)) return hipErrorInvalidValue;
     if (!conv1x1_chain_ok(c1, k1, (has2 && !pair2) ? k2 : c1) || a.M <= 0 || (!has2 && !with3x3)) return hipErrorInvalidValue;
-    // C >= 256 codes: 1 = one fragment, 9 = second conv split over two workgroups, 11 = split + 8 waves per workgroup
-    // C = 128 codes: 2 | 1 fragments, + 4 = 8 waves per workgroup
-    const bool w8 = (c1 >= 256 && (tile & 7) == 3) || (c1 == 128 && (tile & 4));
-    const int tn = c1 == 128 ? tile & 3 : (w8 ? 1 : tile & 7), sp = (tile & 8) ? 2 : 1;
-    const dim3 block(w8 ? 512 : 256);
-    const dim3 grid((with3x3 ? a.tiles_per_img * a.N : (a.M + 16 * tn - 1) / (16 * tn)) * sp);
-#define SABER_CHAIN(KS1, G1, MFG2, G2, TN, R, C3, SP, ...) \
-    hipLaunchKernelGGL((conv1x1_chain_kernel<KS1, G1, MFG2, G2, TN, R, C3, SP, ##__VA_ARGS__>), grid, block, 0, s, a)
+    const dim3 block(64 * waves);
+    const dim3 grid((with3x3 ? a.tiles_per_img * a.N : (a.M + 16 * rows - 1) / (16 * rows)) * split);
+    // the kind of chain: 1x1 chain | 3x3-led with a second conv | 3x3 head alone | strided 3x3 head alone | strided head + sibling pair
+    enum { PLAIN, LED, HEAD, SHEAD, PAIR };
+    const int kind = pair2 ? PAIR : (!has2 ? (a.s0 == 2 ? SHEAD : HEAD) : (with3x3 ? LED : PLAIN));
+#define SABER_CHAIN(KIND, C1, ROWS, NW, SP, KS1, G1, MFG2, G2, R)                                                                   \
+    case (((KIND * 1024 + C1) * 8 + ROWS) * 16 + NW) * 4 + SP:                                                                      \
+        hipLaunchKernelGGL((conv1x1_chain_kernel<KS1, G1, MFG2, G2, ROWS, R, KIND != PLAIN, SP, KIND == PLAIN || KIND == LED || KIND == PAIR, NW, \
+                                                 KIND == SHEAD || KIND == PAIR ? 2 : 1>), grid, block, 0, s, a);                   \
+        break;
+    // the forms every kind but the pair has (C = 64, 128, 256 with 4 waves; C = 128 with 8), written once
+#define SABER_CHAIN_W4(KIND)                          \
+    SABER_CHAIN(KIND, 64, 4, 4, 1, 1, 1, 1, 1, 4)     \
+    SABER_CHAIN(KIND, 64, 2, 4, 1, 1, 1, 1, 1, 4)     \
+    SABER_CHAIN(KIND, 128, 2, 4, 1, 2, 2, 2, 1, 8)    \
+    SABER_CHAIN(KIND, 128, 1, 4, 1, 2, 2, 2, 1, 8)    \
+    SABER_CHAIN(KIND, 256, 1, 4, 1, 4, 4, 4, 1, 16)
+#define SABER_CHAIN_C128_W8(KIND)                     \
+    SABER_CHAIN(KIND, 128, 2, 8, 1, 2, 1, 1, 1, 8)    \
+    SABER_CHAIN(KIND, 128, 1, 8, 1, 2, 1, 1, 1, 8)
     // ring depths: measured with scripts/probe/timeline_probe.hip (chain): deeper rings (32 / 64 steps, or the whole
     // stream in registers) only move the wait into the prologue - the stream is bound by the CU's vector-memory path
     // (~43 B/clk measured for these 1 KB-per-instruction loads), not by the latency of one round trip
-    if (pair2) {
-        switch (tile) {
-        case 4: SABER_CHAIN(1, 1, 2, 5, 4, 4, true, 1, true, 4, 2); break;
-        case 2: SABER_CHAIN(1, 1, 2, 5, 2, 4, true, 1, true, 4, 2); break;
-        default: return hipErrorInvalidValue;
-        }
-        return hipGetLastError();
-    }
-    if (!has2 && a.s0 == 2) {      // strided head (the last block of a stage after the reference's stride-up)
-        switch (c1 * 32 + tile) {
-        case 64 * 32 + 4: SABER_CHAIN(1, 1, 1, 1, 4, 4, true, 1, false, 4, 2); break;
-        case 64 * 32 + 2: SABER_CHAIN(1, 1, 1, 1, 2, 4, true, 1, false, 4, 2); break;
-        case 128 * 32 + 2: SABER_CHAIN(2, 2, 2, 1, 2, 8, true, 1, false, 4, 2); break;
-        case 128 * 32 + 1: SABER_CHAIN(2, 2, 2, 1, 1, 8, true, 1, false, 4, 2); break;
-        case 256 * 32 + 1: SABER_CHAIN(4, 4, 4, 1, 1, 16, true, 1, false, 4, 2); break;
-        case 256 * 32 + 3: SABER_CHAIN(4, 2, 2, 1, 1, 16, true, 1, false, 8, 2); break;     // 8 waves
-        case 128 * 32 + 6: SABER_CHAIN(2, 1, 1, 1, 2, 8, true, 1, false, 8, 2); break;
-        case 128 * 32 + 5: SABER_CHAIN(2, 1, 1, 1, 1, 8, true, 1, false, 8, 2); break;
-        default: return hipErrorInvalidValue;
-        }
-        return hipGetLastError();
-    }
-    if (!has2) {
-        switch (c1 * 32 + tile) {
-        case 64 * 32 + 4: SABER_CHAIN(1, 1, 1, 1, 4, 4, true, 1, false); break;
-        case 64 * 32 + 2: SABER_CHAIN(1, 1, 1, 1, 2, 4, true, 1, false); break;
-        case 128 * 32 + 2: SABER_CHAIN(2, 2, 2, 1, 2, 8, true, 1, false); break;
-        case 128 * 32 + 1: SABER_CHAIN(2, 2, 2, 1, 1, 8, true, 1, false); break;
-        case 256 * 32 + 1: SABER_CHAIN(4, 4, 4, 1, 1, 16, true, 1, false); break;
-        case 256 * 32 + 3: SABER_CHAIN(4, 2, 2, 1, 1, 16, true, 1, false, 8); break;        // 8 waves
-        case 128 * 32 + 6: SABER_CHAIN(2, 1, 1, 1, 2, 8, true, 1, false, 8); break;
-        case 128 * 32 + 5: SABER_CHAIN(2, 1, 1, 1, 1, 8, true, 1, false, 8); break;
-        default: return hipErrorInvalidValue;
-        }
-        return hipGetLastError();
-    }
-    switch (c1 * 32 + tile * 2 + (with3x3 ? 1 : 0)) {
-    case 64 * 32 + 4 * 2: SABER_CHAIN(1, 1, 1, 1, 4, 4, false, 1); break;
-    case 64 * 32 + 2 * 2: SABER_CHAIN(1, 1, 1, 1, 2, 4, false, 1); break;
-    case 128 * 32 + 2 * 2: SABER_CHAIN(2, 2, 2, 1, 2, 8, false, 1); break;
-    case 128 * 32 + 1 * 2: SABER_CHAIN(2, 2, 2, 1, 1, 8, false, 1); break;
-    case 256 * 32 + 1 * 2: SABER_CHAIN(4, 4, 4, 1, 1, 16, false, 1); break;
-    case 256 * 32 + 9 * 2: SABER_CHAIN(4, 4, 2, 1, 1, 16, false, 2); break;     // second conv split over two workgroups
-    case 256 * 32 + 11 * 2: SABER_CHAIN(4, 2, 1, 1, 1, 16, false, 2, true, 8); break;   // ... and 8 waves
-    case 512 * 32 + 1 * 2: SABER_CHAIN(8, 8, 4, 2, 1, 16, false, 1); break;
-    case 512 * 32 + 9 * 2: SABER_CHAIN(8, 8, 4, 1, 1, 16, false, 2); break;
-    case 64 * 32 + 4 * 2 + 1: SABER_CHAIN(1, 1, 1, 1, 4, 4, true, 1); break;
-    case 64 * 32 + 2 * 2 + 1: SABER_CHAIN(1, 1, 1, 1, 2, 4, true, 1); break;
-    case 128 * 32 + 2 * 2 + 1: SABER_CHAIN(2, 2, 2, 1, 2, 8, true, 1); break;
-    case 128 * 32 + 1 * 2 + 1: SABER_CHAIN(2, 2, 2, 1, 1, 8, true, 1); break;
-    case 256 * 32 + 1 * 2 + 1: SABER_CHAIN(4, 4, 4, 1, 1, 16, true, 1); break;
-    case 256 * 32 + 3 * 2 + 1: SABER_CHAIN(4, 2, 2, 1, 1, 16, true, 1, true, 8); break;   // 3x3-led, 8 waves: 32 / 128 / 32 channels per wave
-    case 128 * 32 + 6 * 2: SABER_CHAIN(2, 1, 1, 1, 2, 8, false, 1, true, 8); break;      // 8 waves
-    case 128 * 32 + 5 * 2: SABER_CHAIN(2, 1, 1, 1, 1, 8, false, 1, true, 8); break;
-    case 128 * 32 + 6 * 2 + 1: SABER_CHAIN(2, 1, 1, 1, 2, 8, true, 1, true, 8); break;
-    case 128 * 32 + 5 * 2 + 1: SABER_CHAIN(2, 1, 1, 1, 1, 8, true, 1, true, 8); break;
+    switch ((((kind * 1024 + c1) * 8 + rows) * 16 + waves) * 4 + split) {
+    SABER_CHAIN(PAIR, 64, 4, 4, 1, 1, 1, 2, 5, 4)
+    SABER_CHAIN(PAIR, 64, 2, 4, 1, 1, 1, 2, 5, 4)
+    SABER_CHAIN_W4(SHEAD)
+    SABER_CHAIN(SHEAD, 256, 1, 8, 1, 4, 2, 2, 1, 16)      // 3x3-led, 8 waves: 32 / 128 / 32 channels per wave
+    SABER_CHAIN_C128_W8(SHEAD)
+    SABER_CHAIN_W4(HEAD)
+    SABER_CHAIN(HEAD, 256, 1, 8, 1, 4, 2, 2, 1, 16)
+    SABER_CHAIN_C128_W8(HEAD)
+    SABER_CHAIN_W4(PLAIN)
+    SABER_CHAIN(PLAIN, 256, 1, 4, 2, 4, 4, 2, 1, 16)      // second conv split over two workgroups
+    SABER_CHAIN(PLAIN, 256, 1, 8, 2, 4, 2, 1, 1, 16)      // ... and 8 waves
+    SABER_CHAIN(PLAIN, 512, 1, 4, 1, 8, 8, 4, 2, 16)
+    SABER_CHAIN(PLAIN, 512, 1, 4, 2, 8, 8, 4, 1, 16)
+    SABER_CHAIN_W4(LED)
+    SABER_CHAIN(LED, 256, 1, 8, 1, 4, 2, 2, 1, 16)
+    SABER_CHAIN_C128_W8(PLAIN)
+    SABER_CHAIN_C128_W8(LED)
     default: return hipErrorInvalidValue;
     }
+#undef SABER_CHAIN_C128_W8
+#undef SABER_CHAIN_W4
 #undef SABER_CHAIN
     return hipGetLastError();
 }

@@ -166,10 +166,9 @@ struct CoopKArgs {
     int n_tiles;
 };
 bool conv1x1_chain_ok(int c1, int k1, int k2);
-// number of 16-pixel fragments per workgroup the launcher uses for (c1, m) / 0 if unsupported
-int conv1x1_chain_tn(int c1, int m);
-// bytes of the packed weight stream / its per-wave step geometry
-hipError_t launch_conv1x1_chain(const ChainKArgs& a, int c1, int k1, int k2, int tn, int with3x3, hipStream_t s);
+// rows: 16-pixel fragments per workgroup (with3x3: rows of its 16-column tile), waves per workgroup (4 | 8), split: workgroups the second
+// conv's output channels are split over (1 | 2) - the decoded fields of a ChainForm (api_internal.h); k2 == 0: no second conv
+hipError_t launch_conv1x1_chain(const ChainKArgs& a, int c1, int k1, int k2, int rows, int waves, int split, int with3x3, hipStream_t s);
 // conv3x3 + conv1x1 (+ eltwise) + conv1x1 at C1 = 256 with the weight stream split over two cooperating workgroups per pixel tile
 hipError_t launch_conv_chain_coop(const CoopKArgs& a, hipStream_t s);
 

@@ -152,7 +152,7 @@ int main(int argc, char** argv) {
             const int tiles = n * hw;
             char nm[96];
             snprintf(nm, sizeof nm, "conv3x3+chain C=256 14x14 b%d 1x16 w8", n);
-            run(P, nm, tiles, 6, [&] { launch_conv1x1_chain(a, c, K1, c, 3, 1, P.st); });
+            run(P, nm, tiles, 6, [&] { launch_conv1x1_chain(a, c, K1, c, 1, 8, 1, 1, P.st); });
             CoopKArgs ck;
             ck.c = a;
             ck.coop_ctr = (unsigned long long*)dalloc((size_t)tiles * 32 * 8, 0);
@@ -249,9 +249,9 @@ int main(int argc, char** argv) {
     if (argc > 1 && !strcmp(argv[1], "chain")) {
         // conv1x1 chain: phases 0 entry, 1 loads / DMA issued, 2 first group's MFMAs done + DMA barrier, 3 first conv done,
         // 4 tile stored / second conv's operand in registers, 5 done
-        struct { const char* name; int c, hw, n, tn, w3; } cs[] = {
+        struct { const char* name; int c, hw, n, rows, w3, split; } cs[] = {      // (split 0: one workgroup per pixel tile)
             {"conv3x3+chain C=64 56x56 b8 2x16", 64, 56, 8, 2, 1}, {"conv3x3+chain C=128 28x28 b8 1x16", 128, 28, 8, 1, 1},
-            {"conv3x3+conv1x1 C=64 56x56 b8 2x16", 64, 56, 8, 2, 2}, {"chain C=256 14x14 b8 px16 split2", 256, 14, 8, 9, 0},
+            {"conv3x3+conv1x1 C=64 56x56 b8 2x16", 64, 56, 8, 2, 2}, {"chain C=256 14x14 b8 px16 split2", 256, 14, 8, 1, 0, 2},
             {"conv3x3+chain C=64 56x56 b1 2x16", 64, 56, 1, 2, 1},
             {"chain C=64 56x56 b8 px64", 64, 56, 8, 4}, {"chain C=64 56x56 b8 px32", 64, 56, 8, 2},
             {"chain C=128 28x28 b8 px32", 128, 28, 8, 2}, {"chain C=128 28x28 b8 px16", 128, 28, 8, 1},
@@ -268,8 +268,8 @@ int main(int argc, char** argv) {
             a.prm1 = dalloc((size_t)K1 * 12, 0); a.prm2 = dalloc((size_t)g.c * 12 + 1024, 0);
             a.y1 = dalloc((size_t)M * K1, 0); a.y2 = dalloc((size_t)M * g.c, 0);
             a.wstream = dalloc((size_t)4 * K1 * g.c + (size_t)9 * g.c * g.c + 65536, -1);
-            const int tn = g.tn & 7;
-            int blocks = ((M + 16 * tn - 1) / (16 * tn)) * ((g.tn & 8) ? 2 : 1);
+            const int tn = g.rows, split = g.split ? g.split : 1;
+            int blocks = ((M + 16 * tn - 1) / (16 * tn)) * split;
             if (g.w3) {
                 auto magic = [](int d) { return d >= 2 ? (unsigned)((0x100000000ull + (unsigned)d - 1) / (unsigned)d) : 0u; };
                 a.prm0 = dalloc((size_t)g.c * 12 + 1024, 0); a.zero = zero; a.N = g.n; a.H = a.W = g.hw;
@@ -277,7 +277,7 @@ int main(int argc, char** argv) {
                 a.mg_tiles_x = magic(a.tiles_x); a.mg_tpi = magic(a.tiles_per_img); a.in0_u8 = 1; a.relu0 = 1;
                 blocks = a.tiles_per_img * g.n;
             }
-            run(P, g.name, blocks, 6, [&] { launch_conv1x1_chain(a, g.c, K1, g.w3 == 2 ? 0 : g.c, g.tn, g.w3 ? 1 : 0, P.st); });
+            run(P, g.name, blocks, 6, [&] { launch_conv1x1_chain(a, g.c, K1, g.w3 == 2 ? 0 : g.c, tn, 4, split, g.w3 ? 1 : 0, P.st); });
         }
         return 0;
     }

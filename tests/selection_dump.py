@@ -8,6 +8,7 @@ Run in a process of its own: once loaded, the mock shadows the HIP runtime for t
     python tests/selection_dump.py              the dump
     python tests/selection_dump.py --roundtrip  the operator table only, each accepted code followed by what set_tile(get_tile()) does on a
                                                 fresh operator of the same descriptor (tests/test_abi.py asserts on these lines)
+    python tests/selection_dump.py --chains     the conv-chain section only (the last section of the dump; tests/test_abi.py asserts on it)
 """
 import ctypes as C
 import os
@@ -52,7 +53,7 @@ TABLE = [
 _keep = []      # host buffers the library may still point at
 
 
-def make(n, hw, c, k, kk, stride, group, int8, in_dt, in_layout, out_dt, act=0, pad=None):
+def make(n, hw, c, k, kk, stride, group, int8, in_dt, in_layout, out_dt, act=0, pad=None, **more):
     d = L.ConvDesc()
     d.n, d.h, d.w, d.c, d.k, d.kh, d.kw = n, hw, hw, c, k, kk, kk
     d.pad_h = d.pad_w = kk // 2 if pad is None else pad
@@ -61,6 +62,8 @@ def make(n, hw, c, k, kk, stride, group, int8, in_dt, in_layout, out_dt, act=0, 
     d.group = group
     d.in_dtype, d.out_dtype, d.in_layout, d.out_layout, d.int8_weights, d.act = in_dt, out_dt, in_layout, L.NHWC, int8, act
     d.sum_scale = d.coeff_conv = d.coeff_res = d.scale_res = 1.0
+    for key, v in more.items():
+        setattr(d, key, v)
     h = C.c_void_p()
     assert lib.saber_hip_conv2d_create(C.byref(d), C.byref(h)) == 0, lib.saber_hip_last_error()
     w = (np.random.default_rng(0).standard_normal((k, c // group, kk, kk)) * 0.1).astype(np.float32)
@@ -117,6 +120,62 @@ def out_bytes(row):
     return n * (hw // stride + 1) ** 2 * k * 4
 
 
+def chain_section():
+    """Chains formed by saber_hip_net_optimize: per chain head every code 0..15 through saber_hip_net_set_choice (status, get_choice, the names of the
+    ops of the block; codes are applied in order to ONE net, a last line switches the head's chain off again), then the candidates
+    saber_hip_net_autotune times. On the mock the placement probe fails, so the cooperative forms (codes 7, 15) and the stages are refused."""
+    def block(tag, c, hw, stride=1, second=True, pair=False):
+        net = C.c_void_p()
+        assert lib.saber_hip_net_create(C.byref(net)) == 0
+        t = lambda nbytes: lib.saber_hip_net_add_tensor(net, nbytes)      # noqa: E731
+        m, k1 = hw * hw, 4 * c
+        elt = dict(res_mode=L.RES_ELTWISE, res_act=L.ACT_RELU)
+        if stride == 2:
+            elt.update(res_stride=2, res_h=2 * hw, res_w=2 * hw)
+        ops = [make(1, hw * stride, c, c, 3, stride, 1, 1, L.U8, L.NHWC, L.U8, act=L.ACT_RELU),
+               make(1, hw, c, k1, 1, 1, 1, 1, L.U8, L.NHWC, L.S8, **elt)]
+        x, res, y0, y1 = t(m * stride * stride * c), t(m * stride * stride * k1), t(m * c), t(m * k1)
+        assert lib.saber_hip_net_add_conv(net, ops[0], x, y0, -1) >= 0, lib.saber_hip_last_error()
+        assert lib.saber_hip_net_add_conv(net, ops[1], y0, y1, res) >= 0, lib.saber_hip_last_error()
+        if pair:      # the next stage's branch1 | branch2a: 256 -> 512 | 128
+            ops += [make(1, hw, k1, 512, 1, 1, 1, 1, L.S8, L.NHWC, L.S8), make(1, hw, k1, 128, 1, 1, 1, 1, L.S8, L.NHWC, L.U8, act=L.ACT_RELU)]
+            p = C.c_void_p()
+            assert lib.saber_hip_conv2d_create_pair(ops[2], ops[3], C.byref(p)) == 0, lib.saber_hip_last_error()
+            ops.append(p)
+            assert lib.saber_hip_net_add_conv_pair(net, p, y1, t(m * 512), t(m * 128)) >= 0, lib.saber_hip_last_error()
+        elif second:
+            ops.append(make(1, hw, k1, c, 1, 1, 1, 1, L.S8, L.NHWC, L.U8, act=L.ACT_RELU))
+            assert lib.saber_hip_net_add_conv(net, ops[2], y1, t(m * c), -1) >= 0, lib.saber_hip_last_error()
+        removed = lib.saber_hip_net_optimize(net, 16 | 32 | 256 | 1024)
+        assert lib.saber_hip_net_finalize(net) == 0, lib.saber_hip_last_error()
+        n = lib.saber_hip_net_num_ops(net)
+        names = lambda: " | ".join(lib.saber_hip_net_op_name(net, i).decode() for i in range(n))      # noqa: E731
+        print("chain %s optimize=%d ops=%d %s" % (tag, removed, n, names()))
+        for i in range(n):
+            bit = (lib.saber_hip_net_get_choice(net, i) >> 28) & 3      # 1: heads a 1x1 chain, 2: a 3x3 conv that leads one
+            if not bit:
+                continue
+            for code in list(range(16)) + [0]:
+                rc = lib.saber_hip_net_set_choice(net, i, (bit << 28) | (code << 24))
+                print("chaincode %s op%d %2d rc=%d 0x%08x %s" % (tag, i, code, rc, lib.saber_hip_net_get_choice(net, i), names()))
+        rc, cands = logged(lambda: lib.saber_hip_net_autotune(net, None, 3))
+        for cd in cands:
+            print("cand %s %s" % (tag, cd))
+        print("autotune %s rc=%d candidates=%d -> %s %s" % (tag, rc, len(cands), " ".join("0x%08x" % lib.saber_hip_net_get_choice(net, i) for i in range(n)), names()))
+        lib.saber_hip_net_destroy(net)
+        for h in ops:
+            lib.saber_hip_conv2d_destroy(h)
+
+    for c, hw in ((64, 9), (128, 6), (256, 5), (512, 3)):
+        block("block_c%d" % c, c, hw)
+    for c in (128, 256):
+        block("strided_head_c%d" % c, c, 4, stride=2, second=False)
+    block("strided_head_pair", 64, 4, stride=2, pair=True)
+
+
+if "--chains" in sys.argv:
+    chain_section()
+    sys.exit(0)
 roundtrip = "--roundtrip" in sys.argv
 for row in TABLE:
     name = row[0]
@@ -189,3 +248,5 @@ for tag, int8, dt in (("fc_i8_f32in", 1, L.F32), ("fc_i8_s8in", 1, L.S8), ("fc_f
     print("create %s %s" % (tag, lib.saber_hip_fc_algo(h).decode()))
     codes(tag, h, set_tile=lib.saber_hip_fc_set_tile, show=lambda h: lib.saber_hip_fc_algo(h).decode())
     lib.saber_hip_fc_destroy(h)
+
+chain_section()

@@ -143,3 +143,40 @@ def test_every_accepted_selection_code_names_one_kernel_and_round_trips(built):
         assert len(set(cands[op])) == len(cands[op]), (op, "a candidate is timed twice")
         assert set(cands[op]) <= names[op], (op, sorted(set(cands[op]) - names[op]))
     assert [len(cands[op]) for op in ops] == [51, 40, 47, 41, 56, 19, 61, 61, 62, 63, 41, 3, 3, 0]
+
+
+def test_chain_codes_read_back_and_a_refused_code_changes_nothing(built):
+    """tests/selection_dump.py --chains in a subprocess (mock HIP runtime, as above): one bottleneck block per C in {64, 128, 256, 512}, strided
+    heads, the strided head + sibling pair, chained by saber_hip_net_optimize. Every code 0..15 goes through saber_hip_net_set_choice at each
+    chain head. An accepted code reads back through saber_hip_net_get_choice (bits 24..27); a refused one leaves get_choice and every op name
+    as they were. The accepted sets are the chain-form table's (api_chain.hip) without the placement-dependent forms, whose probe cannot
+    succeed on the mock. And the chain candidates saber_hip_net_autotune times are exactly the forms the accepted codes name."""
+    import subprocess
+    import sys
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "tests", "selection_dump.py"), "--chains"], capture_output=True, text=True, cwd=ROOT, timeout=600)
+    assert r.returncode == 0, r.stdout[-1500:] + r.stderr[-3000:]
+    accepted, named, cands, prev = {}, {}, {}, None
+    for ln in r.stdout.splitlines():
+        p = ln.split(None, 6)
+        if p[0] == "chain":
+            prev = None
+        elif p[0] == "chaincode":
+            tag, op, code, rc, choice, names = p[1], p[2], int(p[3]), p[4], int(p[5], 16), p[6]
+            if rc == "rc=0":
+                assert (choice >> 24) & 15 == code, ln
+                if code:
+                    accepted.setdefault((tag, op), set()).add(code)
+                    named.setdefault(tag, set()).add(names.split(" | ")[int(op[2:])])
+            else:
+                assert prev is not None and (choice, names) == prev, "a refused code changed the net: %s" % ln
+            prev = (choice, names)
+        elif p[0] == "cand" and (p[2].startswith("chain1x1") or p[2].startswith("conv3x3+")):
+            cands.setdefault(p[1], []).append("conv:" + p[2])
+    assert accepted == {
+        ("block_c64", "op0"): {4, 2}, ("block_c64", "op1"): {4, 2},
+        ("block_c128", "op0"): {2, 1, 6, 5}, ("block_c128", "op1"): {2, 1, 6, 5},
+        ("block_c256", "op0"): {1, 3}, ("block_c256", "op1"): {1, 9, 11},
+        ("block_c512", "op1"): {1, 9},
+        ("strided_head_c128", "op0"): {2, 1, 6, 5}, ("strided_head_c256", "op0"): {1, 3}, ("strided_head_pair", "op0"): {4, 2}}, accepted
+    for tag in named:
+        assert len(set(cands[tag])) == len(cands[tag]) and set(cands[tag]) == named[tag], (tag, cands[tag], sorted(named[tag]))

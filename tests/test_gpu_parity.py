@@ -2274,6 +2274,81 @@ def test_strided_conv3x3_conv1x1_chain_with_subsampled_shortcut(case):
         S.SaberConvChain(plain, None, conv3x3=c0)
 
 
+def test_chain_set_tile_accepts_the_form_table_and_every_form_gives_the_default_bytes():
+    """Every code 0..15 through saber_hip_conv2d_chain_set_tile on every kind of chain, at the smallest shapes of the cases above. The accepted
+    set is the chain-form table's (api_chain.hip: chain_forms), written out here; the cooperative forms of the 3x3-led C = 256 chain (7, 15)
+    exist together or not at all (the placement probe decides). Every accepted code writes the bytes of the default code; a refused one
+    raises, leaves the selection alone and nothing is launched for it."""
+    rng = np.random.default_rng(5150)
+    s_x, s_in, s_mid, s_res, s_sum, s_out = 0.023, 0.02, 0.05, 0.043, 0.06, 0.031
+    cf = 1.0 / s_sum
+
+    def conv(shape, k, ksz, stride, idt, odt, si, so, relu, elt=False, res_hw=None):
+        c = shape[1]
+        w = (rng.standard_normal((k, c, ksz, ksz)) * np.sqrt(2.0 / (ksz * ksz * c))).astype(np.float32)
+        b = (rng.standard_normal(k) * 0.5).astype(np.float32)
+        p = S.ConvParam(w, b, 1, (ksz // 2, ksz // 2), (stride, stride), (1, 1), bool(relu))
+        if elt:
+            p.res_mode, p.res_relu, p.sum_scale, p.coeff, p.scale_res = L.RES_ELTWISE, True, 1.0, (cf, cf), s_res
+        if res_hw:
+            p.res_stride, p.res_hw = 2, res_hw
+        return S.SaberConv2D(int8=True).init(shape, p, idt, odt, si, so)
+
+    def check(what, chain, want_codes, x, res, outs):
+        default = chain.tile()
+        assert default in want_codes, (what, default)
+
+        def run():
+            zs = [o.new_output() for o in outs]
+            for z in zs:
+                z.fill_(77)
+            chain.dispatch(dev(x), dev(res), *zs)
+            return [host(z) for z in zs]
+        want = run()
+        accepted = set()
+        for code in range(16):
+            before = chain.tile()
+            try:
+                chain.set_tile(code)
+            except L.SaberHipError:
+                assert chain.tile() == before, (what, code)
+                continue
+            accepted.add(code)
+            assert chain.tile() == code, (what, code)
+            for g, w in zip(run(), want):
+                assert np.array_equal(g, w), (what, code, "differs from code %d" % default)
+        coop = accepted & {7, 15}
+        assert (accepted - coop) == want_codes and coop in (set(), {7, 15} if what == "conv3x3+chain C=256" else set()), (what, sorted(accepted))
+
+    forms = {64: {4, 2}, 128: {2, 1, 6, 5}}
+    for Cc, H, Wd in ((64, 7, 9), (128, 5, 17), (256, 3, 5), (512, 3, 3)):
+        K1 = 4 * Cc
+        x = rng.integers(0, 256, (1, H, Wd, Cc)).astype(np.uint8)
+        res = rng.integers(-128, 128, (1, H, Wd, K1)).astype(np.int8)
+        ca = conv((1, Cc, H, Wd), K1, 1, 1, O.U8, O.S8, s_in, s_mid, 0, elt=True)
+        cb = conv((1, K1, H, Wd), Cc, 1, 1, O.S8, O.U8, s_sum, s_out, 1)
+        check("chain C=%d" % Cc, S.SaberConvChain(ca, cb), forms.get(Cc, {1, 9, 11} if Cc == 256 else {1, 9}), x, res, [ca, cb])
+        if Cc == 512:
+            continue
+        c0 = conv((1, Cc, H, Wd), Cc, 3, 1, O.U8, O.U8, s_x, s_in, 1)
+        check("conv3x3+chain C=%d" % Cc, S.SaberConvChain(ca, cb, conv3x3=c0), forms.get(Cc, {1, 3}), x, res, [ca, cb])
+        check("conv3x3+conv1x1 C=%d" % Cc, S.SaberConvChain(ca, None, conv3x3=c0), forms.get(Cc, {1, 3}), x, res, [ca])
+    for what, Cc, H, Wd, want_codes in (("strided head C=256", 256, 9, 7, {1, 3}), ("strided head + pair", 64, 27, 41, {4, 2})):
+        K1 = 4 * Cc
+        Ho, Wo = (H + 2 - 3) // 2 + 1, (Wd + 2 - 3) // 2 + 1
+        Hs, Ws = 2 * Ho - (1 if H % 2 else 0), 2 * Wo - (1 if Wd % 2 else 0)
+        x = rng.integers(0, 256, (1, H, Wd, Cc)).astype(np.uint8)
+        res = rng.integers(-128, 128, (1, Hs, Ws, K1)).astype(np.int8)
+        c0 = conv((1, Cc, H, Wd), Cc, 3, 2, O.U8, O.U8, s_x, s_in, 1)
+        ca = conv((1, Cc, Ho, Wo), K1, 1, 1, O.U8, O.S8, s_in, s_mid, 0, elt=True, res_hw=(Hs, Ws))
+        if Cc == 256:
+            check(what, S.SaberConvChain(ca, None, conv3x3=c0), want_codes, x, res, [ca])
+        else:
+            pb = conv((1, K1, Ho, Wo), 512, 1, 1, O.S8, O.S8, s_sum, 0.045, 0)
+            pc = conv((1, K1, Ho, Wo), 128, 1, 1, O.S8, O.U8, s_sum, 0.033, 1)
+            check(what, S.SaberConvChain(ca, pb, conv3x3=c0, pair_b=pc), want_codes, x, res, [ca, pb, pc])
+
+
 def _random_conv_geometry(rng, int8):
     k = int(rng.choice([1, 1, 3, 3, 3, 5, 7]))
     stride = int(rng.choice([1, 1, 1, 2]))
