@@ -78,7 +78,7 @@ static int tune(saber_hip_conv* op, hipStream_t s, int iters, const std::functio
 // caller re-initialises it).
 int saber_hip_conv2d_autotune(saber_hip_conv_t* op, const void* x, void* y, const void* res, void* workspace,
                                          saber_hip_stream_t stream, int iters) {
-    if ((op->algo > ALGO_IGEMM_F32 && !dw_ok(op)) || op->pool_fused || op->gpool) return SABER_HIP_OK;   // (one fused conv+pooling kernel)
+    if ((op->algo > ALGO_IGEMM_F32 && !dw_ok(op) && !group_ok(op)) || op->pool_fused || op->gpool) return SABER_HIP_OK;   // (one fused conv+pooling kernel)
     if (op->pair_k2) return fail(SABER_HIP_INVALID_VALUE, "sibling pair: use saber_hip_conv2d_autotune_pair");
     if (op->sel.fam == FAM_FC_SMALL) return SABER_HIP_OK;   // small-batch fc: one launch at the latency floor, nothing to tune
     hipStream_t s = (hipStream_t)stream;

@@ -223,6 +223,10 @@ int saber_hip_conv2d_create(const saber_hip_conv_desc* desc, saber_hip_conv_t** 
     if (op->algo > ALGO_IGEMM_F32) sel = sel_direct(sel);      // (keeps the parameters: see sel_valid)
     if (stem_ok(op)) sel = sel_stem(sel);
     if (dw_ok(op)) sel = sel_dw(sel, dw_static_form(op));
+    if (group_ok(op)) {
+        const int form = group_static_form(op);
+        if (form) sel = sel_group(sel, form);
+    }
     const int rc = sel_set(op, sel);
     if (rc) {
         delete op;
@@ -296,6 +300,15 @@ int dw_static_form(const saber_hip_conv* op) {
     return lanes >= DW_STRIP_MIN_LANES ? 1 : 2;
 }
 
+// STATIC form of an eligible grouped 3x3 op, from the measured table (profiles/group3x3/README.md): the matrix-core form is 1.9 - 26x faster
+// than the direct kernel in windows of 20 warm launches (1.3 - 14x for single cold-L2 launches) on every one of the seven ResNeXt-50
+// shapes at batch 1 and at batch 8, so it is the choice for
+// every eligible op. 0 would be the direct kernel.
+int group_static_form(const saber_hip_conv* op) {
+    (void)op;
+    return 1;
+}
+
 int saber_hip_conv2d_set_weights(saber_hip_conv_t* op, const void* w, int w_dtype, const float* w_scale,
                                  const float* bias, float in_scale, float out_scale) {
     if (!op || !w) return fail(SABER_HIP_INVALID_VALUE, "null argument");
@@ -360,14 +373,6 @@ int saber_hip_conv2d_set_weights(saber_hip_conv_t* op, const void* w, int w_dtyp
                                                                    : ((size_t)(i * op->kw_pad + j) * 4 + c);
                             wr[(size_t)k * op->Kg_pad + kk] = (uint8_t)v;
                         }
-            if (in_dt == DT_U8) {  // +128 * sum(w): compensation of the u8 -> s8 shift
-                comp.assign(K_pad, 0);
-                for (int k = 0; k < K; ++k) {
-                    int s = 0;
-                    for (size_t i = 0; i < inner; ++i) s += (int)q[k * inner + i];
-                    comp[k] = 128 * s;
-                }
-            }
         } else {  // direct: [K][kh][kw][Cg]
             wr.assign((size_t)K * inner, 0);
             for (int k = 0; k < K; ++k)
@@ -382,6 +387,20 @@ int saber_hip_conv2d_set_weights(saber_hip_conv_t* op, const void* w, int w_dtyp
             for (int k = 0; k < K; ++k)
                 for (int t = 0; t < 9; ++t) wd[(size_t)t * K + k] = (uint8_t)q[(size_t)k * 9 + t];
             HIP_TRY(op->d_wdw.upload(wd));
+        }
+        if (group_ok(op)) {      // grouped 3x3: the MFMA fragment planes of conv_group3x3.hip and, for u8 input, its shift compensation (the direct
+                                 // kernel reads true u8 values and is launched without it)
+            std::vector<uint8_t> wg;
+            group3x3_pack(q, d.c, Cg, wg);
+            HIP_TRY(op->d_wg.upload(wg));
+        }
+        if (in_dt == DT_U8 && (op->algo != ALGO_DIRECT_I8 || group_ok(op))) {  // +128 * sum(w): compensation of the u8 -> s8 shift
+            comp.assign(K_pad, 0);
+            for (int k = 0; k < K; ++k) {
+                int s = 0;
+                for (size_t i = 0; i < inner; ++i) s += (int)q[k * inner + i];
+                comp[k] = 128 * s;
+            }
         }
         bias_p.resize(K_pad, 0.f);
         scale.resize(K_pad, 0.f);

@@ -101,7 +101,8 @@ enum ConvFamily {
     FAM_B3H,         // FP32: LDS-halo bf16-plane kernel (conv3x3_b3h.hip, planes d_w3h1 / d_w3h2), variant 1..5 = 3x3 forms, 6..8 = pointwise
     FAM_PW,          // FP32 1x1 / stride 1 (planes d_wpw): variant 0 = persistent register-weights kernel (C = 64 / 128, conv1x1_pw.hip),
                      // 1 .. 4 = the reduction-split kernel's variants (C = 128 .. 2048, conv1x1_pwk.hip)
-    FAM_DW           // depthwise 3x3 (dw_ok): variant 1 .. DW3X3_FORMS = that form of conv_dw3x3.hip (weights d_wdw)
+    FAM_DW,          // depthwise 3x3 (dw_ok): variant 1 .. DW3X3_FORMS = that form of conv_dw3x3.hip (weights d_wdw)
+    FAM_GROUP        // INT8 grouped 3x3 with Cg == Kg (group_ok): variant 1 .. G3X3_FORMS = that form of conv_group3x3.hip (weights d_wg, d_comp)
 };
 struct ConvSel {
     ConvFamily fam = FAM_DIRECT;
@@ -141,6 +142,7 @@ inline ConvSel sel_fc_small(const ConvSel& base) { return sel_family(base, FAM_F
 inline ConvSel sel_b3h(ConvSel base, int variant) { base.dma = 0; return sel_family(base, FAM_B3H, variant); }
 inline ConvSel sel_pw(ConvSel base, int variant) { base.dma = 0; return sel_family(base, FAM_PW, variant); }
 inline ConvSel sel_dw(const ConvSel& base, int form) { return sel_family(base, FAM_DW, form); }
+inline ConvSel sel_group(const ConvSel& base, int form) { return sel_family(base, FAM_GROUP, form); }
 
 }  // namespace saber_api
 using namespace saber_api;
@@ -159,6 +161,7 @@ struct saber_hip_conv {
     DevBuf<uint8_t> d_w3h1, d_w3h2;   // FAM_B3H: the weight planes in MFMA fragment order for 1 / 2 row tiles per wave
     DevBuf<uint8_t> d_wpw;   // FAM_PW: the weight planes in that kernel's fragment order
     DevBuf<uint8_t> d_wdw;   // FAM_DW: the weights as [tap][C] (s8 / f32), packed by set_weights
+    DevBuf<uint8_t> d_wg;    // FAM_GROUP: the weights in MFMA fragment order (group3x3_pack), packed by set_weights together with d_comp
     DevBuf<float> d_fcpart;  // FP32 fc at <= 16 rows and <= 2048 outputs: the split-K kernel's partial sums + arrival counters (fc_f32_splitk.hip;
     DevBuf<unsigned> d_fcctr; // allocated by set_weights when the shape is eligible AND SABER_HIP_FC_F32_SPLITK=1: opt-in, measured no faster - profiles/r06/fc_tail.txt)
     DevBuf<float> d_wfc;     // FP32 fc at <= 16 rows: the weights fragment-major for the streaming kernel (fc_small.hip: fc_f32_stream_kernel PACKED)
@@ -456,10 +459,12 @@ unsigned long long sel_kernel_key(const saber_hip_conv* op, const saber_api::Con
 int sel_launch(saber_hip_conv* op, saber_mi355x::ConvKArgs& a, hipStream_t s);
 void for_each_candidate(const saber_hip_conv* op, const saber_api::ConvSel* best, const std::function<void(const saber_api::ConvSel&)>& fn);
 bool dw_ok(const saber_hip_conv* op);
+bool group_ok(const saber_hip_conv* op);
 bool stem_ok(const saber_hip_conv* op);
 bool fc_small_ok(const saber_hip_conv* op);
 bool b3_tile_ok(const saber_hip_conv* op, int tile, int ks);
 int dw_static_form(const saber_hip_conv* op);      // api_conv.hip: create's choice among the depthwise forms
+int group_static_form(const saber_hip_conv* op);      // api_conv.hip: create's choice among the direct kernel (0) and the grouped 3x3 forms
 constexpr long DW_STRIP_MIN_LANES = 150000;     // (lanes = channel vectors x output pixels. Measured, profiles/dw3x3/README.md: at 200 704 lanes and above the strip form is the faster one for both element types, at 100 352 and below the one-pixel form)
 std::string stem_pair_name(const saber_api::NetOp& o);      // api_net_optimize.hip
 void conv_fill_args(const saber_hip_conv* op, saber_mi355x::ConvKArgs& a, const void* x, void* y, const void* res);   // api_conv.hip

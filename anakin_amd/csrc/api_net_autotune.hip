@@ -15,7 +15,7 @@ static saber_hip_conv* net_op_conv(saber_hip_net* net, int index) {
 // pixel fragments in bits 24..27 (0: run as two launches)
 int saber_hip_net_get_choice(saber_hip_net_t* net, int index) {
     saber_hip_conv* c = net_op_conv(net, index);
-    int choice = (c && !c->pool_fused && (c->algo <= ALGO_IGEMM_F32 || dw_ok(c))) ? saber_hip_conv2d_get_tile(c) : 0;
+    int choice = (c && !c->pool_fused && (c->algo <= ALGO_IGEMM_F32 || dw_ok(c) || group_ok(c))) ? saber_hip_conv2d_get_tile(c) : 0;
     if (c && net->ops[index].chain) choice |= (1 << 28) | ((net->ops[index].use_chain ? net->ops[index].chain->form.code : 0) << 24);
     if (c && net->ops[index].chain3) choice |= (1 << 29) | ((net->ops[index].use_chain3 ? net->ops[index].chain3->form.code : 0) << 24);
     if (c && net->ops[index].stage && net->ops[index].use_stage) choice |= 1 << 30;      // this op launches its whole stage
@@ -27,7 +27,7 @@ int saber_hip_net_stage_blocks(const saber_hip_net_t* net, int index) {
 }
 int saber_hip_net_set_choice(saber_hip_net_t* net, int index, int choice) {
     saber_hip_conv* c = net_op_conv(net, index);
-    if (!c || !choice || c->pool_fused || (c->algo > ALGO_IGEMM_F32 && !dw_ok(c))) return SABER_HIP_OK;
+    if (!c || !choice || c->pool_fused || (c->algo > ALGO_IGEMM_F32 && !dw_ok(c) && !group_ok(c))) return SABER_HIP_OK;
     if (net->reproducible_fp32 && !c->is_i8) return SABER_HIP_OK;      // flag 8192: a restored selection does not move FP32 ops either
     if (net->ops[index].kind == OP_CONV_PAIR && index > 0 && net->ops[index - 1].stem_pair) return SABER_HIP_OK;      // no kernel of its own (flag 512)
     const int chain_bits = (choice >> 24) & 63;

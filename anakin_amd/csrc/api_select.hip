@@ -15,6 +15,15 @@ bool dw_ok(const saber_hip_conv* op) {
     if (op->is_i8 && op->epi != EPI_I8_CONV) return false;
     return conv_dw3x3_ok(!op->is_i8, d.n, d.c, d.k, d.group, d.kh, d.kw, d.stride_h, d.stride_w, d.pad_h, d.pad_w, d.dil_h, d.dil_w, op->oh, op->ow);
 }
+// the grouped 3x3 INT8 kernels exist for this op (conv_group3x3.hip): group > 1, not depthwise, Cg == Kg in {4, 8, 16, 32, 64}, C % 64 == 0, 3x3,
+// dilation 1, stride 1 | 2, pad 0 | 1, 8-bit NHWC in, NHWC s8 / u8 / f32 out, no residual. A property of the descriptor: known at create
+bool group_ok(const saber_hip_conv* op) {
+    const saber_hip_conv_desc& d = op->d;
+    if (op->algo != ALGO_DIRECT_I8 || !op->is_i8 || op->epi != EPI_I8_CONV) return false;
+    if (d.res_mode != SABER_HIP_RES_NONE || op->pre_quant || op->pre_pad || d.in_layout != SABER_HIP_NHWC || d.out_layout != SABER_HIP_NHWC) return false;
+    if (d.in_dtype != SABER_HIP_S8 && d.in_dtype != SABER_HIP_U8) return false;
+    return conv_group3x3_ok(d.n, d.c, d.k, d.group, d.kh, d.kw, d.stride_h, d.stride_w, d.pad_h, d.pad_w, d.dil_h, d.dil_w, op->oh, op->ow);
+}
 // the pointwise kernels (planes packed on demand by pw_prepare): 0 = the persistent register-weights kernel, 1 .. 4 = the reduction-split one
 static bool pw_variant_ok(const saber_hip_conv* op, int variant) {
     if (!pw_eligible(op)) return false;
@@ -94,6 +103,7 @@ bool sel_valid(const saber_hip_conv* op, const ConvSel& s) {
     case FAM_B3H: return b3h_ok(op, s.variant);
     case FAM_PW: return pw_variant_ok(op, s.variant);
     case FAM_DW: return dw_ok(op) && s.variant >= 1 && s.variant <= DW3X3_FORMS;
+    case FAM_GROUP: return group_ok(op) && s.variant >= 1 && s.variant <= G3X3_FORMS;
     }
     return false;
 }
@@ -114,6 +124,8 @@ static const char* sel_requirements(ConvFamily fam) {
     case FAM_PW: return "pointwise kernels: FP32 NHWC 1x1 / stride-1 conv, K % 64 == 0, C in {64, 128} (variant 0) or C % 128 == 0 (1..4)";
     case FAM_DW: return "depthwise 3x3 kernels: group == c == k, 3x3, dilation 1, stride 1 | 2, pad 0 | 1, NHWC 8-bit (C % 16 == 0) or f32 (C % 4 == 0) "
                         "tensors, no residual; low byte 0 (direct kernel) .. 2";
+    case FAM_GROUP: return "grouped 3x3 kernels: INT8, group > 1 with Cg == Kg in {4, 8, 16, 32, 64}, C % 64 == 0, 3x3, dilation 1, stride 1 | 2, pad 0 | 1, "
+                           "NHWC 8-bit input, NHWC s8 / u8 / f32 output, no residual; low byte 0 (direct kernel) | 1";
     }
     return "";
 }
@@ -171,10 +183,12 @@ int sel_set(saber_hip_conv* op, const ConvSel& s) {
 //    14        pointwise kernels: 0 = register weights, 1 .. 4 = the reduction-split variants
 //    15        FP32 stem launch (a property of the fused conv + pooling op, not a selection: saber_hip_conv2d_set_tile)
 //    16        depthwise 3x3: 0 = the direct kernel, 1 .. DW3X3_FORMS = the forms of conv_dw3x3.hip
+//    17        INT8 grouped 3x3 (Cg == Kg): 0 = the direct kernel, 1 .. G3X3_FORMS = the forms of conv_group3x3.hip
 // ================================================================================================
 int sel_encode(const saber_hip_conv* op) {
     const ConvSel& s = op->sel;
     if (dw_ok(op)) return (16 << 16) | (s.fam == FAM_DW ? s.variant : 0);      // (an eligible op always answers in this encoding)
+    if (group_ok(op)) return (17 << 16) | (s.fam == FAM_GROUP ? s.variant : 0);      // (likewise)
     switch (s.fam) {
     case FAM_PW: return (14 << 16) | s.variant;
     case FAM_B3H: return (13 << 16) | s.variant;
@@ -185,6 +199,7 @@ int sel_encode(const saber_hip_conv* op) {
     case FAM_STEM: return 7 << 16;
     case FAM_HALO: return s.tile | (s.ks << 8) | ((s.variant == 4 ? 5 : 6) << 16);
     case FAM_DW:
+    case FAM_GROUP:
     case FAM_DIRECT:
     case FAM_IGEMM: break;
     }
@@ -223,6 +238,10 @@ int sel_decode(const saber_hip_conv* op, int code, ConvSel* out) {
     case 16:
         if (!dw_ok(op) || low > DW3X3_FORMS) return fail(SABER_HIP_INVALID_VALUE, sel_requirements(FAM_DW));
         *out = low ? sel_dw(cur, low) : sel_direct(cur);
+        return SABER_HIP_OK;
+    case 17:
+        if (!group_ok(op) || low > G3X3_FORMS) return fail(SABER_HIP_INVALID_VALUE, sel_requirements(FAM_GROUP));
+        *out = low ? sel_group(cur, low) : sel_direct(cur);
         return SABER_HIP_OK;
     default: return fail(SABER_HIP_INVALID_VALUE, "bad staging variant");
     }
@@ -274,6 +293,7 @@ void sel_name(saber_hip_conv* op) {
     case FAM_IMG: snprintf(buf, sizeof buf, "img3x3_i8_%dimg_x_%drows_k16_w%d", s.img_ib, s.img_rb, s.img_nw); break;
     case FAM_HALO: snprintf(buf, sizeof buf, "halo3x3_i8_%dx16", s.variant); break;
     case FAM_DW: snprintf(buf, sizeof buf, "dw3x3_%s_%s", op->is_i8 ? "i8" : "f32", conv_dw3x3_form_name(s.variant, !op->is_i8)); break;
+    case FAM_GROUP: snprintf(buf, sizeof buf, "g3x3_i8_%s", conv_group3x3_form_name(s.variant)); break;
     case FAM_DIRECT: snprintf(buf, sizeof buf, "%s", an[op->algo]); break;
     case FAM_B3:
     case FAM_IGEMM: {
@@ -302,6 +322,11 @@ unsigned long long sel_kernel_key(const saber_hip_conv* op, const ConvSel& s) {
     const u64 k = (u64)op->algo | ((u64)ek << 4), sum = (u64)(d.res_mode == SABER_HIP_RES_SUM_INPLACE) << 32;
     switch (s.fam) {
     case FAM_DW: return k | (11ull << 8) | ((u64)s.variant << 16) | ((u64)(d.stride_h == 2) << 24) | ((u64)(d.in_dtype == SABER_HIP_U8) << 25);
+    case FAM_GROUP: {      // <CGC, U8, PT>: channel class, input type, form (and the stride, a run-time argument, as the depthwise key has it)
+        const int cg = d.c / d.group;
+        return k | (12ull << 8) | ((u64)s.variant << 16) | ((u64)(d.stride_h == 2) << 24) | ((u64)(d.in_dtype == SABER_HIP_U8) << 25) |
+               ((u64)(cg <= 16 ? 0 : (cg == 32 ? 1 : 2)) << 26);
+    }
     case FAM_PW: return s.variant ? k | (10ull << 8) | ((u64)(s.variant + 1) << 16) | sum : k | (9ull << 8) | ((u64)op->c_eff << 16) | sum;
     case FAM_B3H: return k | (8ull << 8) | ((u64)s.variant << 16);
     case FAM_IMG1: return k | (7ull << 8) | ((u64)(d.kh == 3) << 16);      // one function for all image-resident shapes
@@ -371,6 +396,11 @@ int sel_launch(saber_hip_conv* op, ConvKArgs& a, hipStream_t s) {
         a.w = op->d_wdw.p;
         HIP_TRY(launch_conv_dw3x3(c.variant, !op->is_i8, a, s));
         break;
+    case FAM_GROUP:
+        if (!group_ok(op) || !op->d_wg.p || (a.in_u8 && !a.comp)) return fail(SABER_HIP_INVALID_VALUE, "grouped 3x3 kernel selected on an op without its fragment-ordered weights");
+        a.w = op->d_wg.p;
+        HIP_TRY(launch_conv_group3x3(c.variant, a, op->d.group, s));
+        break;
     case FAM_DIRECT:
         a.comp = nullptr;
         HIP_TRY(launch_conv_direct(op->is_i8 ? 0 : 1, a, op->d.group, s));
@@ -390,6 +420,11 @@ void for_each_candidate(const saber_hip_conv* op, const ConvSel* best, const std
     if (dw_ok(op)) {      // depthwise 3x3: the direct kernel and every form of conv_dw3x3.hip
         fn(sel_direct(entry));
         for (int f = 1; f <= DW3X3_FORMS; ++f) fn(sel_dw(entry, f));
+        return;
+    }
+    if (group_ok(op)) {      // INT8 grouped 3x3: the direct kernel and every form of conv_group3x3.hip
+        fn(sel_direct(entry));
+        for (int f = 1; f <= G3X3_FORMS; ++f) fn(sel_group(entry, f));
         return;
     }
     ConvSel last = entry;

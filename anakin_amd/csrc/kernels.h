@@ -315,6 +315,15 @@ const char* conv_dw3x3_form_name(int form, bool f32);
 bool conv_dw3x3_ok(bool f32, int n, int c, int k, int group, int kh, int kw, int stride_h, int stride_w, int pad_h, int pad_w, int dil_h,
                    int dil_w, int oh, int ow);
 hipError_t launch_conv_dw3x3(int form, bool f32, const ConvKArgs& a, hipStream_t s);
+// Grouped 3x3 INT8 on the i8 matrix cores (group > 1, Cg == Kg in {4, 8, 16, 32, 64}, C % 64 == 0, dilation 1, stride 1 | 2, pad 0 | 1, NHWC
+// in / out, no residual; conv_group3x3.hip): a wave owns 16 output pixels x 64 output channels (form 1, "w16").
+// a.w = the fragment-ordered planes of group3x3_pack, a.comp = 128 * sum(w[k]) for u8 input. Same bits as launch_conv_direct on these ops.
+constexpr int G3X3_FORMS = 1;
+const char* conv_group3x3_form_name(int form);
+int conv_group3x3_steps(int cg);      // 64-byte K-steps per 16-channel row block
+bool conv_group3x3_ok(int n, int c, int k, int group, int kh, int kw, int stride_h, int stride_w, int pad_h, int pad_w, int dil_h, int dil_w,
+                      int oh, int ow);
+hipError_t launch_conv_group3x3(int form, const ConvKArgs& a, int group, hipStream_t s);
 
 // reads `bytes` of device memory through every XCD (autotuning: the timed launch then finds none of its operands in
 // an L2, which is how it runs inside the op list)
@@ -356,6 +365,7 @@ hipError_t launch_gemm_f32(int ta, int tb, int m, int n, int k, float alpha, con
 // FP32 stem: NCHW f32 image -> conv 7x7 / 2 / pad 3 (3 -> 64) + bias + relu -> max pooling 3x3 / 2 -> NHWC f32, one launch (conv_stem_f32.hip)
 struct StemF32Args;
 void stem_f32_pack(const float* w_oihw, std::vector<uint8_t>& out);
+void group3x3_pack(const int8_t* q_oihw, int c, int cg, std::vector<uint8_t>& out);      // conv_group3x3.hip: [C / 64][4][steps][64 lanes][16]
 hipError_t launch_conv_stem_f32_pool_raw(const float* x, const void* w, const float* bias, float* y, int n, int h, int w_, int oh, int ow, int ph,
                                          int pw, int variant, hipStream_t s);
 }  // namespace saber_mi355x

@@ -22,14 +22,27 @@ F32, S8, U8 = 0, 1, 2
 # --------------------------------------------------------------------------------------------- topology
 def resnet_spec(depth=50):
     """Returns the layer list: dicts with kind in {conv, pool, eltwise, gpool, fc, softmax}."""
-    blocks = {50: [3, 4, 6, 3], 101: [3, 4, 23, 3]}[depth]
+    return _bottleneck_spec({50: [3, 4, 6, 3], 101: [3, 4, 23, 3]}[depth], 64, 4, 1, False)
+
+
+def resnext_spec():
+    """ResNeXt-50 32x4d: ResNet50's layer graph with a bottleneck of 128 << stage channels (cout = 2 x mid) whose 3x3 `branch2b` has 32
+    groups (4 / 8 / 16 / 32 channels each), and - as in the published model - the block's stride on `branch2b` and `branch1`
+    (`branch2a` always has stride 1)."""
+    return _bottleneck_spec([3, 4, 6, 3], 128, 2, 32, True)
+
+
+def _bottleneck_spec(blocks, width, expand, group, stride_3x3):
+    """conv1 + pool1, stages of bottleneck blocks (1x1 -> 3x3 -> 1x1 + shortcut) with mid = width << stage and cout = expand x mid,
+    pool5, fc1000, prob. group > 1: the 3x3 conv is grouped (its dict carries `group`). stride_3x3: the first block of stages 3-5
+    has its stride on the 3x3 conv instead of on `branch2a` (Caffe's ResNet)."""
     L = []
     L.append(dict(kind="conv", name="conv1", src="data", cin=3, cout=64, k=7, stride=2, pad=3, relu=True))
     L.append(dict(kind="pool", name="pool1", src="conv1", win=3, stride=2, pad=0, type=0))
     prev, cin, hw = "pool1", 64, 56
     for si, nb in enumerate(blocks):
-        mid = 64 << si
-        cout = mid * 4
+        mid = width << si
+        cout = mid * expand
         for bi in range(nb):
             stride = 2 if (bi == 0 and si > 0) else 1
             # Caffe naming: res4a, res4b, ... for short stages; res4a, res4b1 .. res4b22 for ResNet101's long stage
@@ -40,10 +53,12 @@ def resnet_spec(depth=50):
                 shortcut = tag + "_branch1"
             else:
                 shortcut = prev
-            L.append(dict(kind="conv", name=tag + "_branch2a", src=prev, cin=cin, cout=mid, k=1, stride=stride, pad=0,
+            L.append(dict(kind="conv", name=tag + "_branch2a", src=prev, cin=cin, cout=mid, k=1, stride=1 if stride_3x3 else stride, pad=0,
                           relu=True))
-            L.append(dict(kind="conv", name=tag + "_branch2b", src=tag + "_branch2a", cin=mid, cout=mid, k=3, stride=1,
+            L.append(dict(kind="conv", name=tag + "_branch2b", src=tag + "_branch2a", cin=mid, cout=mid, k=3, stride=stride if stride_3x3 else 1,
                           pad=1, relu=True))
+            if group > 1:
+                L[-1]["group"] = group
             L.append(dict(kind="conv", name=tag + "_branch2c", src=tag + "_branch2b", cin=mid, cout=cout, k=1,
                           stride=1, pad=0, relu=False, eltwise=tag))
             L.append(dict(kind="eltwise", name=tag, a=tag + "_branch2c", b=shortcut, relu=True))
@@ -209,7 +224,7 @@ def fold_bn(w, bias, bn_scale, eps, mean, var, scale_w, scale_b):
 def build_model(name="resnet50", seed=42):
     """Seeded weights: conv ~ N(0, sqrt(2/(C*k*k))), BN gamma U(.5,1.5), beta/mean U(-.1,.1), var U(.5,1.5)."""
     spec = {"resnet50": lambda: resnet_spec(50), "resnet101": lambda: resnet_spec(101), "vgg16": vgg16_spec,
-            "mobilenet_v1": mobilenet_v1_spec}[name]()
+            "mobilenet_v1": mobilenet_v1_spec, "resnext50_32x4d": resnext_spec}[name]()
     params, raw = {}, {}          # raw: the BatchNorm / Scale blobs before folding (what a model file holds)
     for idx, l in enumerate(spec):
         rng = np.random.default_rng(seed + idx)

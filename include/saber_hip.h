@@ -163,7 +163,12 @@ const char* saber_hip_conv2d_algo(const saber_hip_conv_t* op);
  *   16 depthwise 3x3 (group == c == k, dilation 1, stride 1 | 2, pad 0 | 1, no residual; 8-bit NHWC tensors with C % 16 == 0 or f32
  *      NHWC tensors with C % 4 == 0): low byte 0 = the direct one-output-per-thread kernel, 1 = a strip of output rows per lane (2 rows
  *      INT8, 4 rows FP32), 2 = one output pixel per lane. All three compute the same bits. get_tile of an eligible op always answers
- *      in this encoding; on any other op, or for a larger low byte, set_tile returns SABER_HIP_INVALID_VALUE. */
+ *      in this encoding; on any other op, or for a larger low byte, set_tile returns SABER_HIP_INVALID_VALUE;
+ *   17 INT8 grouped 3x3 (group > 1, not depthwise, c / group == k / group in {4, 8, 16, 32, 64}, c % 64 == 0, dilation 1, stride 1 | 2,
+ *      pad 0 | 1, no residual; 8-bit NHWC input, NHWC s8 / u8 / f32 output): low byte 0 = the direct one-output-per-thread kernel,
+ *      1 = matrix-core kernel with 16 output pixels x 64 channels per wave. Both compute
+ *      the same bits. get_tile of an eligible op always answers in this encoding; on any other op, or for a larger low byte,
+ *      set_tile returns SABER_HIP_INVALID_VALUE and changes nothing. */
 int saber_hip_conv2d_set_tile(saber_hip_conv_t* op, int tile);
 int saber_hip_conv2d_get_tile(const saber_hip_conv_t* op);
 int saber_hip_conv2d_autotune(saber_hip_conv_t* op, const void* x, void* y, const void* res, void* workspace,
