@@ -6,6 +6,7 @@
 //   api_autotune.hip      per-op and per-pair autotuner (cold-L2 timing loop, kernel-reuse preference)
 //   api_ops.hip           fc, INT8 / FP32 GEMM, the streaming operators' wrappers
 //   api_chain.hip         conv1x1 chains (two / three convs in one launch): the table of launch forms, stream repacking, create / run
+//   api_sep.hip           separable pairs (depthwise 3x3 + pointwise 1x1 in one launch): eligibility, repacking, create / run
 //   api_net.hip           op-list executor: arena, lanes, hipGraph capture / replay, in-pass timing
 //   api_net_optimize.hip  executor-level fusions (saber_hip_net_optimize)
 //   api_net_autotune.hip  whole-net autotuner, selection save / restore
@@ -259,6 +260,17 @@ struct saber_hip_chain_stage {
     }
 };
 
+// a depthwise 3x3 INT8 conv and the pointwise 1x1 INT8 conv that reads it in one launch (conv_sep.hip); refers to the two ops, owns
+// the depthwise weights / constants and the pointwise fragment stream / constants as they were when it was created
+struct saber_hip_sep {
+    saber_hip_conv* dw = nullptr;
+    saber_hip_conv* pw = nullptr;
+    int form = 0;                   // the selected row of conv_sep.hip's form table (its code)
+    DevBuf<uint8_t> d_wdw, d_wpw, d_prm;
+    DevBuf<float> d_dw_bias, d_dw_scale;
+    std::string name;               // "sep_dw3x3_pw_i8_<form>" of the selected form
+};
+
 struct saber_hip_fc {
     saber_hip_fc_desc d;
     saber_hip_conv* conv = nullptr;
@@ -388,6 +400,11 @@ struct NetOp {
     // op (the pair, `skip`) launches nothing; stem_y1 / stem_y2 are the pair's outputs and this op's own output edge is not written
     saber_hip_stem_pair* stem_pair = nullptr;
     int stem_y1 = -1, stem_y2 = -1;
+    // a depthwise 3x3 conv and the 1x1 conv behind it (flag 16384, SABER_HIP_NET_SEPARABLE): THIS op is the depthwise conv, the next op is the
+    // pointwise one and carries `skip` while use_sep is set; this op's own output edge is then not written, sep_out is the pointwise output
+    saber_hip_sep* sep = nullptr;
+    int sep_out = -1;
+    bool use_sep = false;
     int lane = 0;            // 0: caller's stream, 1: the net's side stream (graph::Lane, operator_func.h:103-114)
     bool record = false;     // an op on the other lane consumes this op's output: record an event after it
     int p[16] = {0};
@@ -434,6 +451,7 @@ struct saber_hip_net {
     std::vector<saber_hip_chain*> owned_chains;
     std::vector<saber_hip_chain_stage*> owned_stages;
     std::vector<saber_hip_stem_pair*> owned_stem_pairs;
+    std::vector<saber_hip_sep*> owned_seps;
 };
 
 // Op-list capture (api_capture.hip; saber_hip_capture_begin / _end): while g_capture is set on the calling thread every
@@ -493,4 +511,10 @@ ChainForm chain_form_default(const saber_hip_chain* ch);      // create's choice
 ChainForm chain_form_plain(const saber_hip_chain* ch);      // what a placement-dependent form falls back to
 std::string chain_form_name(const saber_hip_chain* ch);      // of the selected form
 void for_each_chain_candidate(const saber_hip_chain* ch, bool shared_device, const std::function<void(const ChainForm&)>& fn);
+// separable pairs (api_sep.hip)
+bool conv_sep_ok(const saber_hip_conv* dw, const saber_hip_conv* pw, std::string* why);      // the pair is one conv_sep.hip can run
+bool sep_form_valid(const saber_hip_sep* sp, int code);      // the form exists for this pair
+void for_each_sep_form(const saber_hip_sep* sp, const std::function<void(int code)>& fn);      // its forms, in the autotuner's candidate order
+int sep_static_form(const saber_hip_sep* sp);      // the executor's static choice: a form code, or 0 = two launches
+void net_set_sep(saber_hip_net* net, int i, int code);      // api_net_optimize.hip: the site headed by ops[i] on (a valid form code) / off (0)
 int stage_run(saber_hip_chain_stage* st, const void* x, const void* res, void* const* y1, void* const* y2, hipStream_t s);   // api_chain.hip

@@ -42,6 +42,7 @@ int net_launch(saber_hip_net* net, const NetOp& o, hipStream_t s) {
             return rc;
         }
         if (o.chain && o.use_chain) return saber_hip_conv2d_chain_run(o.chain, T(o.in), T(o.in2), T(o.out), T(o.chain_out), s);
+        if (o.sep && o.use_sep) return saber_hip_conv2d_sep_run(o.sep, T(o.in), nullptr, T(o.sep_out), s);      // the depthwise edge stays in LDS
         if (o.conv->gpool) return saber_hip_conv2d_run_gpool(o.conv, T(o.in), T(o.out), T(o.in2), T(o.out2), s);
         return saber_hip_conv2d_run(o.conv, T(o.in), T(o.out), T(o.in2), ws, s);
     case OP_CONV_PAIR:
@@ -307,13 +308,14 @@ int saber_hip_net_compact_arena(saber_hip_net_t* net, const int* keep, int n_kee
         if (o.chain3) span(i, 3);
         if (o.chain) span(i, 2);
         if (o.stem_pair) span(i, 2);
+        if (o.sep) span(i, 2);      // (the one launch reads the depthwise conv's input while it writes the pointwise conv's output)
         if ((o.kind == OP_FC || o.kind == OP_FC_Q) && o.out2 >= 0) span(i, 2);
         if (i + 1 < nops && net->ops[i + 1].skip) span(i, 2);      // (whatever else made the follower silent)
     }
     for (int i = 0; i < nops; ++i) {
         const NetOp& o = net->ops[i];
         const int rd[] = {o.in, o.in2, o.chain3_res};
-        const int wr[] = {o.out, o.out2, o.chain_out, o.chain3_y1, o.chain3_y2, o.chain3_y3, o.stem_y1, o.stem_y2};
+        const int wr[] = {o.out, o.out2, o.chain_out, o.chain3_y1, o.chain3_y2, o.chain3_y3, o.stem_y1, o.stem_y2, o.sep_out};
         auto touch = [&](int t) {
             if (t < 0 || t >= nt) return;
             first[t] = std::min(first[t], g_lo[i]);
@@ -475,8 +477,8 @@ int saber_hip_net_set_lane(saber_hip_net_t* net, int index, int lane) {
     if (index < 0 || index >= (int)net->ops.size() || lane < 0 || lane > 1) return fail(SABER_HIP_INVALID_VALUE, "bad op index / lane");
     if (net->lanes_ready) return fail(SABER_HIP_INVALID_VALUE, "lanes are fixed after the first run");
     for (const NetOp& o : net->ops)
-        if (lane && (o.chain || o.chain3 || o.stem_pair))
-            return fail(SABER_HIP_INVALID_VALUE, "the net has conv1x1 chain launches: lanes must be assigned before saber_hip_net_optimize (a chain launch spans several ops' tensors)");
+        if (lane && (o.chain || o.chain3 || o.stem_pair || o.sep))
+            return fail(SABER_HIP_INVALID_VALUE, "the net has launches that span several ops' tensors (conv1x1 chains, the stem pair, separable sites): lanes must be assigned before saber_hip_net_optimize");
     if (lane) {   // both lanes share the arena's single workspace: an op that uses it stays on the main lane
         const NetOp& o = net->ops[index];
         const size_t ws = o.kind == OP_CONV && o.conv ? o.conv->ws_bytes : (o.kind == OP_FC && o.fc ? saber_hip_fc_workspace_bytes(o.fc) : 0);
@@ -558,7 +560,7 @@ int saber_hip_net_op_work(const saber_hip_net_t* net, int index, double* bytes, 
             conv_work(net->ops[index + 1].conv, *bytes, *flops);
         } else if (o.chain3 && o.use_chain3) {
             for (int j = index + 1; j < (int)net->ops.size() && net->ops[j].skip; ++j) conv_work(net->ops[j].conv, *bytes, *flops);
-        } else if (o.chain && o.use_chain) {
+        } else if ((o.chain && o.use_chain) || (o.sep && o.use_sep)) {
             if (index + 1 < (int)net->ops.size() && net->ops[index + 1].skip) conv_work(net->ops[index + 1].conv, *bytes, *flops);
         }
         return SABER_HIP_OK;
@@ -674,7 +676,7 @@ int saber_hip_net_tensor_unwritten(const saber_hip_net_t* net, int id) {
     if (id < 0 || id >= (int)net->tensor_bytes.size()) return 0;
     if (net->tensor_bytes[id] == 0) return 1;      // the edge was removed by saber_hip_net_optimize (it has no storage)
     for (const NetOp& o : net->ops)
-        if (((o.chain3 && o.use_chain3) || o.stem_pair) && o.out == id) return 1;
+        if (((o.chain3 && o.use_chain3) || o.stem_pair || (o.sep && o.use_sep)) && o.out == id) return 1;
     return 0;
 }
 // After a pass has COMPLETED (the caller has synchronised): did one of its cooperative launches - a stage launch, a two-workgroup
@@ -738,6 +740,7 @@ void saber_hip_net_destroy(saber_hip_net_t* net) {
     for (saber_hip_stem_pair* sp : net->owned_stem_pairs) saber_hip_conv2d_stem_pair_destroy(sp);
     for (saber_hip_chain_stage* st : net->owned_stages) saber_hip_conv2d_stage_destroy(st);
     for (saber_hip_chain* c : net->owned_chains) saber_hip_conv2d_chain_destroy(c);
+    for (saber_hip_sep* sp : net->owned_seps) saber_hip_conv2d_sep_destroy(sp);
     for (saber_hip_conv* c : net->owned) saber_hip_conv2d_destroy(c);
     for (hipEvent_t e : net->ev_op)
         if (e) (void)hipEventDestroy(e);

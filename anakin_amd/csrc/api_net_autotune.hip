@@ -12,12 +12,14 @@ static saber_hip_conv* net_op_conv(saber_hip_net* net, int index) {
     return nullptr;
 }
 // bits 0..23: saber_hip_conv2d_get_tile of the op; chain heads add bit 28 (a chain decision is recorded) and the chain's
-// pixel fragments in bits 24..27 (0: run as two launches)
+// pixel fragments in bits 24..27 (0: run as two launches). A depthwise op never heads a chain: bits 28 AND 29 together on it say that a
+// separable decision is recorded (flag 16384), bits 24..27 then hold the separable launch's form code (0: two launches)
 int saber_hip_net_get_choice(saber_hip_net_t* net, int index) {
     saber_hip_conv* c = net_op_conv(net, index);
     int choice = (c && !c->pool_fused && (c->algo <= ALGO_IGEMM_F32 || dw_ok(c) || group_ok(c))) ? saber_hip_conv2d_get_tile(c) : 0;
     if (c && net->ops[index].chain) choice |= (1 << 28) | ((net->ops[index].use_chain ? net->ops[index].chain->form.code : 0) << 24);
     if (c && net->ops[index].chain3) choice |= (1 << 29) | ((net->ops[index].use_chain3 ? net->ops[index].chain3->form.code : 0) << 24);
+    if (c && net->ops[index].sep) choice |= (3 << 28) | ((net->ops[index].use_sep ? net->ops[index].sep->form : 0) << 24);
     if (c && net->ops[index].stage && net->ops[index].use_stage) choice |= 1 << 30;      // this op launches its whole stage
     return choice;
 }
@@ -42,6 +44,9 @@ int saber_hip_net_set_choice(saber_hip_net_t* net, int index, int choice) {
     int tn = chain_bits & 15;      // 0: the chain off
     if (ch && net->shared_device && chain_form(ch, tn).placement) tn = chain_form_plain(ch).code;
     if (ch && tn && !chain_form_valid(ch, tn)) return saber_hip_conv2d_chain_set_tile(ch, tn);      // (its status and message)
+    // ... and the separable decision (bits 28 and 29 together on the depthwise op of a site), refused likewise
+    const bool sep_bits = o.sep && (chain_bits & 48) == 48;
+    if (sep_bits && tn && !sep_form_valid(o.sep, tn)) return saber_hip_conv2d_sep_set_tile(o.sep, tn);      // (its status and message)
     int rc = choice ? saber_hip_conv2d_set_tile(c, choice) : SABER_HIP_OK;
     if (rc) return rc;
     o.name = std::string(o.kind == OP_FC || o.kind == OP_FC_Q ? "fc:" : "conv:") + c->algo_name;
@@ -53,6 +58,8 @@ int saber_hip_net_set_choice(saber_hip_net_t* net, int index, int choice) {
     if (o.skip) o.name = (o.chain3 && o.use_chain3) ? "conv:(in the stage launch)" : "conv:(in the chain launch)";
     if (o.skip && o.kind == OP_CONV_PAIR) o.name = (index > 0 && net->ops[index - 1].stem_pair) ? "conv:(in the stem launch)" : "conv:(in the chain launch)";
     if (o.stem_pair) o.name = stem_pair_name(o);
+    if (o.sep) net_set_sep(net, index, sep_bits ? tn : (o.use_sep ? o.sep->form : 0));      // (a choice without the bits leaves the site as it is; the names follow)
+    if (o.skip && index > 0 && net->ops[index - 1].sep && net->ops[index - 1].use_sep) o.name = "conv:(in the separable launch)";
     if (net->exec) {
         (void)hipGraphExecDestroy(net->exec);
         (void)hipGraphDestroy(net->graph);
@@ -73,7 +80,7 @@ static int net_consolidate_kernels(saber_hip_net* net, hipStream_t s) {
         if (e[0] == '1') return SABER_HIP_OK;
     struct Site { int op; unsigned long long key; ConvSel choice; };
     auto conv_of = [&](const NetOp& o) -> saber_hip_conv* {
-        if (o.skip || (o.chain && o.use_chain) || (o.chain3 && o.use_chain3) || (o.stage && o.use_stage)) return nullptr;
+        if (o.skip || (o.chain && o.use_chain) || (o.chain3 && o.use_chain3) || (o.stage && o.use_stage) || (o.sep && o.use_sep)) return nullptr;
         if (o.kind != OP_CONV && o.kind != OP_CONV_PAIR) return nullptr;
         if (net->reproducible_fp32 && o.conv && !o.conv->is_i8) return nullptr;      // flag 8192: this pass moves no FP32 op either
         return (o.conv && !o.conv->pool_fused && o.conv->algo <= ALGO_IGEMM_F32) ? o.conv : nullptr;
@@ -263,6 +270,30 @@ int saber_hip_net_autotune(saber_hip_net_t* net, saber_hip_stream_t stream, int 
                 net_set_chain_mode(net, first + 3 * k + 1, modes[k]);
             }
         }
+        rc = run_all();   // every written output holds the selected form's result
+        if (rc) return rc;
+    }
+    // separable sites (flag 16384): the two tuned launches against every form of the one launch, cold L2, on the real tensors
+    for (size_t i = 0; i + 1 < net->ops.size(); ++i) {
+        NetOp& D = net->ops[i];
+        if (!D.sep) continue;
+        hipStream_t s = (hipStream_t)stream;
+        auto run_all = [&]() -> int { return net_launch(net, net->ops[i], s) | net_launch(net, net->ops[i + 1], s); };
+        auto timed = [&](float* t) { return time_enqueued(s, run_all, 20, t); };
+        float best = 0.f;
+        int best_code = 0;
+        net_set_sep(net, (int)i, 0);
+        int rc = timed(&best);
+        if (rc) return rc;
+        log_cand(D.conv, "separate", best);
+        for_each_sep_form(D.sep, [&](int code) {
+            float us = -1.f;
+            net_set_sep(net, (int)i, code);
+            const int rt = timed(&us);
+            log_cand(D.conv, D.name.substr(5), us);
+            if (rt == SABER_HIP_OK && us < best) { best = us; best_code = code; }
+        });
+        net_set_sep(net, (int)i, best_code);
         rc = run_all();   // every written output holds the selected form's result
         if (rc) return rc;
     }

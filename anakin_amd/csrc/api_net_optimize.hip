@@ -78,6 +78,18 @@ int net_chain_mode(const saber_hip_net* net, int ia) {
     const NetOp& A = net->ops[ia];
     return A.skip ? 2 : (A.use_chain ? 1 : 0);
 }
+// The separable site headed by ops[i] (NetOp::sep): code = a valid form of the pair -> the one launch with that form, the pointwise op behind
+// it launches nothing and the depthwise edge is not written; 0 -> the two ops launch on their own again.
+void net_set_sep(saber_hip_net* net, int i, int code) {
+    NetOp& D = net->ops[i];
+    if (!D.sep || i + 1 >= (int)net->ops.size()) return;
+    NetOp& P = net->ops[i + 1];
+    if (code && saber_hip_conv2d_sep_set_tile(D.sep, code) != SABER_HIP_OK) code = 0;
+    D.use_sep = code != 0;
+    P.skip = D.use_sep;
+    D.name = std::string("conv:") + (D.use_sep ? saber_hip_conv2d_sep_algo(D.sep) : D.conv->algo_name.c_str());
+    P.name = D.use_sep ? std::string("conv:(in the separable launch)") : std::string("conv:") + P.conv->algo_name;
+}
 static int clone_conv_i8(const saber_hip_conv* src, const saber_hip_conv_desc& d, saber_hip_conv** out) {
     int rc = saber_hip_conv2d_create(&d, out);
     if (rc) return rc;
@@ -114,8 +126,13 @@ int saber_hip_net_optimize(saber_hip_net_t* net, int flags) {
             if (!dead[i] && (ops[i].out == t || ops[i].out2 == t)) return i;
         return -1;
     };
+    // an op of a separable site (flag 16384 in an earlier call) keeps its conv: the site's object was made from it
+    auto in_sep = [&](const NetOp& o) {
+        const size_t i = (size_t)(&o - ops.data());
+        return o.sep != nullptr || (i > 0 && i < ops.size() && ops[i - 1].sep != nullptr);
+    };
     auto plain_i8_conv = [&](const NetOp& o) {
-        return o.kind == OP_CONV && o.conv && o.conv->is_i8 && o.conv->weights_set && o.conv->epi == EPI_I8_CONV &&
+        return !in_sep(o) && o.kind == OP_CONV && o.conv && o.conv->is_i8 && o.conv->weights_set && o.conv->epi == EPI_I8_CONV &&
                o.conv->d.res_mode == SABER_HIP_RES_NONE && !o.conv->pair_k2 && !o.conv->pool_fused && o.lane == 0;
     };
     // ---- 1: conv + eltwise -----------------------------------------------------------------------------------
@@ -286,7 +303,7 @@ int saber_hip_net_optimize(saber_hip_net_t* net, int flags) {
                 q.p[12] == SABER_HIP_POOL_MAX || q.p[13] != q.p[14])
                 continue;
             const int p = producer(q.in, (int)i);
-            if (p < 0 || ops[p].kind != OP_CONV || !ops[p].conv || ops[p].lane != q.lane || ops[p].out2 >= 0) continue;
+            if (p < 0 || ops[p].kind != OP_CONV || !ops[p].conv || ops[p].lane != q.lane || ops[p].out2 >= 0 || in_sep(ops[p])) continue;
             const saber_hip_conv* src = ops[p].conv;
             if (!src->is_i8 || src->pair_k2 || src->pool_fused || src->gpool || !img_conv_ok(src) || src->d.n != q.p[0] ||
                 src->d.k != q.p[3] || src->oh != q.p[1] || src->ow != q.p[2] || src->d.out_dtype != q.p[13])
@@ -348,6 +365,30 @@ int saber_hip_net_optimize(saber_hip_net_t* net, int flags) {
     bool two_lanes = false;
     for (const NetOp& o : ops) two_lanes |= o.lane != 0;
     if (two_lanes) flags &= ~(16 | 32);
+    // ---- 16384 (SABER_HIP_NET_SEPARABLE): a depthwise 3x3 conv + the 1x1 conv that alone reads it, the NEXT op (MobileNet's separable pairs)
+    // -> a site of the one-launch form (conv_sep.hip). Both ops stay; which sites are on is sep_static_form's choice until the autotuner has
+    // timed every form against the two launches. No workgroup of that kernel depends on another: allowed on a shared device. Counted: the
+    // sites formed (each removes one launch while a form is selected).
+    if ((flags & SABER_HIP_NET_SEPARABLE) && !two_lanes) {
+        for (size_t i = 0; i + 1 < ops.size(); ++i) {
+            NetOp& D = ops[i];
+            NetOp& P = ops[i + 1];
+            if (D.kind != OP_CONV || P.kind != OP_CONV || !D.conv || !P.conv || D.sep || D.skip || P.skip || D.lane || P.lane || D.chain || D.chain3 ||
+                D.stem_pair || P.chain || P.chain3 || P.stem_pair || P.sep || D.in2 >= 0 || P.in2 >= 0 || D.out2 >= 0 || P.out2 >= 0 || P.in != D.out)
+                continue;
+            if (!D.conv->is_i8 || !dw_ok(D.conv)) continue;
+            int readers = 0;
+            for (const NetOp& o : ops) readers += (o.in == D.out) + (o.in2 == D.out);
+            if (readers != 1) continue;
+            saber_hip_sep* sp = nullptr;
+            if (saber_hip_conv2d_sep_create(D.conv, P.conv, &sp) != SABER_HIP_OK) continue;      // not a pair the kernel takes
+            net->owned_seps.push_back(sp);
+            D.sep = sp;
+            D.sep_out = P.out;
+            net_set_sep(net, (int)i, sep_static_form(sp));
+            ++removed;
+        }
+    }
     // ---- 16: conv1x1 chains (on the compacted list: the pair must be adjacent) --------------------------------
     if (flags & 16) {
         for (size_t i = 0; i + 1 < ops.size(); ++i) {

@@ -325,6 +325,36 @@ bool conv_group3x3_ok(int n, int c, int k, int group, int kh, int kw, int stride
                       int oh, int ow);
 hipError_t launch_conv_group3x3(int form, const ConvKArgs& a, int group, hipStream_t s);
 
+// Depthwise 3x3 + pointwise 1x1 INT8 in one launch (MobileNet's separable pair; conv_sep.hip): a workgroup computes the depthwise conv of a
+// tile of `rows` x 16 output pixels for all C channels into LDS and multiplies it on the i8 matrix cores with its slice of the pointwise
+// conv's output channels. C % 32 == 0, 32 <= C <= 1024, K % 32 == 0.
+struct SepKArgs {
+    const void* x;        // the depthwise conv's input [N][H][W][C], s8 or u8
+    const void* wdw;      // its weights [tap][C] s8
+    const float* dw_bias; // its bias' [C] (never null: zeros stand for "no bias", (float)acc + 0.f == (float)acc)
+    const float* dw_scale;
+    const void* wpw;      // the pointwise conv's weights in fragment order (sep_pw_pack)
+    const void* prm;      // the pointwise conv's {scale[4], bias'[4], comp[4]} per 4 output channels, padded to a multiple of 64 channels
+    void* y_dw;           // [N][OH][OW][C] 8-bit, or null: the depthwise edge is not written
+    void* y_pw;           // [N][OH][OW][K] 8-bit
+    int N, H, W, C, OH, OW, K;
+    int stride, pad;
+    int tiles_x, tiles_per_img;   // 16-column tiles per tile row, tiles per image
+    int kgroups;          // 64-channel groups of the pointwise conv per workgroup
+    int nslices;          // workgroups per pixel tile (each recomputes the depthwise tile): ceil(K / 64 / kgroups)
+    int dw_relu, mid_u8;  // the depthwise conv's relu and output type (= the pointwise conv's input type)
+    int pw_relu, out_u8;
+};
+// the table of launch forms: code 1 .. 15 -> pixel rows per tile, output channels per workgroup (0: all of them), waves per workgroup; false: no
+// such form. sep_form_ok: the form exists and fits this pair (a form that splits K needs more than one slice)
+constexpr int SEP_MAX_CODE = 15;
+bool conv_sep_form(int code, int* rows, int* kper, int* waves);
+bool conv_sep_form_ok(int code, int c, int k);
+size_t conv_sep_lds_bytes(int rows, int c);
+void sep_pw_pack(const int8_t* w_kc, int k, int c, std::vector<uint8_t>& out);      // [ceil(K / 64)][ceil(C / 64)][4][64 lanes][16], zero padded
+hipError_t conv_sep_prepare();      // per device, once: the kernels may use more than 64 KB of LDS
+hipError_t launch_conv_sep(int code, bool in_u8, const SepKArgs& a, hipStream_t s);
+
 // reads `bytes` of device memory through every XCD (autotuning: the timed launch then finds none of its operands in
 // an L2, which is how it runs inside the op list)
 hipError_t launch_l2_flush(const void* buf, size_t bytes, unsigned* sink, hipStream_t s);

@@ -381,6 +381,37 @@ class SaberStemPair:
             pass
 
 
+class SaberConvSep:
+    """A depthwise 3x3 INT8 conv `dw` and the 1x1 INT8 conv `pw` that reads it in ONE launch (saber_hip_conv2d_sep_create): MobileNet's
+    separable pair. dispatch(x, y_pw, y_dw=None): y_dw only when the depthwise edge is wanted. The outputs hold the bits of dispatching
+    the two operators one after the other (net.cpp:417-509). The object keeps the weights the ops had when it was made."""
+
+    def __init__(self, dw, pw):
+        self.ops = (dw, pw)                          # keep them alive: the object refers to them
+        self.h = C.c_void_p()
+        L.check(L.load().saber_hip_conv2d_sep_create(dw.h, pw.h, C.byref(self.h)))
+
+    def dispatch(self, x, y_pw, y_dw=None):
+        L.check(L.load().saber_hip_conv2d_sep_run(self.h, _p(x), _p(y_dw), _p(y_pw), _stream()))
+        return y_pw
+
+    def set_tile(self, code):
+        L.check(L.load().saber_hip_conv2d_sep_set_tile(self.h, code))
+
+    def tile(self):
+        return L.load().saber_hip_conv2d_sep_get_tile(self.h)
+
+    def algo(self):
+        return L.load().saber_hip_conv2d_sep_algo(self.h).decode()
+
+    def __del__(self):
+        try:
+            if self.h:
+                L.load().saber_hip_conv2d_sep_destroy(self.h)
+        except Exception:
+            pass
+
+
 class SaberStage:
     """XCD-resident stage (saber_hip_stage_create): `phases` = [(conv, in_slot, out_slot, res_slot | -1), ...] run as ONE
     persistent launch, image i on XCD i % 8; dispatch(tensors) takes the device tensors by slot. Every output slot holds

@@ -292,7 +292,7 @@ def _out_hw(h, k, s, p):
 
 
 def build_int8_net(model, scales, batch, hw=224, fuse=True, chain=2, stage=True, stem_pair=True, head_pair=False, shared_device=False,
-                   fc_softmax=True, absorb_pool=True, **legacy):
+                   fc_softmax=True, absorb_pool=True, separable=False, **legacy):
     """ResNet INT8 op list on the device (see the module docstring for the dtype rules): ONE op per reference operator, exactly the list
     `model["spec"]` holds (workloads.framework_spec: what the reference's own optimiser emits) - and, with `fuse`, handed to the C++ host
     side (saber_hip_net_optimize, the product's only executor-level fuser) which finds conv + eltwise, sibling pairs, conv + pooling,
@@ -309,6 +309,9 @@ def build_int8_net(model, scales, batch, hw=224, fuse=True, chain=2, stage=True,
     shared_device: the net runs beside other nets / streams / processes on its GPU (flag SABER_HIP_NET_SHARED_DEVICE = 2048): no stage
     launch, no cooperating-workgroup chains, no split-K through one XCD's L2 - excluded from the static selection, the autotuner and
     restored selections.
+    separable (opt-in): a depthwise 3x3 conv and the 1x1 conv that alone reads it (MobileNet's separable pairs) become sites of the one-launch
+    form (flag SABER_HIP_NET_SEPARABLE = 16384, after the flag-15 pass): net.separated counts them. Which sites run fused is the static
+    rule's choice, then the autotuner's (profiles/sep/README.md); the default builds exactly the list it built before.
     (The Python fuser of rounds 1 - 5 lives in tests/py_fuser.py: test infrastructure.)"""
     from . import lib as L
     from . import saber as S
@@ -376,9 +379,12 @@ def build_int8_net(model, scales, batch, hw=224, fuse=True, chain=2, stage=True,
     if shared_device:
         net.optimize(2048)           # (sticks to the net: every later optimize / autotune / set_choices call honours it)
         stage = False
-    net.removed = net.absorbed = net.gpooled = net.stem_paired = net.chained = net.fc_softmaxed = 0
+    net.removed = net.absorbed = net.gpooled = net.stem_paired = net.chained = net.fc_softmaxed = net.separated = 0
     if fuse:
         net.removed = net.optimize(15)      # conv + eltwise, sibling pairs, conv + pooling, pool -> fc quantisation
+    if separable:
+        net.separated = net.optimize(16384)      # the sites formed (each removes a launch while one of its forms is selected)
+    if fuse:
         # a stride-up shortcut pooling (framework_spec) read only by a fused eltwise epilogue is folded into that read
         net.absorbed = net.optimize(64) if absorb_pool else 0
         # the last block's conv (+ fused eltwise) also writes the global average pooling of its output (flag 128): pool5's launch goes

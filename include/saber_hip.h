@@ -252,6 +252,25 @@ void saber_hip_conv2d_stem_pair_destroy(saber_hip_stem_pair_t* sp);
 int saber_hip_conv2d_stem_pair_run(saber_hip_stem_pair_t* sp, const void* x, void* y_pool, void* y_a, void* y_b, void* workspace,
                                    saber_hip_stream_t stream);
 
+/* Separable pair: `dw` = a depthwise 3x3 INT8 conv (group == C == K, stride 1 | 2, pad 0 | 1, 8-bit NHWC in and out, C % 32 == 0,
+ * 32 <= C <= 1024) and `pw` = the plain 1x1 / stride-1 INT8 conv that reads its output (C -> K, K % 32 == 0, no residual, no fused pooling,
+ * 8-bit NHWC output) run as ONE launch (anakin_amd/csrc/conv_sep.hip: sep_dw3x3_pw_i8): a workgroup computes the depthwise conv of a pixel
+ * tile into LDS and multiplies it on the matrix cores - MobileNet-v1's 13 pairs. An executor-level fusion with no counterpart in the
+ * reference (framework/core/net/net.cpp:417-509 dispatches one operator at a time). y_pw - and y_dw unless it is NULL, in which case the
+ * depthwise edge is not written - hold the bits of  saber_hip_conv2d_run(dw) ; saber_hip_conv2d_run(pw). The object refers to the two ops
+ * (they must outlive it) and owns the packed pointwise weight stream and both ops' parameter tables: it KEEPS THE WEIGHTS ITS MEMBERS HAD
+ * WHEN IT WAS CREATED. Null operands: SABER_HIP_INVALID_VALUE; operands without weights or not of this shape: SABER_HIP_UNIMPL.
+ * set_tile takes a form code 1 .. 15 (pixel rows per tile, output channels per workgroup, waves: the table in conv_sep.hip; some forms
+ * split K over several workgroups that each recompute the depthwise tile); a code without a form for this pair returns
+ * SABER_HIP_INVALID_VALUE and changes nothing. algo: "sep_dw3x3_pw_i8_<form>". */
+typedef struct saber_hip_sep saber_hip_sep_t;
+int saber_hip_conv2d_sep_create(saber_hip_conv_t* dw, saber_hip_conv_t* pw, saber_hip_sep_t** out);
+int saber_hip_conv2d_sep_run(saber_hip_sep_t* sep, const void* x, void* y_dw /* may be NULL */, void* y_pw, saber_hip_stream_t stream);
+int saber_hip_conv2d_sep_set_tile(saber_hip_sep_t* sep, int code);
+int saber_hip_conv2d_sep_get_tile(const saber_hip_sep_t* sep);
+const char* saber_hip_conv2d_sep_algo(const saber_hip_sep_t* sep);
+void saber_hip_conv2d_sep_destroy(saber_hip_sep_t* sep);
+
 /* XCD-resident stage: a run of INT8 convolutions over SMALL feature maps (h * w <= 64 pixels per image: ResNet's res5) as
  * ONE persistent launch. Image i is computed entirely on XCD i % 8 (32 CUs, one workgroup each); the convolutions
  * ("phases") follow each other inside the kernel, separated by an XCD-local barrier where one reads what an earlier one
@@ -481,9 +500,19 @@ int saber_hip_net_add_fc_q(saber_hip_net_t* net, saber_hip_fc_t* op, int in_q_id
  * nets built from one model answer bit-identically (the reference's x86 FP32 path is deterministic for a fixed thread count; this is
  * the switch that gives a maintainer the same property, at the static selection's speed). INT8 ops are exact under every selection
  * and stay tunable.
+ * 16384 (SABER_HIP_NET_SEPARABLE; NOT in 255, never implied): a depthwise 3x3 INT8 conv on lane 0 whose output has exactly one reader, the
+ * NEXT op, a plain 1x1 INT8 conv that saber_hip_conv2d_sep_create accepts together with it (MobileNet's separable pairs) -> a site of the
+ * one-launch form. Both ops stay in the list; while a form is selected the 1x1 conv launches nothing and the depthwise edge is not written
+ * (saber_hip_net_tensor_unwritten). Which sites are ON is the static rule's choice (measured, profiles/sep/README.md), then
+ * saber_hip_net_autotune's, which times every form against the two tuned launches; saber_hip_net_get_choice of the depthwise op reports
+ * (3 << 28) | (form << 24) | its own selection - bits 28 and 29 together: a separable decision is recorded, form 0 = two launches.
+ * Ignored in a net with a side lane (as 16 and 32); allowed with SABER_HIP_NET_SHARED_DEVICE (no workgroup depends on another).
+ * For THIS flag the return value counts the SITES formed, whether the static rule turns them on or not (a site removes one launch
+ * while a form is selected; saber_hip_net_num_launches reports what a pass launches now) - the one exception to the sentence below.
  * Bytes of every surviving edge are unchanged. Returns the number of launches removed (>= 0) or a status < 0. */
 #define SABER_HIP_NET_SHARED_DEVICE 2048
 #define SABER_HIP_NET_REPRODUCIBLE_FP32 8192
+#define SABER_HIP_NET_SEPARABLE 16384
 int saber_hip_net_optimize(saber_hip_net_t* net, int flags);
 /* How many cooperative launches of this net have reported a failed pass since it was created (each made saber_hip_net_status /
  * the site's next launch return SABER_HIP_RUNTIME_ERROR once and its site fall back to single-workgroup launches): 0 on a net that
