@@ -142,7 +142,7 @@ static void pack_coop4_stream(const saber_hip_conv* c3, const saber_hip_conv* a,
                 for (int kl = 0; kl < 2; ++kl) pack_frag3(c3->wq_oihw.data(), C, q * 64 + nt * 16, tap, kh * 2 + kl, out);
             for (int i = 0; i < 4; ++i)
                 for (int mf = 0; mf < 2; ++mf) pack_frag1(a->wq_oihw.data(), C, q * 256 + w * 32, 2, mf, (q + i) & 3, out);
-            for (int jj = 0; jj < 8; ++jj) {
+            for (int jj = 0; b && jj < 8; ++jj) {      // (b == nullptr: a stage's tail has no second 1x1 conv - 26 fragments per (quarter, wave))
                 const int j = jj < 2 ? kh * 2 + jj : 4 + kh * 6 + (jj - 2);
                 pack_frag1(b->wq_oihw.data(), K1, q * 64 + nt * 16, 1, 0, (q * 4 + j) & 15, out);
             }
@@ -230,8 +230,18 @@ saber_hip_chain::~saber_hip_chain() {
 // ------------------------------------------------------------------------------------------------
 // ceil(2^32 / d) for the kernels' __umulhi divisions by a tile count; 0 for d == 1 (they then skip the division)
 static unsigned div_magic(int d) { return d >= 2 ? (unsigned)((0x100000000ull + (unsigned)d - 1) / (unsigned)d) : 0u; }
-static int stage_build(saber_hip_chain* const* chains, int n, bool per_image, saber_hip_chain_stage** out) {
+// tail (optional): the strided head behind the run - conv3x3 / stride 2 + conv1x1 with the shortcut sub-sampled by 2, no second 1x1 conv -
+// whose 3x3 conv reads the last block's second output and whose shortcut is the last block's first output; it then runs inside the launch
+// whenever stage_run is given its output
+static int stage_build(saber_hip_chain* const* chains, int n, bool per_image, saber_hip_chain* tail, saber_hip_chain_stage** out) {
     if (!chains || n <= 0 || n > saber_mi355x::STAGE4_LONG || !out) return fail(SABER_HIP_INVALID_VALUE, "stage: 1..24 chains");
+    if (tail) {
+        if (!chains[0] || chains[0]->c1 != 256 || tail->c1 != 256) return fail(SABER_HIP_INVALID_VALUE, "stage: a tail goes with a C = 256 stage only");
+        if (n < 2 || !per_image || n + 1 > saber_mi355x::STAGE4_LONG) return fail(SABER_HIP_INVALID_VALUE, "stage: a tail needs 2..23 blocks, an image per XCD");
+        if (!tail->c3 || tail->b || tail->b2 || tail->c3->d.stride_h != 2 || tail->c3->d.stride_w != 2)
+            return fail(SABER_HIP_INVALID_VALUE, "stage: the tail must be a conv3x3 / stride 2 + conv1x1 chain without a second 1x1 conv");
+        if (tail->a->d.res_stride != 2) return fail(SABER_HIP_INVALID_VALUE, "stage: the tail's shortcut must be sub-sampled by 2");
+    }
     if (n > 1 && !per_image) return fail(SABER_HIP_INVALID_VALUE, "stage: several blocks need an image per XCD");
     if (n < 2 && chains[0] && chains[0]->c1 == 128) return fail(SABER_HIP_INVALID_VALUE, "stage: at C = 128 a stage is at least two blocks");
     const saber_hip_chain* c0 = chains[0];
@@ -255,6 +265,13 @@ static int stage_build(saber_hip_chain* const* chains, int n, bool per_image, sa
         blk.push_back(B);
     }
     const saber_hip_conv_desc& d0 = c0->a->d;
+    if (tail) {
+        const saber_hip_conv_desc &d3 = tail->c3->d, &da = tail->a->d;
+        if (d3.n != d0.n || d3.h != d0.h || d3.w != d0.w || da.res_h != d0.h || da.res_w != d0.w)
+            return fail(SABER_HIP_INVALID_VALUE, "stage: the tail's 3x3 conv and shortcut read tensors of the blocks' shape");
+        if ((tail->c3->x_dtype == DT_U8) != (chains[n - 1]->b->d.out_dtype == SABER_HIP_U8))
+            return fail(SABER_HIP_INVALID_VALUE, "stage: the tail's 3x3 conv reads what the last block's last conv writes");
+    }
     saber_hip_chain_stage* st = new saber_hip_chain_stage();
     st->chains.assign(chains, chains + n);
     st->c1 = c0->c1;
@@ -273,7 +290,22 @@ static int stage_build(saber_hip_chain* const* chains, int n, bool per_image, sa
                     "of 2 x 16 pixels; C = 128: width <= 64, <= 32 tiles)");
     }
     const size_t tiles = (size_t)d0.n * st->tiles_per_img;
-    hipError_t e = st->d_blk.upload(blk);
+    hipError_t e = hipSuccess;
+    if (tail) {      // its constants are block n of the table (prm2: unused, the launch copies it like a block's - any readable constants do)
+        std::vector<uint8_t> ts;
+        pack_coop4_stream(tail->c3, tail->a, nullptr, ts);
+        e = st->d_tail_stream.upload(ts);
+        const saber_hip_conv_desc& da = tail->a->d;
+        saber_mi355x::StageBlk B;
+        std::memset(&B, 0, sizeof B);
+        B.wstream = st->d_tail_stream.p; B.prm0 = tail->d_prm0.p; B.prm1 = tail->d_prm1.p; B.prm2 = tail->d_prm0.p;
+        B.coeff_conv = da.coeff_conv; B.scale_conv = tail->a->out_scale; B.coeff_res = da.coeff_res; B.scale_res = da.scale_res;
+        B.in0_u8 = tail->c3->x_dtype == DT_U8; B.relu0 = tail->c3->d.act == SABER_HIP_ACT_RELU;
+        B.in_u8 = tail->a->x_dtype == DT_U8; B.relu1 = da.act == SABER_HIP_ACT_RELU; B.res_relu = da.res_act == SABER_HIP_ACT_RELU;
+        blk.push_back(B);
+        st->tail = tail;
+    }
+    if (e == hipSuccess) e = st->d_blk.upload(blk);
     if (e == hipSuccess && st->c1 == 256) e = st->d_grp_ctr.alloc_zero(tiles * 32);
     if (e == hipSuccess) e = st->d_img_ctr.alloc_zero((size_t)d0.n * (st->tiles_per_img + 1) * 16);
     if (e == hipSuccess) e = st->d_xcc.alloc_zero(tiles * 32);
@@ -288,7 +320,7 @@ static int stage_build(saber_hip_chain* const* chains, int n, bool per_image, sa
     return SABER_HIP_OK;
 }
 template <int MAXB>
-static int stage_launch(saber_hip_chain_stage* st, const void* x, const void* res, void* const* y1, void* const* y2, hipStream_t s) {
+static int stage_launch(saber_hip_chain_stage* st, const void* x, const void* res, void* const* y1, void* const* y2, void* y_tail, hipStream_t s) {
     saber_mi355x::Stage4KArgs<MAXB> k;
     std::memset(&k, 0, sizeof k);
     k.x = x; k.res = res; k.zero = zero_page();
@@ -299,21 +331,28 @@ static int stage_launch(saber_hip_chain_stage* st, const void* x, const void* re
     k.mg_tiles_x = div_magic(st->tiles_x); k.mg_tpi = div_magic(st->tiles_per_img); k.mg_wpi = div_magic(st->tiles_per_img * 4);
     k.per_image = st->per_image;
     for (int i = 0; i < k.nblk; ++i) { k.y1[i] = y1[i]; k.y2[i] = y2[i]; }
-    HIP_TRY(st->c1 == 256 ? saber_mi355x::launch_conv_stage4(k, s) : saber_mi355x::launch_conv_stage1_c128(k, s));
+    if (y_tail) k.y1[k.nblk] = y_tail;      // (the slot behind the last block's: stage_run has picked an argument block with room for it)
+    HIP_TRY(st->c1 == 256 ? saber_mi355x::launch_conv_stage4(k, y_tail != nullptr, s) : saber_mi355x::launch_conv_stage1_c128(k, s));
     return SABER_HIP_OK;
 }
-int stage_run(saber_hip_chain_stage* st, const void* x, const void* res, void* const* y1, void* const* y2, hipStream_t s) {
+int stage_run(saber_hip_chain_stage* st, const void* x, const void* res, void* const* y1, void* const* y2, hipStream_t s, void* y_tail) {
+    if (y_tail && !st->tail) return fail(SABER_HIP_INVALID_VALUE, "stage: created without a tail");
     if (*(volatile unsigned*)st->h_err) {      // an earlier launch found cooperating workgroups on different XCDs or timed out in a barrier
         *(volatile unsigned*)st->h_err = 0u;
         return fail(SABER_HIP_RUNTIME_ERROR, "cooperative stage: an earlier launch's workgroups did not share an XCD or timed out at a barrier "
                     "(its outputs are not valid)");
     }
-    return (int)st->chains.size() <= saber_mi355x::STAGE4_SHORT ? stage_launch<saber_mi355x::STAGE4_SHORT>(st, x, res, y1, y2, s)
-                                                                : stage_launch<saber_mi355x::STAGE4_LONG>(st, x, res, y1, y2, s);
+    return (int)st->chains.size() + (y_tail ? 1 : 0) <= saber_mi355x::STAGE4_SHORT ? stage_launch<saber_mi355x::STAGE4_SHORT>(st, x, res, y1, y2, y_tail, s)
+                                                                                   : stage_launch<saber_mi355x::STAGE4_LONG>(st, x, res, y1, y2, y_tail, s);
 }
 int saber_hip_conv2d_stage_create(saber_hip_chain_t* const* chains, int n, saber_hip_chain_stage_t** out) {
     if (!xcd_round_robin()) return fail(SABER_HIP_UNIMPL, "stage: this device does not place workgroup b on XCD b % 8");
-    return stage_build(chains, n, true, out);
+    return stage_build(chains, n, true, nullptr, out);
+}
+int saber_hip_conv2d_stage_create_tail(saber_hip_chain_t* const* chains, int n, saber_hip_chain_t* tail, saber_hip_chain_stage_t** out) {
+    if (!tail) return fail(SABER_HIP_INVALID_VALUE, "null argument");
+    if (!xcd_round_robin()) return fail(SABER_HIP_UNIMPL, "stage: this device does not place workgroup b on XCD b % 8");
+    return stage_build(chains, n, true, tail, out);
 }
 void saber_hip_conv2d_stage_destroy(saber_hip_chain_stage_t* st) { delete st; }
 int saber_hip_conv2d_stage_run(saber_hip_chain_stage_t* st, const void* x, const void* res, void* const* y1, void* const* y2, saber_hip_stream_t stream) {
@@ -322,6 +361,14 @@ int saber_hip_conv2d_stage_run(saber_hip_chain_stage_t* st, const void* x, const
     for (size_t i = 0; i < st->chains.size(); ++i)
         if (!y1[i] || !y2[i]) return fail(SABER_HIP_INVALID_VALUE, "stage: an output pointer per block");
     return stage_run(st, x, res, y1, y2, (hipStream_t)stream);
+}
+int saber_hip_conv2d_stage_run_tail(saber_hip_chain_stage_t* st, const void* x, const void* res, void* const* y1, void* const* y2, void* y_tail,
+                                    saber_hip_stream_t stream) {
+    if (g_capture) return capture_unsupported("saber_hip_conv2d_stage_run_tail (saber_hip_net_optimize forms stages itself)");
+    if (!st || !x || !res || !y1 || !y2 || !y_tail) return fail(SABER_HIP_INVALID_VALUE, "null argument");
+    for (size_t i = 0; i < st->chains.size(); ++i)
+        if (!y1[i] || !y2[i]) return fail(SABER_HIP_INVALID_VALUE, "stage: an output pointer per block");
+    return stage_run(st, x, res, y1, y2, (hipStream_t)stream, y_tail);
 }
 // the weight stream of one layout, in the order the waves of the forms that read it consume it (conv1x1_chain.hip, conv_chain_coop.hip)
 static void pack_chain_stream(const saber_hip_chain* ch, ChainStream layout, std::vector<uint8_t>& out) {
@@ -451,7 +498,7 @@ static int chain_build(saber_hip_conv* c3, saber_hip_conv* a, saber_hip_conv* b,
         return hip_fail(e, "chain: device copies");
     }
     if (ch->d_stream[CS_COOP4].p) {      // the four-workgroup form = a one-block stage, tiles spread over all XCDs
-        const int rc = stage_build(&ch, 1, false, &ch->stage1);
+        const int rc = stage_build(&ch, 1, false, nullptr, &ch->stage1);
         if (rc != SABER_HIP_OK) {
             delete ch;
             return rc;

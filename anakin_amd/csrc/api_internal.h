@@ -248,6 +248,8 @@ struct saber_hip_chain {
 // hand-off counters / exchange tiles / XCC words of the launch, a pinned error word. The chains are NOT owned.
 struct saber_hip_chain_stage {
     std::vector<saber_hip_chain*> chains;
+    saber_hip_chain* tail = nullptr;      // the strided head behind the run (saber_hip_conv2d_stage_create_tail): d_blk[chains.size()] holds its constants
+    DevBuf<uint8_t> d_tail_stream;        // ... and this its weight fragments (api_chain.hip: pack_coop4_stream without b)
     DevBuf<saber_mi355x::StageBlk> d_blk;
     DevBuf<unsigned long long> d_grp_ctr, d_img_ctr;
     DevBuf<uint8_t> d_xch;
@@ -396,6 +398,11 @@ struct NetOp {
     saber_hip_chain_stage* stage = nullptr;
     int stage_n = 0;
     bool use_stage = false;
+    // ... with the strided head behind the run as the launch's TAIL (the stage was created with one): the two ops behind the last block -
+    // ops[3 * stage_n] (its 3x3 conv, tail_of = the index of THIS op) and the 1x1 conv behind it - carry `skip` while use_tail is set;
+    // only ever set together with use_stage. tail_mode: the head's own chain mode while the tail is off (net_set_chain_mode)
+    bool use_tail = false;
+    int tail_of = -1, tail_mode = 0;
     // the fused stem conv + pooling with the sibling pair that reads the pooled tensor (flag 512): THIS op is the stem conv, the next
     // op (the pair, `skip`) launches nothing; stem_y1 / stem_y2 are the pair's outputs and this op's own output edge is not written
     saber_hip_stem_pair* stem_pair = nullptr;
@@ -503,7 +510,8 @@ int fc_softmax_prepare(saber_hip_fc* fc);        // ... allocates the arrival co
 void net_set_chain_mode(saber_hip_net* net, int ia, int mode);      // api_net_optimize.hip
 int net_chain_mode(const saber_hip_net* net, int ia);      // api_net_optimize.hip
 // the stage headed by ops[i0] (NetOp::stage) on / off: on forces every block's 3x3-led chain form and makes ops[i0] launch them all
-void net_set_stage(saber_hip_net* net, int i0, bool on);   // api_net_optimize.hip
+void net_set_stage(saber_hip_net* net, int i0, bool on);   // api_net_optimize.hip (on: with its tail, where it has one; off: both)
+void net_set_tail(saber_hip_net* net, int i0, bool on);    // api_net_optimize.hip: the tail of the stage headed by ops[i0]; stays off while the stage is off
 // chain forms (api_chain.hip)
 ChainForm chain_form(const saber_hip_chain* ch, int code);      // the table: what `code` means for this chain, code 0 if nothing
 bool chain_form_valid(const saber_hip_chain* ch, int code);      // the form exists for this chain and its stream is packed
@@ -517,4 +525,5 @@ bool sep_form_valid(const saber_hip_sep* sp, int code);      // the form exists 
 void for_each_sep_form(const saber_hip_sep* sp, const std::function<void(int code)>& fn);      // its forms, in the autotuner's candidate order
 int sep_static_form(const saber_hip_sep* sp);      // the executor's static choice: a form code, or 0 = two launches
 void net_set_sep(saber_hip_net* net, int i, int code);      // api_net_optimize.hip: the site headed by ops[i] on (a valid form code) / off (0)
-int stage_run(saber_hip_chain_stage* st, const void* x, const void* res, void* const* y1, void* const* y2, hipStream_t s);   // api_chain.hip
+// api_chain.hip; y_tail: the tail's output - the tail then runs inside the launch (a stage created with one), null: the blocks only
+int stage_run(saber_hip_chain_stage* st, const void* x, const void* res, void* const* y1, void* const* y2, hipStream_t s, void* y_tail = nullptr);

@@ -18,7 +18,7 @@ int net_launch(saber_hip_net* net, const NetOp& o, hipStream_t s) {
                 y1[k] = T(ops[3 * k].chain3_y1);
                 y2[k] = T(ops[3 * k].chain3_y2);
             }
-            const int rc = stage_run(o.stage, T(o.in), T(o.chain3_res), y1, y2, s);
+            const int rc = stage_run(o.stage, T(o.in), T(o.chain3_res), y1, y2, s, o.use_tail ? T(ops[3 * o.stage_n].chain3_y1) : nullptr);
             if (rc == SABER_HIP_RUNTIME_ERROR) {      // an earlier launch of it timed out (conv_stage_coop.hip): block by block from now on
                 ++net->coop_fallbacks;
                 ++g_coop_fallbacks_total;
@@ -304,7 +304,7 @@ int saber_hip_net_compact_arena(saber_hip_net_t* net, const int* keep, int n_kee
     };
     for (int i = 0; i < nops; ++i) {
         const NetOp& o = net->ops[i];
-        if (o.stage) span(i, 3 * o.stage_n);
+        if (o.stage) span(i, 3 * o.stage_n + (o.stage->tail ? 2 : 0));      // (with the strided head it may run as its tail)
         if (o.chain3) span(i, 3);
         if (o.chain) span(i, 2);
         if (o.stem_pair) span(i, 2);
@@ -718,9 +718,12 @@ int saber_hip_net_status(saber_hip_net_t* net) {
     return fail(SABER_HIP_RUNTIME_ERROR, "a cooperative launch of the last pass did not complete (workgroups on different XCDs, or a hand-off "
                 "timed out: another kernel held the CUs); its outputs are not valid - those sites now launch block by block: run the pass again");
 }
-// testing aid: makes the next saber_hip_net_status report a failed cooperative launch at the first site that has an error word
+// testing aid: makes the next saber_hip_net_status report a failed cooperative launch at the first stage that is selected or, where none
+// is, at the first site that has an error word
 int saber_hip_net_inject_coop_error(saber_hip_net_t* net) {
     if (!net) return fail(SABER_HIP_INVALID_VALUE, "null argument");
+    for (NetOp& o : net->ops)
+        if (o.stage && o.use_stage && o.stage->h_err) { *(volatile unsigned*)o.stage->h_err = 1u; return SABER_HIP_OK; }
     for (NetOp& o : net->ops) {
         if (o.stage && o.stage->h_err) { *(volatile unsigned*)o.stage->h_err = 1u; return SABER_HIP_OK; }
         if (o.chain3 && o.chain3->h_coop_err) { *(volatile unsigned*)o.chain3->h_coop_err = 1u; return SABER_HIP_OK; }

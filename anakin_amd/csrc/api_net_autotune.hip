@@ -18,9 +18,13 @@ int saber_hip_net_get_choice(saber_hip_net_t* net, int index) {
     saber_hip_conv* c = net_op_conv(net, index);
     int choice = (c && !c->pool_fused && (c->algo <= ALGO_IGEMM_F32 || dw_ok(c) || group_ok(c))) ? saber_hip_conv2d_get_tile(c) : 0;
     if (c && net->ops[index].chain) choice |= (1 << 28) | ((net->ops[index].use_chain ? net->ops[index].chain->form.code : 0) << 24);
-    if (c && net->ops[index].chain3) choice |= (1 << 29) | ((net->ops[index].use_chain3 ? net->ops[index].chain3->form.code : 0) << 24);
+    // (a strided head that currently runs as its stage's tail reports the mode it has on its own)
+    const bool in_tail = c && net->ops[index].tail_of >= 0 && net->ops[net->ops[index].tail_of].use_tail;
+    const bool led = net->ops[index].chain3 && (in_tail ? net->ops[index].tail_mode == 2 : net->ops[index].use_chain3);
+    if (c && net->ops[index].chain3) choice |= (1 << 29) | ((led ? net->ops[index].chain3->form.code : 0) << 24);
     if (c && net->ops[index].sep) choice |= (3 << 28) | ((net->ops[index].use_sep ? net->ops[index].sep->form : 0) << 24);
     if (c && net->ops[index].stage && net->ops[index].use_stage) choice |= 1 << 30;      // this op launches its whole stage
+    if (c && net->ops[index].stage && net->ops[index].use_tail) choice |= (int)0x80000000u;      // ... and the strided head behind it as the launch's tail
     return choice;
 }
 int saber_hip_net_stage_blocks(const saber_hip_net_t* net, int index) {
@@ -34,6 +38,7 @@ int saber_hip_net_set_choice(saber_hip_net_t* net, int index, int choice) {
     if (net->ops[index].kind == OP_CONV_PAIR && index > 0 && net->ops[index - 1].stem_pair) return SABER_HIP_OK;      // no kernel of its own (flag 512)
     const int chain_bits = (choice >> 24) & 63;
     const bool stage_on = ((choice >> 30) & 1) && !net->shared_device;
+    const bool tail_on = stage_on && (((unsigned)choice >> 31) & 1u);      // (ignored on a stage without a tail)
     choice &= 0xffffff;
     // a selection tuned on a net that owned its device: placement-dependent variants are mapped to their plain forms (bf16-plane kernel: split-K off)
     if (net->shared_device && ((choice >> 16) & 0xff) == 11) choice &= ~(0xf << 12);
@@ -49,13 +54,22 @@ int saber_hip_net_set_choice(saber_hip_net_t* net, int index, int choice) {
     if (sep_bits && tn && !sep_form_valid(o.sep, tn)) return saber_hip_conv2d_sep_set_tile(o.sep, tn);      // (its status and message)
     int rc = choice ? saber_hip_conv2d_set_tile(c, choice) : SABER_HIP_OK;
     if (rc) return rc;
+    // a strided head inside its stage's launch (the stage head came first and decided that): its own mode is restored underneath
+    const bool in_tail = o.tail_of >= 0 && net->ops[o.tail_of].use_tail;
+    if (in_tail) net_set_tail(net, o.tail_of, false);
     o.name = std::string(o.kind == OP_FC || o.kind == OP_FC_Q ? "fc:" : "conv:") + c->algo_name;
     if ((o.kind == OP_FC || o.kind == OP_FC_Q) && o.out2 >= 0) o.name += fc_softmax_ok(o.fc, o.kind == OP_FC_Q) ? "+softmax" : " | softmax_f32";
     if (ch && tn) (void)saber_hip_conv2d_chain_set_tile(ch, tn);
-    if (ch && ch == o.chain3) net_set_chain_mode(net, index + 1, tn ? 2 : net_chain_mode(net, index + 1) == 2 ? 1 : net_chain_mode(net, index + 1));
+    // (a block inside a selected stage - its head came first - stays in the 3x3-led mode the stage launch stands for, whatever form the word
+    // recorded while the stage was off: its followers must not launch beside the stage)
+    const bool in_stage = o.chain3 && o.skip && !o.stage;
+    if (ch && ch == o.chain3) net_set_chain_mode(net, index + 1, (tn || in_stage) ? 2 : net_chain_mode(net, index + 1) == 2 ? 1 : net_chain_mode(net, index + 1));
     else if (ch) net_set_chain_mode(net, index, net_chain_mode(net, index) == 2 ? 2 : (tn ? 1 : 0));   // (also restores the names)
     if (o.stage) net_set_stage(net, index, stage_on);      // (a stage head comes before its blocks: set_choices runs in op order)
+    if (o.stage) net_set_tail(net, index, tail_on);
+    if (in_tail) net_set_tail(net, o.tail_of, true);
     if (o.skip) o.name = (o.chain3 && o.use_chain3) ? "conv:(in the stage launch)" : "conv:(in the chain launch)";
+    if (o.skip && index > 0 && net->ops[index - 1].tail_of >= 0 && net->ops[net->ops[index - 1].tail_of].use_tail) o.name = "conv:(in the stage launch)";
     if (o.skip && o.kind == OP_CONV_PAIR) o.name = (index > 0 && net->ops[index - 1].stem_pair) ? "conv:(in the stem launch)" : "conv:(in the chain launch)";
     if (o.stem_pair) o.name = stem_pair_name(o);
     if (o.sep) net_set_sep(net, index, sep_bits ? tn : (o.use_sep ? o.sep->form : 0));      // (a choice without the bits leaves the site as it is; the names follow)
@@ -238,11 +252,13 @@ int saber_hip_net_autotune(saber_hip_net_t* net, saber_hip_stream_t stream, int 
         rc = run_all();   // every written output holds the selected form's result
         if (rc) return rc;
     }
-    // stages: the blocks' tuned launches one after the other against the one persistent launch
+    // stages: the blocks' tuned launches one after the other against the one persistent launch; where the strided head behind the run can be
+    // the launch's tail, the head's ops are timed with them: blocks and head on their own | stage + head | stage with tail
     for (size_t i = 0; i < net->ops.size(); ++i) {
         NetOp& H0 = net->ops[i];
         if (!H0.stage || net->shared_device) continue;
-        const int first = (int)i, last = first + 3 * H0.stage_n - 1;
+        const bool has_tail = H0.stage->tail != nullptr;
+        const int first = (int)i, last = first + 3 * H0.stage_n - 1 + (has_tail ? 2 : 0);
         hipStream_t s = (hipStream_t)stream;
         auto run_all = [&]() -> int {
             int rc = 0;
@@ -260,8 +276,18 @@ int saber_hip_net_autotune(saber_hip_net_t* net, saber_hip_stream_t stream, int 
         if (rc) return rc;
         log_cand(H0.conv, "separate", sep);
         net_set_stage(net, first, true);
-        const bool ok = timed(&one) == SABER_HIP_OK && hipStreamSynchronize(s) == hipSuccess && !*(volatile unsigned*)H0.stage->h_err;
+        net_set_tail(net, first, false);
+        bool ok = timed(&one) == SABER_HIP_OK && hipStreamSynchronize(s) == hipSuccess && !*(volatile unsigned*)H0.stage->h_err;
         log_cand(H0.conv, H0.name.substr(5), ok ? one : -1.f);
+        if (ok && has_tail) {
+            float wt = 0.f;
+            net_set_tail(net, first, true);
+            const bool ok_t = timed(&wt) == SABER_HIP_OK && hipStreamSynchronize(s) == hipSuccess && !*(volatile unsigned*)H0.stage->h_err;
+            log_cand(H0.conv, H0.name.substr(5), ok_t ? wt : -1.f);
+            if (*(volatile unsigned*)H0.stage->h_err) ok = false;      // (a launch that did not complete: the site falls back as a whole)
+            else if (ok_t && wt < one) one = wt;
+            else net_set_tail(net, first, false);
+        }
         if (!ok || one >= sep) {
             *(volatile unsigned*)H0.stage->h_err = 0u;
             net_set_stage(net, first, false);

@@ -30,7 +30,8 @@ static void net_name_chain(NetOp& A, NetOp& B) {
 // mode of the ops around A = ops[ia] (a 1x1 conv with the fused eltwise): 0 separate launches, 1 A + B chained (A.chain),
 // 2 the 3x3 conv ops[ia - 1] leads the launch (its chain3; with or without B)
 static std::string stage_name(const NetOp& H0) {
-    return "conv:stage_c" + std::to_string(H0.stage->c1) + "_" + std::to_string(H0.stage_n) + "x[conv3x3+chain1x1]_2x16" + (H0.stage->c1 == 256 ? "_coop4" : "");
+    return "conv:stage_c" + std::to_string(H0.stage->c1) + "_" + std::to_string(H0.stage_n) + "x[conv3x3+chain1x1]_2x16" + (H0.stage->c1 == 256 ? "_coop4" : "") +
+           (H0.use_tail ? "+[conv3x3/2+conv1x1]" : "");
 }
 void net_set_chain_mode(saber_hip_net* net, int ia, int mode) {
     NetOp& A = net->ops[ia];
@@ -60,9 +61,26 @@ void net_set_chain_mode(saber_hip_net* net, int ia, int mode) {
 std::string stem_pair_name(const NetOp& o) {
     return std::string("conv:") + o.conv->algo_name + "+pair1x1_" + std::to_string(o.stem_pair->a->d.k) + "+" + std::to_string(o.stem_pair->b->d.k);
 }
+// The strided head behind the stage headed by ops[i0] inside / outside the stage launch. Inside: its two ops launch nothing (like a
+// block's they are in chain mode 2: the 3x3 conv's edge is not written), the stage head's launch writes the 1x1 conv's output.
+void net_set_tail(saber_hip_net* net, int i0, bool on) {
+    NetOp& H0 = net->ops[i0];
+    if (!H0.stage || !H0.stage->tail) return;
+    const int it = i0 + 3 * H0.stage_n;
+    NetOp& Ht = net->ops[it];
+    on = on && H0.use_stage;
+    if (on == H0.use_tail) return;
+    if (on) Ht.tail_mode = net_chain_mode(net, it + 1);
+    H0.use_tail = on;
+    Ht.skip = on;
+    net_set_chain_mode(net, it + 1, on ? 2 : Ht.tail_mode);
+    if (on) net->ops[it + 1].name = "conv:(in the stage launch)";
+    if (H0.use_stage) H0.name = stage_name(H0);
+}
 void net_set_stage(saber_hip_net* net, int i0, bool on) {
     NetOp& H0 = net->ops[i0];
     if (!H0.stage) return;
+    if (!on) net_set_tail(net, i0, false);
     for (int k = 0; k < H0.stage_n; ++k) {
         if (on || H0.use_stage) net_set_chain_mode(net, i0 + 3 * k + 1, 2);
         NetOp& Hk = net->ops[i0 + 3 * k];
@@ -72,6 +90,7 @@ void net_set_stage(saber_hip_net* net, int i0, bool on) {
         }
     }
     H0.use_stage = on;
+    if (on) net_set_tail(net, i0, true);
     if (on) H0.name = stage_name(H0);
 }
 int net_chain_mode(const saber_hip_net* net, int ia) {
@@ -476,12 +495,23 @@ int saber_hip_net_optimize(saber_hip_net_t* net, int flags) {
             }
             if (run.size() >= 2) {
                 saber_hip_chain_stage* st = nullptr;
-                if (saber_hip_conv2d_stage_create(run.data(), (int)run.size(), &st) == SABER_HIP_OK) {
+                // the strided head behind a C = 256 run (res4f's conv3x3 / stride 2 + conv1x1 + eltwise) reads the last block's two outputs:
+                // the launch's tail (conv_stage_coop.hip); where the stage does not take it, the stage without
+                const size_t pl = i + 3 * (run.size() - 1), jt = pl + 3;
+                saber_hip_chain* tail = nullptr;
+                if (jt + 1 < ops.size() && run[0]->c1 == 256 && ops[jt].chain3 && !ops[jt].chain3->b && !ops[jt].chain3->b2 && !ops[jt].stage &&
+                    ops[jt].chain3->c1 == 256 && ops[jt].chain3->c3->d.stride_h == 2 && ops[jt].in == ops[pl].chain3_y2 &&
+                    ops[jt].chain3_res == ops[pl].chain3_y1 && ops[jt].chain3_y1 >= 0)
+                    tail = ops[jt].chain3;
+                if (tail && saber_hip_conv2d_stage_create_tail(run.data(), (int)run.size(), tail, &st) != SABER_HIP_OK) tail = nullptr;
+                if (tail || saber_hip_conv2d_stage_create(run.data(), (int)run.size(), &st) == SABER_HIP_OK) {
                     net->owned_stages.push_back(st);
                     ops[i].stage = st;
                     ops[i].stage_n = (int)run.size();
+                    if (tail) ops[jt].tail_of = (int)i;
                     int before = 0;
                     for (size_t k = 0; k < run.size(); ++k) before += 3 - (ops[i + 3 * k].skip + ops[i + 3 * k + 1].skip + ops[i + 3 * k + 2].skip);
+                    if (tail) before += 2 - (ops[jt].skip + ops[jt + 1].skip);
                     // default until the autotuner has timed both forms: the res4 stage (C = 256) on from batch 4 (an image per XCD: fewer
                     // images leave XCDs idle); the res3 stage (C = 128) off - measured slower than its chain launches
                     const bool on = run[0]->a->d.n >= 4 && run[0]->c1 == 256;

@@ -31,10 +31,11 @@
 
 namespace saber_mi355x {
 
-template <int MAXB>
+template <int MAXB, bool TAIL>
 __global__ __launch_bounds__(512) void conv_stage4_c256_kernel(const Stage4KArgs<MAXB> ka) {
     constexpr int C1 = 256, K1 = 1024, K2 = 256, NW = 8;
     constexpr int F0 = 18, F1 = 8, F2 = 8;                   // 1 KB weight fragments per wave and phase
+    constexpr int FB = F0 + F1 + F2, FT = F0 + F1;           // ... per wave of a block / of the tail (no second 1x1 conv)
     constexpr int K0Q = C1 / 4, K1Q = K1 / 4, K2Q = K2 / 4;  // this workgroup's output channels per phase: 64, 256, 64
     constexpr int CH1 = C1 / 16, PCH = CH1 + 1, HW = 18, HP = 4 * HW;
     constexpr int HCH = (HP * PCH + 63) / 64 * 64;
@@ -137,9 +138,10 @@ __global__ __launch_bounds__(512) void conv_stage4_c256_kernel(const Stage4KArgs
         for (int i = wave; i < P1C / 64; i += NW) lds_dma16((const v4i*)B.prm1 + q * P1C + i * 64 + lane, prm1 + i * 64);
         if (wave < P2C / 64) lds_dma16((const v4i*)B.prm2 + q * (K2Q / 4 * 3) + wave * 64 + lane, prm2 + wave * 64);
     };
-    auto stream_of = [&](const StageBlk& B) -> const v4i* {   // this (quarter, wave)'s fragments of block B, lane's 16 bytes
-        return (const v4i*)B.wstream + (size_t)(q * NW + wave) * ((F0 + F1 + F2) * 64) + lane;
+    auto stream_of = [&](const StageBlk& B, int nf) -> const v4i* {   // this (quarter, wave)'s nf fragments of block B, lane's 16 bytes
+        return (const v4i*)B.wstream + (size_t)(q * NW + wave) * (nf * 64) + lane;
     };
+    const int nall = ka.nblk + (TAIL ? 1 : 0);                // blocks + the tail: what the last ordinary block prefetches and waits for
 
     // ---- entry: the first block's halo, shortcut tile and constants by DMA; its first 20 weight fragments ------------------------
     dma_halo(ka.x, false);
@@ -148,7 +150,7 @@ __global__ __launch_bounds__(512) void conv_stage4_c256_kernel(const Stage4KArgs
     asm volatile("" ::: "memory");
     v4i fr[F0 + 2];
     {
-        const v4i* wsb = stream_of(ka.blk[0]);
+        const v4i* wsb = stream_of(ka.blk[0], FB);
 #pragma unroll
         for (int r = 0; r < F0 + 2; ++r) {
             fr[r] = wsb[r * 64];
@@ -212,7 +214,7 @@ __global__ __launch_bounds__(512) void conv_stage4_c256_kernel(const Stage4KArgs
         // the rest of this block's stream, requested under the wait for the partners: 6 fragments of the first 1x1 conv, 8 of the second
         v4i fs[F1 - 2 + F2];
         {
-            const v4i* wsb = stream_of(B);
+            const v4i* wsb = stream_of(B, FB);
 #pragma unroll
             for (int r = 0; r < F1 - 2 + F2; ++r) {
                 fs[r] = wsb[(F0 + 2 + r) * 64];
@@ -277,9 +279,9 @@ __global__ __launch_bounds__(512) void conv_stage4_c256_kernel(const Stage4KArgs
         if (okt) *(v4i*)((char*)ka.y1[k] + (size_t)pt * K1 + q * K1Q + tc * 16) = tile[tid];      // this quarter's 32 x 256 tile -> y1, coalesced
         coop_arrive(ctr + 16);
         SABER_TL(4);
-        const StageBlk Bn = ka.blk[k + 1 < ka.nblk ? k + 1 : k];      // the next block's constants, one phase ahead of their use
-        if (k + 1 < ka.nblk) {         // the next block's first 20 fragments: one block ahead, behind the arrival
-            const v4i* wsb = stream_of(Bn);
+        const StageBlk Bn = ka.blk[k + 1 < nall ? k + 1 : k];         // the next block's (or the tail's) constants, one phase ahead of their use
+        if (k + 1 < nall) {            // the next block's first 20 fragments: one block ahead, behind the arrival
+            const v4i* wsb = stream_of(Bn, TAIL && k + 1 == ka.nblk ? FT : FB);
 #pragma unroll
             for (int r = 0; r < F0 + 2; ++r) {
                 fr[r] = wsb[r * 64];
@@ -339,7 +341,7 @@ __global__ __launch_bounds__(512) void conv_stage4_c256_kernel(const Stage4KArgs
             }
         }
         SABER_TL(6);
-        if (k + 1 < ka.nblk) {
+        if (k + 1 < nall) {
             // ============= between two blocks: the next halo = the y2 rows of this tile and of the tiles above and below it ==============
             // One counter per EDGE between two tile rows of the image (tiles_x = 1): every workgroup of the two tiles at an edge arrives there
             // when its y2 stores are in the L2 (8 arrivals; 4 at the image's top and bottom edge, where one tile takes part), and its
@@ -367,6 +369,94 @@ __global__ __launch_bounds__(512) void conv_stage4_c256_kernel(const Stage4KArgs
             B = Bn;
             SABER_TL(7);
         }
+    }
+    if constexpr (TAIL) {
+        // ================= tail: the strided head behind the last block (conv 3x3 / stride 2 / pad 1, C -> C; conv 1x1 C -> 4C + eltwise with
+        // the shortcut sub-sampled by 2) on what the last block left on this CU. Tile row ty makes output row ty: its input rows 2 ty - 1 ..
+        // 2 ty + 1 and columns 2 ox - 1 .. 2 ox + 1 are rows 0..2 of the halo the edge barrier above has just brought in (W <= 16), the
+        // shortcut pixel (2 ty, 2 ox) is row 0 of the last block's y1 tile, still in LDS. One 16-pixel fragment (ox = lane & 15, <= 8 valid),
+        // so one accumulator per weight fragment; the same 18 + 8 fragments per wave, the same hand-off on the tile's first counter.
+        const v4i z = {0, 0, 0, 0};
+        int ln = lane;
+        asm volatile("" : "+v"(ln));                         // (the tail's index arithmetic starts HERE: hoisted over the blocks it cost them registers)
+        const int frow = ln & 15, fq = ln >> 4;
+        const int OW = (W + 1) >> 1;
+        const int ox = frow < OW ? frow : OW - 1;
+        SABER_TL(8);
+        {
+            const int xm0 = B.in0_u8 ? (int)0x80808080u : 0;
+            const int c0 = nt * 16 + fq * 4;                 // within this quarter
+            const v4i* pp = prm0 + (c0 / 4) * 3;
+            v4i acc0 = kh ? z : pp[2];
+            const v4i* hb = halo + 2 * ox * PCH + fq + kh * 8;
+#pragma unroll
+            for (int s = 0; s < F0; ++s) {
+                const int kl = s % 2, tap = s / 2;
+                const int dy = tap / 3, dx = tap % 3;
+                v4i b0 = hb[(dy * HW + dx) * PCH + kl * 4];
+                b0.x ^= xm0; b0.y ^= xm0; b0.z ^= xm0; b0.w ^= xm0;
+                acc0 = mma_step(fr[s], b0, acc0);
+            }
+            if (kh) red[nt * 2 * 64 + ln] = acc0;
+            asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+            __builtin_amdgcn_s_barrier();
+            if (!kh) {
+                const v4i r0 = red[nt * 2 * 64 + ln];
+                acc0.x += r0.x; acc0.y += r0.y; acc0.z += r0.z; acc0.w += r0.w;
+                const float lo0 = B.relu0 ? 0.f : -3.0e38f;
+                const float off0 = B.in_u8 ? 0.f : 128.f;
+                const unsigned xo0 = B.in_u8 ? 0u : 0x80808080u;
+                const unsigned o0 = chain_out_pack(acc0, z, __builtin_bit_cast(v4f, pp[1]), __builtin_bit_cast(v4f, pp[0]), lo0, off0, xo0);
+                *(unsigned*)((char*)ka.xch + ((size_t)t * 32 + frow) * C1 + q * K0Q + c0) = o0;      // for the partners (through the L2)
+                *(unsigned*)((char*)mid_own + frow * (MPC * 16) + c0) = o0;                          // for this workgroup (LDS)
+            }
+        }
+        coop_arrive(ctr);
+        v4i ft[F1 - 2];                                      // the other 6 fragments of the 1x1 conv, requested under the wait for the partners
+        {
+            const v4i* wsb = stream_of(B, FT);
+#pragma unroll
+            for (int r = 0; r < F1 - 2; ++r) {
+                ft[r] = wsb[(F0 + 2 + r) * 64];
+                asm volatile("" ::: "memory");
+            }
+        }
+        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+        __builtin_amdgcn_s_barrier();                        // mid_own is complete
+        SABER_TL(9);
+        {
+            const int xmask = B.in_u8 ? (int)0x80808080u : 0;
+            const int cg = wave * 32 + fq * 8;               // within this quarter: 8 consecutive channels of output pixel (ty, frow)
+            const v4i* pp = prm1 + (cg / 4) * 3;
+            v4i a0 = pp[2], a1 = pp[5];
+            v4i bo = mid_own[frow * MPC + fq];
+            bo.x ^= xmask; bo.y ^= xmask; bo.z ^= xmask; bo.w ^= xmask;
+            a0 = mma_step(fr[F0], bo, a0);
+            a1 = mma_step(fr[F0 + 1], bo, a1);
+            coop_wait<31ull>(ctr, ka.err);                   // the partners' quarters of the 3x3 row are in the L2
+            SABER_TL(10);
+            const L2Reader xch_l2(ka.xch);
+            v4i bp[3];
+#pragma unroll
+            for (int i = 0; i < 3; ++i)
+                bp[i] = xch_l2.load16<SABER_COOP_AUX>((unsigned)(((size_t)t * 32 + frow) * C1 + ((q + 1 + i) & 3) * 64 + fq * 16));
+#pragma unroll
+            for (int i = 0; i < 3; ++i) {
+                v4i bv = bp[i];
+                bv.x ^= xmask; bv.y ^= xmask; bv.z ^= xmask; bv.w ^= xmask;
+                a0 = mma_step(ft[i * 2], bv, a0);
+                a1 = mma_step(ft[i * 2 + 1], bv, a1);
+            }
+            const float lo_s8 = B.relu1 ? 0.f : -128.f;
+            const float res_lo = B.res_relu ? 0.f : -3.0e38f;
+            const c2i rs = *(const c2i*)((const char*)tile + (2 * ox * CPRW + ((cg / 16) ^ (2 * ox))) * 16 + (fq & 1) * 8);      // shortcut pixel (2 ty, 2 ox)
+            c2i o;
+            o.x = (int)chain_elt_pack(a0, z, __builtin_bit_cast(v4f, pp[1]), __builtin_bit_cast(v4f, pp[0]), (unsigned)rs.x, lo_s8, res_lo, B);
+            o.y = (int)chain_elt_pack(a1, z, __builtin_bit_cast(v4f, pp[4]), __builtin_bit_cast(v4f, pp[3]), (unsigned)rs.y, lo_s8, res_lo, B);
+            // the tail's output [N][tile rows][OW][1024]
+            if (frow < OW) *(c2i*)((char*)ka.y1[ka.nblk] + ((size_t)(n * ka.tiles_per_img + ty) * OW + frow) * K1 + q * K1Q + cg) = o;
+        }
+        SABER_TL(11);
     }
     if (tid == 0 && ka.err) {      // the quarters of this tile - and, with an image per XCD, its image's first tile - ran on this XCD?
         const L2Reader xr(ka.xcc);
@@ -641,16 +731,19 @@ static hipError_t launch_stage1(const Stage4KArgs<MAXB>& ka, hipStream_t s) {
 hipError_t launch_conv_stage1_c128(const Stage4KArgs<STAGE4_SHORT>& a, hipStream_t s) { return launch_stage1(a, s); }
 hipError_t launch_conv_stage1_c128(const Stage4KArgs<STAGE4_LONG>& a, hipStream_t s) { return launch_stage1(a, s); }
 template <int MAXB>
-static hipError_t launch_stage4(const Stage4KArgs<MAXB>& ka, hipStream_t s) {
+static hipError_t launch_stage4(const Stage4KArgs<MAXB>& ka, bool tail, hipStream_t s) {
+    // tail: blk[nblk] holds the strided head's constants, y1[nblk] is its output (two blocks at least: an image per XCD, W <= 16)
+    if (tail && (ka.nblk < 2 || ka.nblk + 1 > MAXB || !ka.y1[ka.nblk])) return hipErrorInvalidValue;
     if (ka.nblk <= 0 || ka.nblk > MAXB || ka.N <= 0 || !ka.blk || !ka.grp_ctr || !ka.xch || !ka.xcc ||
         (ka.nblk > 1 && (!ka.per_image || !ka.img_ctr || ka.tiles_x != 1)))
         return hipErrorInvalidValue;
     const int tiles = ka.N * ka.tiles_per_img;
     const dim3 grid(ka.per_image ? (ka.N + 7) / 8 * ka.tiles_per_img * 4 * 8 : (tiles + 7) / 8 * 32), block(512);
-    hipLaunchKernelGGL(conv_stage4_c256_kernel<MAXB>, grid, block, 0, s, ka);
+    if (tail) hipLaunchKernelGGL((conv_stage4_c256_kernel<MAXB, true>), grid, block, 0, s, ka);
+    else hipLaunchKernelGGL((conv_stage4_c256_kernel<MAXB, false>), grid, block, 0, s, ka);
     return hipGetLastError();
 }
-hipError_t launch_conv_stage4(const Stage4KArgs<STAGE4_SHORT>& a, hipStream_t s) { return launch_stage4(a, s); }
-hipError_t launch_conv_stage4(const Stage4KArgs<STAGE4_LONG>& a, hipStream_t s) { return launch_stage4(a, s); }
+hipError_t launch_conv_stage4(const Stage4KArgs<STAGE4_SHORT>& a, bool tail, hipStream_t s) { return launch_stage4(a, tail, s); }
+hipError_t launch_conv_stage4(const Stage4KArgs<STAGE4_LONG>& a, bool tail, hipStream_t s) { return launch_stage4(a, tail, s); }
 
 }  // namespace saber_mi355x

@@ -201,8 +201,11 @@ struct Stage4KArgs {
     void* y2[MAXB];                    // per block [M][256] s8 / u8: the second 1x1 conv's output = the next block's 3x3 input
 };
 constexpr int STAGE4_SHORT = 8, STAGE4_LONG = 24;
-hipError_t launch_conv_stage4(const Stage4KArgs<STAGE4_SHORT>& a, hipStream_t s);
-hipError_t launch_conv_stage4(const Stage4KArgs<STAGE4_LONG>& a, hipStream_t s);
+// tail: behind the nblk blocks the strided head that follows the stage in ResNet (conv 3x3 / stride 2 -> conv 1x1 + eltwise, shortcut = the
+// last block's y1 sub-sampled by 2) runs in the same launch: blk[nblk] = its constants (wstream: the 18 + 8 fragments of the first two convs
+// per (quarter, wave); prm2 unused but readable), y1[nblk] = its output [N][ceil(H/2)][ceil(W/2)][1024] s8. Needs nblk >= 2, nblk + 1 <= MAXB.
+hipError_t launch_conv_stage4(const Stage4KArgs<STAGE4_SHORT>& a, bool tail, hipStream_t s);
+hipError_t launch_conv_stage4(const Stage4KArgs<STAGE4_LONG>& a, bool tail, hipStream_t s);
 // the res3 stage (C = 128): one workgroup per tile, an image per XCD, nblk >= 2; grp_ctr / xch unused; tiles_x in {1, 2, 4}
 hipError_t launch_conv_stage1_c128(const Stage4KArgs<STAGE4_SHORT>& a, hipStream_t s);
 hipError_t launch_conv_stage1_c128(const Stage4KArgs<STAGE4_LONG>& a, hipStream_t s);

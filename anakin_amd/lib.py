@@ -29,7 +29,7 @@ SYMBOLS = [
     "saber_hip_conv2d_chain_create", "saber_hip_conv2d_chain_create3", "saber_hip_conv2d_chain_create3_pair", "saber_hip_conv2d_chain_destroy", "saber_hip_conv2d_chain_run",
     "saber_hip_conv2d_chain_run3",
     "saber_hip_conv2d_chain_set_tile", "saber_hip_conv2d_chain_get_tile",
-    "saber_hip_conv2d_stage_create", "saber_hip_conv2d_stage_destroy", "saber_hip_conv2d_stage_run",
+    "saber_hip_conv2d_stage_create", "saber_hip_conv2d_stage_destroy", "saber_hip_conv2d_stage_run", "saber_hip_conv2d_stage_create_tail", "saber_hip_conv2d_stage_run_tail",
     "saber_hip_conv2d_stem_pair_create", "saber_hip_conv2d_stem_pair_destroy", "saber_hip_conv2d_stem_pair_run",
     "saber_hip_conv2d_sep_create", "saber_hip_conv2d_sep_run", "saber_hip_conv2d_sep_set_tile", "saber_hip_conv2d_sep_get_tile",
     "saber_hip_conv2d_sep_algo", "saber_hip_conv2d_sep_destroy",
@@ -134,6 +134,8 @@ def load():
     lib.saber_hip_conv2d_stage_destroy.argtypes = [P]
     lib.saber_hip_conv2d_stage_destroy.restype = None
     lib.saber_hip_conv2d_stage_run.argtypes = [P, P, P, C.POINTER(P), C.POINTER(P), P]
+    lib.saber_hip_conv2d_stage_create_tail.argtypes = [C.POINTER(P), I, P, C.POINTER(P)]
+    lib.saber_hip_conv2d_stage_run_tail.argtypes = [P, P, P, C.POINTER(P), C.POINTER(P), P, P]
     lib.saber_hip_conv2d_stem_pair_create.argtypes = [P, P, P, C.POINTER(P)]
     lib.saber_hip_conv2d_stem_pair_destroy.argtypes = [P]
     lib.saber_hip_conv2d_stem_pair_destroy.restype = None

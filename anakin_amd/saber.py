@@ -336,19 +336,28 @@ class SaberConvChain:
 class SaberChainStage:
     """A run of 3x3-led C = 256 chains (SaberConvChain with conv3x3 and b) as ONE persistent launch (saber_hip_conv2d_stage_create):
     chain i + 1 reads chain i's two outputs. dispatch(x, res, y1s, y2s): chain 0's inputs, every chain's two output tensors. The
-    outputs hold the bits of dispatching the chains (= the operators, net.cpp:417-509) one after the other."""
+    outputs hold the bits of dispatching the chains (= the operators, net.cpp:417-509) one after the other.
+    tail: the strided head behind the run (SaberConvChain(a, None, conv3x3) with a stride-2 conv3x3 and a shortcut sub-sampled by 2;
+    saber_hip_conv2d_stage_create_tail); dispatch(..., y_tail) then runs it inside the launch, dispatch without y_tail the blocks only."""
 
-    def __init__(self, chains):
+    def __init__(self, chains, tail=None):
         self.chains = list(chains)                   # keep them alive: the stage borrows their weights
+        self.tail = tail
         arr = (C.c_void_p * len(chains))(*[c.h for c in chains])
         self.h = C.c_void_p()
-        L.check(L.load().saber_hip_conv2d_stage_create(arr, len(chains), C.byref(self.h)))
+        if tail is None:
+            L.check(L.load().saber_hip_conv2d_stage_create(arr, len(chains), C.byref(self.h)))
+        else:
+            L.check(L.load().saber_hip_conv2d_stage_create_tail(arr, len(chains), tail.h, C.byref(self.h)))
 
-    def dispatch(self, x, res, y1s, y2s):
+    def dispatch(self, x, res, y1s, y2s, y_tail=None):
         n = len(self.chains)
         a = (C.c_void_p * n)(*[t.data_ptr() for t in y1s])
         b = (C.c_void_p * n)(*[t.data_ptr() for t in y2s])
-        L.check(L.load().saber_hip_conv2d_stage_run(self.h, _p(x), _p(res), a, b, _stream()))
+        if y_tail is None:
+            L.check(L.load().saber_hip_conv2d_stage_run(self.h, _p(x), _p(res), a, b, _stream()))
+        else:
+            L.check(L.load().saber_hip_conv2d_stage_run_tail(self.h, _p(x), _p(res), a, b, _p(y_tail), _stream()))
 
     def __del__(self):
         try:
@@ -853,6 +862,22 @@ class Net:
         ch = self.choices()
         for i, _, _ in self.stages():
             ch[i] = (ch[i] | (1 << 30)) if on else (ch[i] & ~(1 << 30))
+        self.set_choices(ch)
+
+    def tails(self):
+        """[(op index of the stage head, blocks)] of the stages that currently run the strided head behind them as the launch's tail
+        (bit 31 of the head's choice word; conv_stage_coop.hip)"""
+        ch = self.choices()
+        return [(i, n) for i, n, on in self.stages() if on and (ch[i] >> 31) & 1]
+
+    def select_tails(self, on):
+        """the tail of every selected stage that has one on / off (what saber_hip_net_autotune decides by timing); a stage without a
+        tail ignores the bit"""
+        ch = self.choices()
+        for i, _, sel in self.stages():
+            if sel:
+                v = ((ch[i] | (1 << 31)) if on else (ch[i] & ~(1 << 31))) & 0xffffffff
+                ch[i] = v - (1 << 32) if v >> 31 else v
         self.set_choices(ch)
 
     def time_ops(self, iters=20):

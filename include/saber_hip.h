@@ -239,6 +239,14 @@ int saber_hip_conv2d_stage_create(saber_hip_chain_t* const* chains, int n, saber
 void saber_hip_conv2d_stage_destroy(saber_hip_chain_stage_t* stage);
 int saber_hip_conv2d_stage_run(saber_hip_chain_stage_t* stage, const void* x, const void* res, void* const* y1, void* const* y2,
                                saber_hip_stream_t stream);
+/* ... with a TAIL: the strided head that follows the run in ResNet (res4f's branch2b / branch2c) = a chain of
+ * saber_hip_conv2d_chain_create3(conv3x3 / stride 2, a with res_stride == 2, NULL) at C = 256 whose 3x3 conv reads the last block's y2 and
+ * whose shortcut is the last block's y1. _run_tail runs it inside the same launch on what the last block left on the CU and writes
+ * y_tail [N][ceil(H/2)][ceil(W/2)][1024] with the bits of saber_hip_conv2d_chain_run3 on that chain; saber_hip_conv2d_stage_run on such a
+ * stage runs the blocks only. At least two blocks; anything else about the tail is refused with SABER_HIP_INVALID_VALUE. */
+int saber_hip_conv2d_stage_create_tail(saber_hip_chain_t* const* chains, int n, saber_hip_chain_t* tail, saber_hip_chain_stage_t** out);
+int saber_hip_conv2d_stage_run_tail(saber_hip_chain_stage_t* stage, const void* x, const void* res, void* const* y1, void* const* y2,
+                                    void* y_tail, saber_hip_stream_t stream);
 
 /* The ResNet stem with its first two consumers in ONE launch: `stem` (an INT8 conv with saber_hip_conv2d_set_pooling's fused 3x3 /
  * stride-2 max pooling, 64 output channels: SaberConv2DPooling<AK_INT8>, saber_conv_pooling.cpp:60-160) followed, on the workgroup's
