@@ -549,48 +549,60 @@ def gemm(trans_a, trans_b, m, n, k, alpha, a, b, beta, c):
     return c
 
 
-def quantize_nchw_to_nhwc(x, scale, out_dtype, c_pad=None):
+def _out(out, shape, dtype):
+    """The result tensor of a streaming wrapper: a new one, or the caller's `out=` (`out_q=`) written in place. `out` must be contiguous,
+    of the result's dtype and element count (any shape of that count: the kernels address it flat); it comes back viewed in the result's
+    shape, over the same memory. Anything else raises SaberHipError before a launch."""
+    if out is None:
+        return torch.empty(shape, dtype=dtype, device="cuda")
+    if out.dtype != dtype or out.numel() != int(np.prod(shape)) or not out.is_contiguous():
+        raise L.SaberHipError("out= must be a contiguous %s tensor of %d elements, got %s %s%s" % (
+            dtype, int(np.prod(shape)), out.dtype, tuple(out.shape), "" if out.is_contiguous() else " (not contiguous)"))
+    return out.view(tuple(shape))
+
+
+def quantize_nchw_to_nhwc(x, scale, out_dtype, c_pad=None, out=None):
     n, c, h, w = x.shape
     c_pad = c if c_pad is None else c_pad
-    y = torch.empty((n, h, w, c_pad), dtype=_TORCH_DT[out_dtype], device="cuda")
+    y = _out(out, (n, h, w, c_pad), _TORCH_DT[out_dtype])
     L.check(L.load().saber_hip_quantize_nchw_to_nhwc(n, c, h, w, c_pad, out_dtype, float(scale), _p(x), _p(y),
                                                      _stream()))
     return y
 
 
-def dequantize_nhwc_to_nchw(x, scale):
+def dequantize_nhwc_to_nchw(x, scale, out=None):
     n, h, w, c = x.shape
-    y = torch.empty((n, c, h, w), dtype=torch.float32, device="cuda")
+    y = _out(out, (n, c, h, w), torch.float32)
     L.check(L.load().saber_hip_dequantize_nhwc_to_nchw(n, c, h, w, dtype_code(x), float(scale), _p(x), _p(y),
                                                        _stream()))
     return y
 
 
-def transpose_nchw_to_nhwc(x, c_pad=None):
+def transpose_nchw_to_nhwc(x, c_pad=None, out=None):
     n, c, h, w = x.shape
     c_pad = c if c_pad is None else c_pad
-    y = torch.empty((n, h, w, c_pad), dtype=torch.float32, device="cuda")
+    y = _out(out, (n, h, w, c_pad), torch.float32)
     L.check(L.load().saber_hip_transpose_nchw_to_nhwc_f32(n, c, h, w, c_pad, _p(x), _p(y), _stream()))
     return y
 
 
-def transpose_nhwc_to_nchw(x, c=None):
+def transpose_nhwc_to_nchw(x, c=None, out=None):
     n, h, w, c_pad = x.shape
     c = c_pad if c is None else c
-    y = torch.empty((n, c, h, w), dtype=torch.float32, device="cuda")
+    y = _out(out, (n, c, h, w), torch.float32)
     L.check(L.load().saber_hip_transpose_nhwc_to_nchw_f32(n, c, h, w, c_pad, _p(x), _p(y), _stream()))
     return y
 
 
-def quantize_flat_s8(x, scale):
-    y = torch.empty(x.shape, dtype=torch.int8, device="cuda")
+def quantize_flat_s8(x, scale, out=None):
+    y = _out(out, x.shape, torch.int8)
     L.check(L.load().saber_hip_quantize_flat_s8(x.numel(), float(scale), _p(x), _p(y), _stream()))
     return y
 
 
-def eltwise_sum(a, b, coeff=(1.0, 1.0), relu=True, scale_a=1.0, scale_b=1.0):
+def eltwise_sum(a, b, coeff=(1.0, 1.0), relu=True, scale_a=1.0, scale_b=1.0, out=None):
     """Eltwise<MI355X, AK_INT8|AK_FLOAT> sum (EltwiseParam :1077-1140)."""
-    y = torch.empty_like(a)
+    y = _out(out, a.shape, a.dtype)
     if a.dtype == torch.int8:
         L.check(L.load().saber_hip_eltwise_sum_i8(a.numel(), _p(a), _p(b), float(scale_a), float(scale_b),
                                                   float(coeff[0]), float(coeff[1]), int(relu), _p(y), _stream()))
@@ -612,7 +624,7 @@ def pool_out_hw(h, w, pad, window, stride, floor_mode=False):
     return (pool_out_dim(h, pad[0], window[0], stride[0], floor_mode, ap), pool_out_dim(w, pad[1], window[1], stride[1], floor_mode, ap))
 
 
-def pooling_i8(x, window, stride, pad, pool_type, out_dtype=None, global_pooling=False, floor_mode=False):
+def pooling_i8(x, window, stride, pad, pool_type, out_dtype=None, global_pooling=False, floor_mode=False, out=None):
     """Pooling<MI355X, AK_INT8> on NHWC s8/u8 (PoolingParam :2087)."""
     n, h, w, c = x.shape
     if global_pooling:
@@ -620,13 +632,13 @@ def pooling_i8(x, window, stride, pad, pool_type, out_dtype=None, global_pooling
     else:
         oh, ow = pool_out_hw(h, w, pad, window, stride, floor_mode)
     od = dtype_code(x) if out_dtype is None else out_dtype
-    y = torch.empty((n, oh, ow, c), dtype=_TORCH_DT[od], device="cuda")
+    y = _out(out, (n, oh, ow, c), _TORCH_DT[od])
     L.check(L.load().saber_hip_pool2d_i8_nhwc(n, h, w, c, oh, ow, window[0], window[1], stride[0], stride[1],
                                               pad[0], pad[1], pool_type, dtype_code(x), od, _p(x), _p(y), _stream()))
     return y
 
 
-def pooling_f32(x, window, stride, pad, pool_type, layout=L.NCHW, global_pooling=False, floor_mode=False):
+def pooling_f32(x, window, stride, pad, pool_type, layout=L.NCHW, global_pooling=False, floor_mode=False, out=None):
     if layout == L.NCHW:
         n, c, h, w = x.shape
     else:
@@ -636,14 +648,14 @@ def pooling_f32(x, window, stride, pad, pool_type, layout=L.NCHW, global_pooling
     else:
         oh, ow = pool_out_hw(h, w, pad, window, stride, floor_mode)
     shape = (n, c, oh, ow) if layout == L.NCHW else (n, oh, ow, c)
-    y = torch.empty(shape, dtype=torch.float32, device="cuda")
+    y = _out(out, shape, torch.float32)
     L.check(L.load().saber_hip_pool2d_f32(n, h, w, c, oh, ow, window[0], window[1], stride[0], stride[1], pad[0],
                                           pad[1], pool_type, layout, _p(x), _p(y), _stream()))
     return y
 
 
 def pooling_f32_from_i8(x, scale, window, stride, pad, pool_type, global_pooling=False, floor_mode=False,
-                        q_scale=None):
+                        q_scale=None, out=None, out_q=None):
     """Pooling<MI355X, AK_FLOAT> fed an s8/u8 NHWC tensor: dequantise on entry, pool, f32 NCHW out.
     q_scale: also return the s8 quantisation of the result (the next INT8 op's quantise-on-entry, fused)."""
     n, h, w, c = x.shape
@@ -651,9 +663,9 @@ def pooling_f32_from_i8(x, scale, window, stride, pad, pool_type, global_pooling
         window, stride, pad, oh, ow = (h, w), (h, w), (0, 0), 1, 1
     else:
         oh, ow = pool_out_hw(h, w, pad, window, stride, floor_mode)
-    y = torch.empty((n, c, oh, ow), dtype=torch.float32, device="cuda")
+    y = _out(out, (n, c, oh, ow), torch.float32)
     if q_scale is not None:
-        yq = torch.empty((n, c, oh, ow), dtype=torch.int8, device="cuda")
+        yq = _out(out_q, (n, c, oh, ow), torch.int8)
         L.check(L.load().saber_hip_pool2d_f32_from_i8_q(n, h, w, c, oh, ow, window[0], window[1], stride[0], stride[1],
                                                         pad[0], pad[1], pool_type, dtype_code(x), float(scale), _p(x),
                                                         _p(y), float(q_scale), _p(yq), _stream()))
@@ -664,9 +676,9 @@ def pooling_f32_from_i8(x, scale, window, stride, pad, pool_type, global_pooling
     return y
 
 
-def softmax(x):
+def softmax(x, out=None):
     rows, cols = x.shape[0], x.numel() // x.shape[0]
-    y = torch.empty_like(x)
+    y = _out(out, x.shape, x.dtype)
     L.check(L.load().saber_hip_softmax_f32(rows, cols, _p(x), _p(y), _stream()))
     return y
 

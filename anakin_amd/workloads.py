@@ -292,7 +292,7 @@ def _out_hw(h, k, s, p):
 
 
 def build_int8_net(model, scales, batch, hw=224, fuse=True, chain=2, stage=True, stem_pair=True, head_pair=False, shared_device=False,
-                   fc_softmax=True, absorb_pool=True, separable=False, **legacy):
+                   fc_softmax=True, absorb_pool=True, separable=False, before_finalize=None, **legacy):
     """ResNet INT8 op list on the device (see the module docstring for the dtype rules): ONE op per reference operator, exactly the list
     `model["spec"]` holds (workloads.framework_spec: what the reference's own optimiser emits) - and, with `fuse`, handed to the C++ host
     side (saber_hip_net_optimize, the product's only executor-level fuser) which finds conv + eltwise, sibling pairs, conv + pooling,
@@ -312,6 +312,8 @@ def build_int8_net(model, scales, batch, hw=224, fuse=True, chain=2, stage=True,
     separable (opt-in): a depthwise 3x3 conv and the 1x1 conv that alone reads it (MobileNet's separable pairs) become sites of the one-launch
     form (flag SABER_HIP_NET_SEPARABLE = 16384, after the flag-15 pass): net.separated counts them. Which sites run fused is the static
     rule's choice, then the autotuner's (profiles/sep/README.md); the default builds exactly the list it built before.
+    before_finalize (optional): called with the net once the op list has its final form, just before finalize() - the place to bind
+    tensors to caller-owned memory (Net.bind; net.tensors maps every edge name to its id).
     (The Python fuser of rounds 1 - 5 lives in tests/py_fuser.py: test infrastructure.)"""
     from . import lib as L
     from . import saber as S
@@ -394,6 +396,8 @@ def build_int8_net(model, scales, batch, hw=224, fuse=True, chain=2, stage=True,
                                    (1024 if int(chain) >= 2 and head_pair else 0)) if chain else 0
         # the fc and the Softmax over its output as one launch (flag 4096: the last-arriving workgroup of the fc kernel normalises the rows)
         net.fc_softmaxed = net.optimize(4096) if fc_softmax else 0
+    if before_finalize is not None:
+        before_finalize(net)
     net.finalize()
     return net
 

@@ -25,7 +25,18 @@
  *                      device. Pairs, chains and stages COPY their members' weights when they are created: they keep the weights
  *                      their members had then.
  *   *_run              every inference ("dispatch"): enqueues on the given hipStream_t, never syncs.
- * All tensor pointers given to *_run are DEVICE pointers owned by the caller. Returns 0 on success
+ * All tensor pointers given to *_run are DEVICE pointers owned by the caller.
+ * Memory contract of every *_run entry point, of saber_hip_net_bind_tensor and of the pointers a captured list records:
+ *   - every tensor pointer and every workspace pointer is 16-byte aligned. The kernels issue 16-byte vector loads and stores
+ *     (uint4 / float4, b128 buffer accesses) from the base pointer and nothing wider; no entry point checks the alignment or
+ *     falls back on a weaker one. Rows inside a tensor need no alignment of their own (any C, K, W).
+ *   - the library reads and writes only [ptr, ptr + bytes) of each tensor (bytes = elements x element size of the shape the
+ *     op was created with; no rounding up to a vector, tile or allocation granule) and only [workspace, workspace +
+ *     *_workspace_bytes()) of a workspace. Read-only tensors (x, res, a) are not written. Memory next to a tensor may belong
+ *     to somebody else: saber_hip_net_compact_arena packs edges that way.
+ *   - a workspace may hold anything on entry; nothing is expected to survive in it between calls.
+ *   (tests/test_gpu_guard.py holds every launch form to this with guard bands around tensors that are aligned to 16 bytes and no more.)
+ * Returns 0 on success
  * or a negative saber_hip_status; the adaptor maps 0 -> SaberSuccess(-1, saber_types.h:224) and
  * the others onto SaberInvalidValue / SaberUnImplError / SaberOutOfMem.
  *

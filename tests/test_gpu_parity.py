@@ -2468,12 +2468,39 @@ def test_conv_f32_random_geometry_every_accepted_selection_within_tolerance(seed
     print("seed %d %s%s: %d kernel forms within 1e-4" % (seed, (N, H, Wd, C, K, k, pad, stride, dil), " + sum" if elt else "", len(tried)))
 
 
-@pytest.mark.parametrize("seed", range(24))
-def test_pooling_eltwise_fc_random_shapes_vs_oracle(seed):
-    """The streaming operators on shapes drawn at random: 8-bit and FP32 pooling (window 1 .. 5, stride 1 .. 3, padding, ceil and floor output
-    rule, max / the two averages, ragged sizes, channel counts that are not multiples of the vector width), INT8 and FP32 eltwise sums with
-    arbitrary coefficients / scales / lengths, INT8 (s8 / u8 / quantise-on-entry) and FP32 fully connected layers with ragged M, N, K - the
-    oracle's bytes where the path is integer or a fixed-order f32 reduction, 1e-4 for the FP32 fc."""
+class StreamOp:
+    """One launch of a streaming operator / fc / GEMM as the generators below yield it: run(T, ws=None) takes the device tensors by name
+    (inputs; an output named in `oracle` is written in place when T has it, allocated by the wrapper otherwise) and returns {name: output
+    tensor}; check(got, want) holds the operator's assertions on {name: ndarray}. prev: {name: ndarray} an in-place output starts from."""
+
+    def __init__(self, name, run, check, ws_bytes=0, prev=None):
+        self.name, self.run, self.check, self.ws_bytes, self.prev = name, run, check, ws_bytes, prev or {}
+
+
+def run_stream_op(op, arrays, oracle):
+    """the launch on ordinary tensors, outputs allocated by the wrappers (in-place ones start from op.prev); asserts op.check"""
+    T = {n: dev(a) for n, a in arrays.items()}
+    for n, a in op.prev.items():
+        T[n] = dev(a.copy())
+    got = op.run(T)
+    op.check({n: host(got[n]) for n in oracle}, oracle)
+
+
+def _fc_run(fc):
+    def run(T, ws=None):
+        if ws is not None:
+            fc.ws = ws
+        y = T["y"] if "y" in T else torch.empty((fc.desc.m, fc.desc.n), dtype=torch.float32, device="cuda")
+        return {"y": fc.dispatch(T["x"], y)}
+    return run
+
+
+def _fc_ws(fc):
+    return int(L.load().saber_hip_fc_workspace_bytes(fc.h))
+
+
+def gen_pooling_eltwise_fc(seed):
+    """test_pooling_eltwise_fc_random_shapes_vs_oracle's cases as (op, arrays, oracle) tuples, drawn in that test's order"""
     rng = np.random.default_rng(8800 + seed)
     # ---- pooling -----------------------------------------------------------------------------------------------------------------
     for _ in range(4):
@@ -2487,16 +2514,23 @@ def test_pooling_eltwise_fc_random_shapes_vs_oracle(seed):
         dt = int(rng.choice([O.S8, O.U8]))
         x = (rng.integers(0, 256, (N, H, Wd, Cc)).astype(np.uint8) if dt == O.U8 else rng.integers(-128, 128, (N, H, Wd, Cc)).astype(np.int8))
         want = O.pool_i8_nhwc(x, (win, win), (st, st), (pad, pad), pt, floor_mode=floor)
-        got = host(S.pooling_i8(dev(x), (win, win), (st, st), (pad, pad), pt, floor_mode=floor))
-        assert got.shape == want.shape and np.array_equal(got, want), ("pool i8", (N, H, Wd, Cc), win, st, pad, pt, floor, dt)
+        geo = ((win, win), (st, st), (pad, pad), pt)
+
+        def check_i8(got, w, what=("pool i8", (N, H, Wd, Cc), win, st, pad, pt, floor, dt)):
+            assert got["y"].shape == w["y"].shape and np.array_equal(got["y"], w["y"]), what
+        yield StreamOp("pooling_i8", lambda T, ws=None, g=geo, f=floor: {"y": S.pooling_i8(T["x"], *g, floor_mode=f, out=T.get("y"))}, check_i8), \
+            {"x": x}, {"y": want}
         xf = rng.standard_normal((N, Cc, H, Wd)).astype(np.float32)
         wantf = O.pool_f32_nchw(xf, (win, win), (st, st), (pad, pad), pt, floor_mode=floor)
-        gotf = host(S.pooling_f32(dev(xf), (win, win), (st, st), (pad, pad), pt, floor_mode=floor))
+
         # (a ceil-mode window that starts past the image - stride > window on the last row - averages nothing: NaN on both sides)
-        assert np.array_equal(gotf, wantf, equal_nan=True), ("pool f32 nchw", (N, Cc, H, Wd), win, st, pad, pt, floor)
+        def check_f(got, w, what=("pool f32", (N, Cc, H, Wd), win, st, pad, pt, floor)):
+            assert np.array_equal(got["y"], w["y"], equal_nan=True), what
+        yield StreamOp("pooling_f32_nchw", lambda T, ws=None, g=geo, f=floor: {"y": S.pooling_f32(T["x"], *g, floor_mode=f, out=T.get("y"))}, check_f), \
+            {"x": xf}, {"y": wantf}
         xh = np.ascontiguousarray(xf.transpose(0, 2, 3, 1))
-        goth = host(S.pooling_f32(dev(xh), (win, win), (st, st), (pad, pad), pt, layout=L.NHWC, floor_mode=floor))
-        assert np.array_equal(goth, wantf.transpose(0, 2, 3, 1), equal_nan=True), ("pool f32 nhwc", (N, Cc, H, Wd), win, st, pad, pt, floor)
+        yield StreamOp("pooling_f32_nhwc", lambda T, ws=None, g=geo, f=floor: {"y": S.pooling_f32(T["x"], *g, layout=L.NHWC, floor_mode=f, out=T.get("y"))},
+                       check_f), {"x": xh}, {"y": np.ascontiguousarray(wantf.transpose(0, 2, 3, 1))}
     # ---- eltwise -----------------------------------------------------------------------------------------------------------------
     for _ in range(4):
         n = int(rng.choice([1, 15, 16, 17, 1003, 4096, 65537]))
@@ -2504,19 +2538,26 @@ def test_pooling_eltwise_fc_random_shapes_vs_oracle(seed):
         sa, sb = float(rng.uniform(0.01, 0.5)), float(rng.uniform(0.01, 0.5))
         c0, c1 = float(np.float32(rng.uniform(0.5, 20.0))), float(np.float32(rng.uniform(0.5, 20.0)))
         relu = bool(rng.integers(0, 2))
-        assert np.array_equal(host(S.eltwise_sum(dev(a), dev(b), (c0, c1), relu, sa, sb)), O.eltwise_i8(a, b, sa, sb, c0, c1, relu)), ("eltwise i8", n, relu)
+
+        def check_e(got, w, what=("eltwise", n, relu)):
+            assert np.array_equal(got["y"], w["y"]), what
+        yield StreamOp("eltwise_sum_i8", lambda T, ws=None, k=((c0, c1), relu, sa, sb): {"y": S.eltwise_sum(T["a"], T["b"], *k, out=T.get("y"))}, check_e), \
+            {"a": a, "b": b}, {"y": O.eltwise_i8(a, b, sa, sb, c0, c1, relu)}
         fa, fb = rng.standard_normal(n).astype(np.float32), rng.standard_normal(n).astype(np.float32)
-        assert np.array_equal(host(S.eltwise_sum(dev(fa), dev(fb), (c0, c1), relu)), O.eltwise_f32(fa, fb, c0, c1, relu)), ("eltwise f32", n, relu)
+        yield StreamOp("eltwise_sum_f32", lambda T, ws=None, k=((c0, c1), relu): {"y": S.eltwise_sum(T["a"], T["b"], *k, out=T.get("y"))}, check_e), \
+            {"a": fa, "b": fb}, {"y": O.eltwise_f32(fa, fb, c0, c1, relu)}
     # ---- fully connected ---------------------------------------------------------------------------------------------------------
     for _ in range(3):
         M, N, K = int(rng.integers(1, 20)), int(rng.choice([1, 7, 10, 33, 64, 100, 1000])), int(rng.choice([16, 48, 100, 256, 528, 1000, 2048, 4112]))
         w = (rng.standard_normal((N, K)) * 0.05).astype(np.float32)
         b = rng.standard_normal(N).astype(np.float32)
-        y = torch.empty((M, N), dtype=torch.float32, device="cuda")
         xf = rng.standard_normal((M, K)).astype(np.float32)
         want = O.fc_f32(xf, w, b)
         fc = S.SaberFc(False).init(M, N, K, w, b, L.F32)
-        assert np.abs(host(fc.dispatch(dev(xf), y)) - want).max() <= FP32_RTOL * max(np.abs(want).max(), 1e-6), ("fc f32", M, N, K, fc.algo())
+
+        def check_fc32(got, wt, what=("fc f32", M, N, K, fc.algo())):
+            assert np.abs(got["y"] - wt["y"]).max() <= FP32_RTOL * max(np.abs(wt["y"]).max(), 1e-6), what
+        yield StreamOp("fc_f32:" + fc.algo(), _fc_run(fc), check_fc32, _fc_ws(fc)), {"x": xf}, {"y": want}
         if K % 16 == 0:
             ws = O.weight_scales(w)
             wq = O.quant_weights(w, ws)
@@ -2524,18 +2565,41 @@ def test_pooling_eltwise_fc_random_shapes_vs_oracle(seed):
                 xs = (rng.integers(0, 256, (M, K)).astype(np.uint8) if dt == L.U8 else rng.integers(-128, 128, (M, K)).astype(np.int8))
                 fc = S.SaberFc(True).init(M, N, K, wq, b, dt, 0.031, 0.5 if dt == L.U8 else 1.0, w_scale=ws)
                 wanti = O.fc_i8(xs, wq, ws, 0.031, b, 0.5) if dt == L.U8 else O.fc_i8(xs, wq, ws, 0.031, b)
-                assert np.array_equal(host(fc.dispatch(dev(xs), y)), wanti), ("fc i8", M, N, K, dt, fc.algo())
+
+                def check_fci(got, wt, what=("fc i8", M, N, K, dt, fc.algo())):
+                    assert np.array_equal(got["y"], wt["y"]), what
+                yield StreamOp("fc_i8:" + fc.algo(), _fc_run(fc), check_fci, _fc_ws(fc)), {"x": xs}, {"y": wanti}
             in_scale = float(np.abs(xf).max() / 127)
             fc = S.SaberFc(True).init(M, N, K, w, b, L.F32, in_scale)
-            assert np.array_equal(host(fc.dispatch(dev(xf), y)), O.fc_i8(O.quant_flat_s8(xf, in_scale), wq, ws, in_scale, b)), ("fc i8 f32-in", M, N, K, fc.algo())
+
+            def check_fcq(got, wt, what=("fc i8 f32-in", M, N, K, fc.algo())):
+                assert np.array_equal(got["y"], wt["y"]), what
+            yield StreamOp("fc_i8_f32in:" + fc.algo(), _fc_run(fc), check_fcq, _fc_ws(fc)), {"x": xf}, \
+                {"y": O.fc_i8(O.quant_flat_s8(xf, in_scale), wq, ws, in_scale, b)}
 
 
-@pytest.mark.parametrize("seed", range(16))
-def test_layout_quant_softmax_gemm_random_shapes_vs_oracle(seed):
-    """The remaining operators of the path on shapes drawn at random: quantise f32 NCHW -> s8 / u8 NHWC (ties, saturation, channel padding),
-    dequantise back, the two f32 transposes, flat quantisation, softmax over ragged row lengths (large logits included), Gemm with both
-    transposes / alpha / beta on ragged M, N, K - bytes where the path is a rounding or a copy, 1e-4 for softmax and the GEMM."""
+@pytest.mark.parametrize("seed", range(24))
+def test_pooling_eltwise_fc_random_shapes_vs_oracle(seed):
+    """The streaming operators on shapes drawn at random: 8-bit and FP32 pooling (window 1 .. 5, stride 1 .. 3, padding, ceil and floor output
+    rule, max / the two averages, ragged sizes, channel counts that are not multiples of the vector width), INT8 and FP32 eltwise sums with
+    arbitrary coefficients / scales / lengths, INT8 (s8 / u8 / quantise-on-entry) and FP32 fully connected layers with ragged M, N, K - the
+    oracle's bytes where the path is integer or a fixed-order f32 reduction, 1e-4 for the FP32 fc. (The cases come from
+    gen_pooling_eltwise_fc, which tests/test_gpu_guard.py runs again between guard bands.)"""
+    ran = 0
+    for op, arrays, oracle in gen_pooling_eltwise_fc(seed):
+        run_stream_op(op, arrays, oracle)
+        ran += 1
+    assert ran >= 4 * 3 + 4 * 2 + 3
+
+
+def gen_layout_quant_softmax_gemm(seed):
+    """test_layout_quant_softmax_gemm_random_shapes_vs_oracle's cases as (op, arrays, oracle) tuples, drawn in that test's order"""
     rng = np.random.default_rng(6600 + seed)
+
+    def eq(what):
+        def check(got, w):
+            assert np.array_equal(got["y"], w["y"]), what
+        return check
     for _ in range(3):
         n, c, h, w = int(rng.integers(1, 4)), int(rng.choice([1, 3, 4, 5, 16, 17, 64, 100])), int(rng.integers(1, 30)), int(rng.integers(1, 30))
         x = (rng.standard_normal((n, c, h, w)) * 40.0).astype(np.float32)
@@ -2543,22 +2607,31 @@ def test_layout_quant_softmax_gemm_random_shapes_vs_oracle(seed):
         scale = float(rng.choice([0.25, 0.5, 1.0, 0.37]))
         for odt in (O.S8, O.U8):
             want = O.quant_nchw_to_nhwc(x, scale, odt)
-            got = host(S.quantize_nchw_to_nhwc(dev(x), scale, odt))
-            assert np.array_equal(got, want), ("quantise", (n, c, h, w), scale, odt)
-            back = host(S.dequantize_nhwc_to_nchw(dev(want), scale))
-            assert np.array_equal(back, O.dequant_nhwc_to_nchw(want, scale)), ("dequantise", (n, c, h, w), scale, odt)
+            yield StreamOp("quantize_nchw_to_nhwc", lambda T, ws=None, k=(scale, odt): {"y": S.quantize_nchw_to_nhwc(T["x"], *k, out=T.get("y"))},
+                           eq(("quantise", (n, c, h, w), scale, odt))), {"x": x}, {"y": want}
+            yield StreamOp("dequantize_nhwc_to_nchw", lambda T, ws=None, k=scale: {"y": S.dequantize_nhwc_to_nchw(T["x"], k, out=T.get("y"))},
+                           eq(("dequantise", (n, c, h, w), scale, odt))), {"x": want}, {"y": O.dequant_nhwc_to_nchw(want, scale)}
         c_pad = c + int(rng.integers(0, 4))
-        t = host(S.transpose_nchw_to_nhwc(dev(x), c_pad))
-        assert np.array_equal(t[..., :c], x.transpose(0, 2, 3, 1)) and not t[..., c:].any(), ("nchw->nhwc", (n, c, h, w), c_pad)
-        assert np.array_equal(host(S.transpose_nhwc_to_nchw(dev(t), c)), x), ("nhwc->nchw", (n, c, h, w), c_pad)
+        t_ref = np.zeros((n, h, w, c_pad), np.float32)
+        t_ref[..., :c] = x.transpose(0, 2, 3, 1)
+
+        def check_t(got, wt, what=("nchw->nhwc", (n, c, h, w), c_pad), c=c):
+            t = got["y"]
+            assert np.array_equal(t[..., :c], wt["y"][..., :c]) and not t[..., c:].any(), what
+        yield StreamOp("transpose_nchw_to_nhwc", lambda T, ws=None, k=c_pad: {"y": S.transpose_nchw_to_nhwc(T["x"], k, out=T.get("y"))}, check_t), \
+            {"x": x}, {"y": t_ref}
+        yield StreamOp("transpose_nhwc_to_nchw", lambda T, ws=None, k=c: {"y": S.transpose_nhwc_to_nchw(T["x"], k, out=T.get("y"))},
+                       eq(("nhwc->nchw", (n, c, h, w), c_pad))), {"x": t_ref}, {"y": x}
         flat = (rng.standard_normal(int(rng.choice([1, 63, 64, 1000, 4097]))) * 30).astype(np.float32)
-        assert np.array_equal(host(S.quantize_flat_s8(dev(flat), scale)), O.quant_flat_s8(flat, scale)), ("flat quantise", flat.size)
+        yield StreamOp("quantize_flat_s8", lambda T, ws=None, k=scale: {"y": S.quantize_flat_s8(T["x"], k, out=T.get("y"))},
+                       eq(("flat quantise", flat.size))), {"x": flat}, {"y": O.quant_flat_s8(flat, scale)}
     for _ in range(3):
         rows, cols = int(rng.integers(1, 20)), int(rng.choice([1, 2, 10, 63, 64, 65, 1000, 1001, 4096]))
         z = (rng.standard_normal((rows, cols)) * float(rng.choice([1.0, 10.0, 60.0]))).astype(np.float32)
-        want = O.softmax_f32(z)
-        got = host(S.softmax(dev(z)))
-        assert np.abs(got - want).max() <= FP32_RTOL * want.max() and np.allclose(got.sum(1), 1.0, atol=1e-5), ("softmax", rows, cols)
+
+        def check_s(got, wt, what=("softmax", rows, cols)):
+            assert np.abs(got["y"] - wt["y"]).max() <= FP32_RTOL * wt["y"].max() and np.allclose(got["y"].sum(1), 1.0, atol=1e-5), what
+        yield StreamOp("softmax", lambda T, ws=None: {"y": S.softmax(T["x"], out=T.get("y"))}, check_s), {"x": z}, {"y": O.softmax_f32(z)}
     for _ in range(3):
         M, N, K = int(rng.choice([1, 3, 8, 17, 64, 100])), int(rng.choice([1, 10, 64, 100, 1000])), int(rng.choice([1, 7, 64, 100, 513, 2048]))
         ta, tb = bool(rng.integers(0, 2)), bool(rng.integers(0, 2))
@@ -2567,9 +2640,24 @@ def test_layout_quant_softmax_gemm_random_shapes_vs_oracle(seed):
         Bm = rng.standard_normal((N, K) if tb else (K, N)).astype(np.float32)
         C0 = rng.standard_normal((M, N)).astype(np.float32)
         want = O.gemm_f32(A, Bm, M, N, K, ta, tb, alpha, beta, C0)
-        cd = dev(C0.copy())
-        got = host(S.gemm(ta, tb, M, N, K, alpha, dev(A), dev(Bm), beta, cd))
-        assert np.abs(got - want).max() <= FP32_RTOL * max(np.abs(want).max(), 1e-6), ("gemm", M, N, K, ta, tb, alpha, beta)
+
+        def check_g(got, wt, what=("gemm", M, N, K, ta, tb, alpha, beta)):
+            assert np.abs(got["c"] - wt["c"]).max() <= FP32_RTOL * max(np.abs(wt["c"]).max(), 1e-6), what
+        yield StreamOp("gemm_f32", lambda T, ws=None, k=(ta, tb, M, N, K, alpha), be=beta: {"c": S.gemm(*k, T["a"], T["b"], be, T["c"])}, check_g,
+                       prev={"c": C0}), {"a": A, "b": Bm}, {"c": want}
+
+
+@pytest.mark.parametrize("seed", range(16))
+def test_layout_quant_softmax_gemm_random_shapes_vs_oracle(seed):
+    """The remaining operators of the path on shapes drawn at random: quantise f32 NCHW -> s8 / u8 NHWC (ties, saturation, channel padding),
+    dequantise back, the two f32 transposes, flat quantisation, softmax over ragged row lengths (large logits included), Gemm with both
+    transposes / alpha / beta on ragged M, N, K - bytes where the path is a rounding or a copy, 1e-4 for softmax and the GEMM. (The cases
+    come from gen_layout_quant_softmax_gemm, which tests/test_gpu_guard.py runs again between guard bands.)"""
+    ran = 0
+    for op, arrays, oracle in gen_layout_quant_softmax_gemm(seed):
+        run_stream_op(op, arrays, oracle)
+        ran += 1
+    assert ran == 3 * 7 + 3 + 3
 
 
 @pytest.mark.parametrize("seed", range(16))
