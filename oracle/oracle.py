@@ -203,6 +203,14 @@ def pool_out_dim(inp, pad, win, stride, floor_mode=False):
     return lib().orc_pool_out_dim(inp, pad, win, stride, int(floor_mode))
 
 
+def pool_out_hw(H, W, pad, win, stride, floor_mode=False):
+    """Both output dims: the reference drops a last window that starts at or past in + pad on BOTH axes whenever EITHER pad is non-zero
+    (pooling_padded(), saber/funcs/pooling.h:118-125)."""
+    ap = int(pad[0] > 0 or pad[1] > 0)
+    return (lib().orc_pool_out_dim2(H, pad[0], win[0], stride[0], int(floor_mode), ap),
+            lib().orc_pool_out_dim2(W, pad[1], win[1], stride[1], int(floor_mode), ap))
+
+
 def pool_i8_nhwc(x, win, stride, pad, ptype, out_dtype=None, global_pool=False, floor_mode=False):
     x = np.ascontiguousarray(x)
     N, H, W, Cc = x.shape
@@ -210,8 +218,7 @@ def pool_i8_nhwc(x, win, stride, pad, ptype, out_dtype=None, global_pool=False, 
         win, stride, pad = (H, W), (H, W), (0, 0)
         oh = ow = 1
     else:
-        oh = pool_out_dim(H, pad[0], win[0], stride[0], floor_mode)
-        ow = pool_out_dim(W, pad[1], win[1], stride[1], floor_mode)
+        oh, ow = pool_out_hw(H, W, pad, win, stride, floor_mode)
     od = code_of(x) if out_dtype is None else out_dtype
     out = np.empty((N, oh, ow, Cc), NP_DTYPE[od])
     lib().orc_pool_i8_nhwc(N, H, W, Cc, oh, ow, win[0], win[1], stride[0], stride[1], pad[0], pad[1],
@@ -226,8 +233,7 @@ def pool_f32_nchw(x, win, stride, pad, ptype, global_pool=False, floor_mode=Fals
         win, stride, pad = (H, W), (H, W), (0, 0)
         oh = ow = 1
     else:
-        oh = pool_out_dim(H, pad[0], win[0], stride[0], floor_mode)
-        ow = pool_out_dim(W, pad[1], win[1], stride[1], floor_mode)
+        oh, ow = pool_out_hw(H, W, pad, win, stride, floor_mode)
     out = np.empty((N, Cc, oh, ow), np.float32)
     lib().orc_pool_f32_nchw(N, Cc, H, W, oh, ow, win[0], win[1], stride[0], stride[1], pad[0], pad[1],
                             ptype, _ptr(x), _ptr(out))

@@ -376,8 +376,9 @@ void orc_eltwise_f32(size_t n, const float* a, const float* b, float c0, float c
 /* ---- pooling -------------------------------------------------------------------------------- */
 
 /* Pooling<>::compute_output_shape (saber/funcs/pooling.h:69-130): ceil unless
- * cmp_out_shape_floor_as_conv; with padding, drop a window that starts beyond the padded input. */
-int orc_pool_out_dim(int in, int pad, int win, int stride, int floor_mode) {
+ * cmp_out_shape_floor_as_conv; when the pooling is padded - EITHER pad non-zero (pooling_padded(),
+ * :118-125): any_pad - a last window that starts at or beyond in + pad is dropped, on both axes. */
+int orc_pool_out_dim2(int in, int pad, int win, int stride, int floor_mode, int any_pad) {
     int o;
     if (floor_mode) {
         o = (int)((float)(in + 2 * pad - win) / stride) + 1;
@@ -385,8 +386,12 @@ int orc_pool_out_dim(int in, int pad, int win, int stride, int floor_mode) {
     } else {
         o = (int)ceilf((float)(in + 2 * pad - win) / stride) + 1;
     }
-    if (pad > 0 && (o - 1) * stride >= in + pad) --o;
+    if (any_pad && (o - 1) * stride >= in + pad) --o;
     return o;
+}
+/* one axis on its own (both axes padded alike) */
+int orc_pool_out_dim(int in, int pad, int win, int stride, int floor_mode) {
+    return orc_pool_out_dim2(in, pad, win, stride, floor_mode, pad > 0);
 }
 
 /* [unpinned: JIT] SaberPooling<X86, AK_INT8> (saber_pooling.cpp:589-654 +

@@ -36,15 +36,15 @@ static int g_fail = 0, g_run = 0;
 
 static DataType ak(int code) { return code == 0 ? AK_FLOAT : (code == 1 ? AK_INT8 : AK_UINT8); }
 
-// one case: conv (+ optional fused eltwise with a residual tensor)
-static void test_conv_int8(int N, int C, int H, int W, int K, int k, int pad, int stride, int dil, bool bias_term,
-                           bool relu, int in_dt /*1 s8, 2 u8*/, int out_dt /*0 f32, 1 s8, 2 u8*/, bool fuse_eltwise,
-                           Context<MI355X>& ctx) {
-    std::mt19937 rng(1234 + N * 7 + C * 13 + K * 17 + k * 19 + pad + stride * 3 + in_dt * 5 + out_dt * 11 + relu);
-    const int OH = (H + 2 * pad - (dil * (k - 1) + 1)) / stride + 1, OW = (W + 2 * pad - (dil * (k - 1) + 1)) / stride + 1;
+// one case: conv (+ optional fused eltwise with a residual tensor); every geometry parameter per axis (h, w)
+static void test_conv_int8_axes(int N, int C, int H, int W, int K, int kh, int kw, int pad_h, int pad_w, int stride_h, int stride_w,
+                                int dil_h, int dil_w, bool bias_term, bool relu, int in_dt /*1 s8, 2 u8*/,
+                                int out_dt /*0 f32, 1 s8, 2 u8*/, bool fuse_eltwise, unsigned seed, Context<MI355X>& ctx) {
+    std::mt19937 rng(seed);
+    const int OH = (H + 2 * pad_h - (dil_h * (kh - 1) + 1)) / stride_h + 1, OW = (W + 2 * pad_w - (dil_w * (kw - 1) + 1)) / stride_w + 1;
     std::vector<uint8_t> x((size_t)N * H * W * C);
     for (auto& v : x) v = in_dt == 2 ? (uint8_t)(rng() % 256) : (uint8_t)(int8_t)((int)(rng() % 256) - 128);
-    std::vector<float> w((size_t)K * C * k * k), b(K);
+    std::vector<float> w((size_t)K * C * kh * kw), b(K);
     std::normal_distribution<float> nd(0.f, 0.3f);
     for (auto& v : w) v = nd(rng);
     for (auto& v : b) v = nd(rng);
@@ -53,8 +53,8 @@ static void test_conv_int8(int N, int C, int H, int W, int K, int k, int pad, in
     // ---- oracle ------------------------------------------------------------------------------
     std::vector<float> ws(K), bp(K), sc(K);
     std::vector<int8_t> wq(w.size());
-    orc_weight_scales(w.data(), K, C * k * k, ws.data());
-    orc_quant_weights(w.data(), K, C * k * k, ws.data(), wq.data());
+    orc_weight_scales(w.data(), K, C * kh * kw, ws.data());
+    orc_quant_weights(w.data(), K, C * kh * kw, ws.data(), wq.data());
     orc_conv_i8_prepare(K, ws.data(), bias_term ? b.data() : nullptr, in_scale, out_scale, in_dt, out_dt, bp.data(), sc.data());
     const size_t on = (size_t)N * OH * OW * K;
     std::vector<uint8_t> want(on * (out_dt == 0 ? 4 : 1)), got(want.size());
@@ -62,11 +62,11 @@ static void test_conv_int8(int N, int C, int H, int W, int K, int k, int pad, in
     for (auto& v : res) v = (int8_t)((int)(rng() % 256) - 128);
     if (fuse_eltwise) {   // conv -> s8, then SaberEltwise<AK_INT8> sum + relu: two oracle ops
         std::vector<int8_t> mid(on);
-        orc_conv_i8(N, H, W, C, K, k, k, pad, pad, stride, stride, dil, dil, 1, in_dt, 1, relu, x.data(), wq.data(),
+        orc_conv_i8(N, H, W, C, K, kh, kw, pad_h, pad_w, stride_h, stride_w, dil_h, dil_w, 1, in_dt, 1, relu, x.data(), wq.data(),
                     bias_term ? bp.data() : nullptr, sc.data(), nullptr, nullptr, mid.data());
         orc_eltwise_i8(on, mid.data(), res.data(), out_scale, res_scale, 1.f / elt_scale, 1.f / elt_scale, 1, (int8_t*)want.data());
     } else {
-        orc_conv_i8(N, H, W, C, K, k, k, pad, pad, stride, stride, dil, dil, 1, in_dt, out_dt, relu, x.data(), wq.data(),
+        orc_conv_i8(N, H, W, C, K, kh, kw, pad_h, pad_w, stride_h, stride_w, dil_h, dil_w, 1, in_dt, out_dt, relu, x.data(), wq.data(),
                     bias_term ? bp.data() : nullptr, sc.data(), nullptr, nullptr, want.data());
     }
 
@@ -79,10 +79,10 @@ static void test_conv_int8(int N, int C, int H, int W, int K, int k, int pad, in
     tres.set_scale({res_scale});
     tin.copy_from_host(x.data());
     tres.copy_from_host(res.data());
-    HostBlob hw(Shape({K, C, k, k}), AK_FLOAT, w.data());
+    HostBlob hw(Shape({K, C, kh, kw}), AK_FLOAT, w.data());
     HostBlob hb(Shape({1, K, 1, 1}), AK_FLOAT, b.data());
     ActivationParam<MI355X> act = relu ? ActivationParam<MI355X>(Active_relu) : ActivationParam<MI355X>();
-    ConvParam<MI355X> cp(1, pad, pad, stride, stride, dil, dil, &hw, bias_term ? &hb : nullptr, act);
+    ConvParam<MI355X> cp(1, pad_h, pad_w, stride_h, stride_w, dil_h, dil_w, &hw, bias_term ? &hb : nullptr, act);
     std::vector<Tensor<MI355X>*> ins{&tin}, outs{&tout};
     SaberStatus st;
     const char* algo = "";
@@ -110,10 +110,17 @@ static void test_conv_int8(int N, int C, int H, int W, int K, int k, int pad, in
     else for (size_t i = 0; i < want.size(); ++i) diff += want[i] != got[i];
     if (diff) {
         ++g_fail;
-        printf("FAIL N=%d C=%d HxW=%dx%d K=%d k=%d pad=%d stride=%d dil=%d bias=%d relu=%d in=%d out=%d fused=%d status=%d "
-               "mismatching bytes=%zu/%zu [%s]\n", N, C, H, W, K, k, pad, stride, dil, bias_term, relu, in_dt, out_dt,
-               fuse_eltwise, (int)st, diff, want.size(), algo);
+        printf("FAIL N=%d C=%d HxW=%dx%d K=%d k=%dx%d pad=%d,%d stride=%d,%d dil=%d,%d bias=%d relu=%d in=%d out=%d fused=%d status=%d "
+               "mismatching bytes=%zu/%zu [%s]\n", N, C, H, W, K, kh, kw, pad_h, pad_w, stride_h, stride_w, dil_h, dil_w, bias_term, relu,
+               in_dt, out_dt, fuse_eltwise, (int)st, diff, want.size(), algo);
     }
+}
+
+// the square case: both axes of every pair the same (the seed is the one these cases have always had)
+static void test_conv_int8(int N, int C, int H, int W, int K, int k, int pad, int stride, int dil, bool bias_term,
+                           bool relu, int in_dt, int out_dt, bool fuse_eltwise, Context<MI355X>& ctx) {
+    test_conv_int8_axes(N, C, H, W, K, k, k, pad, pad, stride, stride, dil, dil, bias_term, relu, in_dt, out_dt, fuse_eltwise,
+                        1234 + N * 7 + C * 13 + K * 17 + k * 19 + pad + stride * 3 + in_dt * 5 + out_dt * 11 + relu, ctx);
 }
 
 // SaberConv2DPooling: conv + pooling through the Saber interface == oracle conv followed by oracle pooling.
@@ -199,6 +206,11 @@ int main() {
     test_conv_int8(2, 512, 7, 7, 512, 3, 1, 1, 1, true, true, 2, 0, false, ctx);       // f32 output
     test_conv_int8(2, 64, 56, 56, 256, 1, 0, 1, 1, true, false, 2, 1, true, ctx);      // res2 2c + fused eltwise
     test_conv_int8(1, 512, 7, 7, 2048, 1, 0, 1, 1, true, false, 2, 1, true, ctx);      // res5 2c + fused eltwise
+    // per-axis geometry through the adaptor's marshalling: a 1x7 kernel with pad (0, 3), a 7x1 with pad (3, 0), a 3x3 with stride (2, 1)
+    test_conv_int8_axes(1, 64, 9, 13, 32, 1, 7, 0, 3, 1, 1, 1, 1, true, true, 2, 2, false, 4001, ctx);
+    test_conv_int8_axes(1, 64, 13, 9, 32, 7, 1, 3, 0, 1, 1, 1, 1, true, false, 1, 1, false, 4002, ctx);
+    test_conv_int8_axes(2, 64, 12, 15, 48, 3, 3, 1, 1, 2, 1, 1, 1, true, true, 2, 0, false, 4003, ctx);
+    test_conv_int8_axes(1, 16, 12, 15, 16, 3, 3, 2, 1, 1, 1, 2, 1, false, false, 1, 1, true, 4004, ctx);      // dilation (2, 1) + fused eltwise
     test_conv_pooling(true, ctx);     // SaberConv2DPooling: fused stem + max pooling
     test_conv_pooling(false, ctx);    // SaberConv2DPooling: two launches behind the same interface
     printf("%d/%d cases bit-exact\n", g_run - g_fail, g_run);
