@@ -148,6 +148,20 @@ static void pack_coop4_stream(const saber_hip_conv* c3, const saber_hip_conv* a,
             }
         }
 }
+// ... and the stream of a stage's HEAD (conv_stage4_c256_kernel<.., HEAD>: the sibling pair in front of the run, 512 -> 1024 | 256), per
+// (quarter q, wave w = K-half kh * 4 + n-tile nt), in consumption order:
+//   a (the shortcut), channels q*256 + w*32 .. +31:    [k-step 0..7][accumulator 0, 1]    16 fragments
+//   b (the 3x3 input), channels q*64 + nt*16 .. +15:   k-steps kh*4 + {0..3}               4
+static void pack_stage_head_stream(const saber_hip_conv* a, const saber_hip_conv* b, std::vector<uint8_t>& out) {
+    const int C0 = 512;
+    for (int q = 0; q < 4; ++q)
+        for (int w = 0; w < 8; ++w) {
+            const int nt = w & 3, kh = w >> 2;
+            for (int ks = 0; ks < 8; ++ks)
+                for (int mf = 0; mf < 2; ++mf) pack_frag1(a->wq_oihw.data(), C0, q * 256 + w * 32, 2, mf, ks, out);
+            for (int j = 0; j < 4; ++j) pack_frag1(b->wq_oihw.data(), C0, q * 64 + nt * 16, 1, 0, kh * 4 + j, out);
+        }
+}
 // ... and the one-workgroup-per-tile stage kernel's (conv_stage1_c128_kernel), C = 128: per wave w, in consumption order:
 //   3x3, channels w*16 .. +15: [tap][k-step 0, 1] (18) | 1x1 + eltwise, channels w*64 .. +63: [k-step 0, 1][accumulator 0..3] (8) |
 //   1x1, channels w*16 .. +15: [k-step 0..7] (8)
@@ -233,8 +247,33 @@ static unsigned div_magic(int d) { return d >= 2 ? (unsigned)((0x100000000ull + 
 // tail (optional): the strided head behind the run - conv3x3 / stride 2 + conv1x1 with the shortcut sub-sampled by 2, no second 1x1 conv -
 // whose 3x3 conv reads the last block's second output and whose shortcut is the last block's first output; it then runs inside the launch
 // whenever stage_run is given its output
-static int stage_build(saber_hip_chain* const* chains, int n, bool per_image, saber_hip_chain* tail, saber_hip_chain_stage** out) {
+// head_a / head_b (optional, both or none): the sibling pair in front of the run - two plain 1x1 convs over one 512-channel tensor whose
+// outputs are exactly the first block's shortcut (head_a: 1024 channels, s8) and 3x3 input (head_b: 256 channels); they then run inside the
+// launch whenever stage_run is given head_b's output
+static int stage_build(saber_hip_chain* const* chains, int n, bool per_image, saber_hip_chain* tail, saber_hip_chain_stage** out,
+                       const saber_hip_conv* head_a = nullptr, const saber_hip_conv* head_b = nullptr) {
     if (!chains || n <= 0 || n > saber_mi355x::STAGE4_LONG || !out) return fail(SABER_HIP_INVALID_VALUE, "stage: 1..24 chains");
+    if (head_a || head_b) {
+        if (!head_a || !head_b) return fail(SABER_HIP_INVALID_VALUE, "null argument");
+        if (!chains[0] || chains[0]->c1 != 256) return fail(SABER_HIP_INVALID_VALUE, "stage: a head goes with a C = 256 stage only");
+        if (!per_image) return fail(SABER_HIP_INVALID_VALUE, "stage: a head needs an image per XCD");
+        for (const saber_hip_conv* o : {head_a, head_b})
+            if (o->d.res_mode != SABER_HIP_RES_NONE) return fail(SABER_HIP_INVALID_VALUE, "stage: the head's convs carry no residual");
+        for (const saber_hip_conv* o : {head_a, head_b}) {
+            const saber_hip_conv_desc& d = o->d;
+            if (!o->is_i8 || !o->weights_set || o->algo != ALGO_IGEMM_I8 || o->epi != EPI_I8_CONV || o->pair_k2 || o->pool_fused || o->pool2 || o->gpool ||
+                o->pre_quant || o->pre_pad || d.kh != 1 || d.kw != 1 || d.stride_h != 1 || d.stride_w != 1 || d.pad_h != 0 || d.pad_w != 0 || d.group != 1 ||
+                o->c_eff != d.c || d.act_negative_slope != 0.f || d.in_layout != SABER_HIP_NHWC || d.out_layout != SABER_HIP_NHWC ||
+                (d.out_dtype != SABER_HIP_S8 && d.out_dtype != SABER_HIP_U8))
+                return fail(SABER_HIP_INVALID_VALUE, "stage: the head must be two plain 1x1 / stride 1 / pad 0 INT8 NHWC convs with weights set");
+        }
+        if (head_a->d.c != 512 || head_b->d.c != 512) return fail(SABER_HIP_INVALID_VALUE, "stage: the head's convs read 512 channels");
+        if (head_a->d.k != 1024 || head_b->d.k != 256) return fail(SABER_HIP_INVALID_VALUE, "stage: the head's convs write 1024 and 256 channels");
+        const saber_hip_conv_desc &d0 = chains[0]->a->d, &da = head_a->d, &db = head_b->d;
+        if (!chains[0]->c3 || da.n != d0.n || da.h != d0.h || da.w != d0.w || db.n != d0.n || db.h != d0.h || db.w != d0.w || head_a->x_dtype != head_b->x_dtype ||
+            da.out_dtype != SABER_HIP_S8 || (db.out_dtype == SABER_HIP_U8) != (chains[0]->c3->x_dtype == DT_U8))
+            return fail(SABER_HIP_INVALID_VALUE, "stage: the head's outputs must be the first block's shortcut (s8) and 3x3 input (its dtype), one input tensor");
+    }
     if (tail) {
         if (!chains[0] || chains[0]->c1 != 256 || tail->c1 != 256) return fail(SABER_HIP_INVALID_VALUE, "stage: a tail goes with a C = 256 stage only");
         if (n < 2 || !per_image || n + 1 > saber_mi355x::STAGE4_LONG) return fail(SABER_HIP_INVALID_VALUE, "stage: a tail needs 2..23 blocks, an image per XCD");
@@ -305,6 +344,22 @@ static int stage_build(saber_hip_chain* const* chains, int n, bool per_image, sa
         blk.push_back(B);
         st->tail = tail;
     }
+    if (head_a) {      // its constants are the table's FIRST entry, in front of block 0's: a launch passes d_blk + 1 (prm0: unused, the launch copies it like a block's)
+        std::vector<uint8_t> hs, p1, p2;
+        pack_stage_head_stream(head_a, head_b, hs);
+        pack_chain_params(head_a, (size_t)head_a->d.k / 4 * 3, p1);
+        pack_chain_params(head_b, ((size_t)head_b->d.k / 4 * 3 + 63) / 64 * 64 + 64, p2);      // (+ slack: whole 64-chunk blocks are copied)
+        if (e == hipSuccess) e = st->d_head_stream.upload(hs);
+        if (e == hipSuccess) e = st->d_head_prm1.upload(p1);
+        if (e == hipSuccess) e = st->d_head_prm2.upload(p2);
+        saber_mi355x::StageBlk B;
+        std::memset(&B, 0, sizeof B);
+        B.wstream = st->d_head_stream.p; B.prm0 = st->d_head_prm2.p; B.prm1 = st->d_head_prm1.p; B.prm2 = st->d_head_prm2.p;
+        B.in_u8 = head_a->x_dtype == DT_U8; B.relu1 = head_a->d.act == SABER_HIP_ACT_RELU;
+        B.relu2 = head_b->d.act == SABER_HIP_ACT_RELU; B.out_u8_2 = head_b->d.out_dtype == SABER_HIP_U8;
+        blk.insert(blk.begin(), B);
+        st->head_a = head_a; st->head_b = head_b;
+    }
     if (e == hipSuccess) e = st->d_blk.upload(blk);
     if (e == hipSuccess && st->c1 == 256) e = st->d_grp_ctr.alloc_zero(tiles * 32);
     if (e == hipSuccess) e = st->d_img_ctr.alloc_zero((size_t)d0.n * (st->tiles_per_img + 1) * 16);
@@ -320,30 +375,32 @@ static int stage_build(saber_hip_chain* const* chains, int n, bool per_image, sa
     return SABER_HIP_OK;
 }
 template <int MAXB>
-static int stage_launch(saber_hip_chain_stage* st, const void* x, const void* res, void* const* y1, void* const* y2, void* y_tail, hipStream_t s) {
+static int stage_launch(saber_hip_chain_stage* st, const void* x, const void* res, void* const* y1, void* const* y2, void* y_tail, void* y_head, hipStream_t s) {
     saber_mi355x::Stage4KArgs<MAXB> k;
     std::memset(&k, 0, sizeof k);
     k.x = x; k.res = res; k.zero = zero_page();
     if (!k.zero) return fail(SABER_HIP_RUNTIME_ERROR, "stage: zero page");
-    k.blk = st->d_blk.p; k.grp_ctr = st->d_grp_ctr.p; k.img_ctr = st->d_img_ctr.p; k.xch = st->d_xch.p; k.xcc = st->d_xcc.p; k.err = st->h_err;
+    k.blk = st->d_blk.p + (st->head_a ? 1 : 0); k.grp_ctr = st->d_grp_ctr.p; k.img_ctr = st->d_img_ctr.p; k.xch = st->d_xch.p; k.xcc = st->d_xcc.p; k.err = st->h_err;
     k.nblk = (int)st->chains.size(); k.N = st->n; k.H = st->h; k.W = st->w;
     k.tiles_x = st->tiles_x; k.tiles_per_img = st->tiles_per_img;
     k.mg_tiles_x = div_magic(st->tiles_x); k.mg_tpi = div_magic(st->tiles_per_img); k.mg_wpi = div_magic(st->tiles_per_img * 4);
     k.per_image = st->per_image;
     for (int i = 0; i < k.nblk; ++i) { k.y1[i] = y1[i]; k.y2[i] = y2[i]; }
     if (y_tail) k.y1[k.nblk] = y_tail;      // (the slot behind the last block's: stage_run has picked an argument block with room for it)
-    HIP_TRY(st->c1 == 256 ? saber_mi355x::launch_conv_stage4(k, y_tail != nullptr, s) : saber_mi355x::launch_conv_stage1_c128(k, s));
+    k.head_y = y_head;                      // (with a head x is the pair's input and res is not read)
+    HIP_TRY(st->c1 == 256 ? saber_mi355x::launch_conv_stage4(k, y_tail != nullptr, y_head != nullptr, s) : saber_mi355x::launch_conv_stage1_c128(k, s));
     return SABER_HIP_OK;
 }
-int stage_run(saber_hip_chain_stage* st, const void* x, const void* res, void* const* y1, void* const* y2, hipStream_t s, void* y_tail) {
+int stage_run(saber_hip_chain_stage* st, const void* x, const void* res, void* const* y1, void* const* y2, hipStream_t s, void* y_tail, void* y_head) {
     if (y_tail && !st->tail) return fail(SABER_HIP_INVALID_VALUE, "stage: created without a tail");
+    if (y_head && !st->head_a) return fail(SABER_HIP_INVALID_VALUE, "stage: created without a head");
     if (*(volatile unsigned*)st->h_err) {      // an earlier launch found cooperating workgroups on different XCDs or timed out in a barrier
         *(volatile unsigned*)st->h_err = 0u;
         return fail(SABER_HIP_RUNTIME_ERROR, "cooperative stage: an earlier launch's workgroups did not share an XCD or timed out at a barrier "
                     "(its outputs are not valid)");
     }
-    return (int)st->chains.size() + (y_tail ? 1 : 0) <= saber_mi355x::STAGE4_SHORT ? stage_launch<saber_mi355x::STAGE4_SHORT>(st, x, res, y1, y2, y_tail, s)
-                                                                                   : stage_launch<saber_mi355x::STAGE4_LONG>(st, x, res, y1, y2, y_tail, s);
+    return (int)st->chains.size() + (y_tail ? 1 : 0) <= saber_mi355x::STAGE4_SHORT ? stage_launch<saber_mi355x::STAGE4_SHORT>(st, x, res, y1, y2, y_tail, y_head, s)
+                                                                                   : stage_launch<saber_mi355x::STAGE4_LONG>(st, x, res, y1, y2, y_tail, y_head, s);
 }
 int saber_hip_conv2d_stage_create(saber_hip_chain_t* const* chains, int n, saber_hip_chain_stage_t** out) {
     if (!xcd_round_robin()) return fail(SABER_HIP_UNIMPL, "stage: this device does not place workgroup b on XCD b % 8");
@@ -353,6 +410,12 @@ int saber_hip_conv2d_stage_create_tail(saber_hip_chain_t* const* chains, int n, 
     if (!tail) return fail(SABER_HIP_INVALID_VALUE, "null argument");
     if (!xcd_round_robin()) return fail(SABER_HIP_UNIMPL, "stage: this device does not place workgroup b on XCD b % 8");
     return stage_build(chains, n, true, tail, out);
+}
+int saber_hip_conv2d_stage_create_head(saber_hip_chain_t* const* chains, int n, saber_hip_chain_t* tail, const saber_hip_conv_t* head_a,
+                                       const saber_hip_conv_t* head_b, saber_hip_chain_stage_t** out) {
+    if (!head_a || !head_b) return fail(SABER_HIP_INVALID_VALUE, "null argument");
+    if (!xcd_round_robin()) return fail(SABER_HIP_UNIMPL, "stage: this device does not place workgroup b on XCD b % 8");
+    return stage_build(chains, n, true, tail, out, head_a, head_b);
 }
 void saber_hip_conv2d_stage_destroy(saber_hip_chain_stage_t* st) { delete st; }
 int saber_hip_conv2d_stage_run(saber_hip_chain_stage_t* st, const void* x, const void* res, void* const* y1, void* const* y2, saber_hip_stream_t stream) {
@@ -369,6 +432,14 @@ int saber_hip_conv2d_stage_run_tail(saber_hip_chain_stage_t* st, const void* x, 
     for (size_t i = 0; i < st->chains.size(); ++i)
         if (!y1[i] || !y2[i]) return fail(SABER_HIP_INVALID_VALUE, "stage: an output pointer per block");
     return stage_run(st, x, res, y1, y2, (hipStream_t)stream, y_tail);
+}
+int saber_hip_conv2d_stage_run_head(saber_hip_chain_stage_t* st, const void* x_head, void* y_head_b, void* const* y1, void* const* y2, void* y_tail,
+                                    saber_hip_stream_t stream) {
+    if (g_capture) return capture_unsupported("saber_hip_conv2d_stage_run_head (saber_hip_net_optimize forms stages itself)");
+    if (!st || !x_head || !y_head_b || !y1 || !y2) return fail(SABER_HIP_INVALID_VALUE, "null argument");
+    for (size_t i = 0; i < st->chains.size(); ++i)
+        if (!y1[i] || !y2[i]) return fail(SABER_HIP_INVALID_VALUE, "stage: an output pointer per block");
+    return stage_run(st, x_head, nullptr, y1, y2, (hipStream_t)stream, y_tail, y_head_b);
 }
 // the weight stream of one layout, in the order the waves of the forms that read it consume it (conv1x1_chain.hip, conv_chain_coop.hip)
 static void pack_chain_stream(const saber_hip_chain* ch, ChainStream layout, std::vector<uint8_t>& out) {

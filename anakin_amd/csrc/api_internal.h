@@ -250,6 +250,11 @@ struct saber_hip_chain_stage {
     std::vector<saber_hip_chain*> chains;
     saber_hip_chain* tail = nullptr;      // the strided head behind the run (saber_hip_conv2d_stage_create_tail): d_blk[chains.size()] holds its constants
     DevBuf<uint8_t> d_tail_stream;        // ... and this its weight fragments (api_chain.hip: pack_coop4_stream without b)
+    // the sibling pair in front of the run (saber_hip_conv2d_stage_create_head; not owned): d_blk[0] holds its constants (the blocks' then start at d_blk[1]), these its
+    // weight fragments (api_chain.hip: pack_stage_head_stream) and the two convs' {scale, bias', comp}
+    const saber_hip_conv* head_a = nullptr;
+    const saber_hip_conv* head_b = nullptr;
+    DevBuf<uint8_t> d_head_stream, d_head_prm1, d_head_prm2;
     DevBuf<saber_mi355x::StageBlk> d_blk;
     DevBuf<unsigned long long> d_grp_ctr, d_img_ctr;
     DevBuf<uint8_t> d_xch;
@@ -403,6 +408,12 @@ struct NetOp {
     // only ever set together with use_stage. tail_mode: the head's own chain mode while the tail is off (net_set_chain_mode)
     bool use_tail = false;
     int tail_of = -1, tail_mode = 0;
+    // ... and with the sibling pair in front of the run as the launch's HEAD (the stage was created with one): the OP_CONV_PAIR op ops[-1]
+    // (head_of = the index of THIS op) carries `skip` while use_head is set and its first output - this op's chain3_res - is not written;
+    // only ever set together with use_stage, and never by switching the stage on. head_req: the pair's choice word asked for the head
+    // while the stage was off (set_choices runs in op order: the stage head's word comes next and consumes it)
+    bool use_head = false, head_req = false;
+    int head_of = -1;
     // the fused stem conv + pooling with the sibling pair that reads the pooled tensor (flag 512): THIS op is the stem conv, the next
     // op (the pair, `skip`) launches nothing; stem_y1 / stem_y2 are the pair's outputs and this op's own output edge is not written
     saber_hip_stem_pair* stem_pair = nullptr;
@@ -511,6 +522,7 @@ void net_set_chain_mode(saber_hip_net* net, int ia, int mode);      // api_net_o
 int net_chain_mode(const saber_hip_net* net, int ia);      // api_net_optimize.hip
 // the stage headed by ops[i0] (NetOp::stage) on / off: on forces every block's 3x3-led chain form and makes ops[i0] launch them all
 void net_set_stage(saber_hip_net* net, int i0, bool on);   // api_net_optimize.hip (on: with its tail, where it has one; off: both)
+void net_set_head(saber_hip_net* net, int i0, bool on);    // api_net_optimize.hip: the head of the stage headed by ops[i0]; stays off while the stage is off
 void net_set_tail(saber_hip_net* net, int i0, bool on);    // api_net_optimize.hip: the tail of the stage headed by ops[i0]; stays off while the stage is off
 // chain forms (api_chain.hip)
 ChainForm chain_form(const saber_hip_chain* ch, int code);      // the table: what `code` means for this chain, code 0 if nothing
@@ -526,4 +538,6 @@ void for_each_sep_form(const saber_hip_sep* sp, const std::function<void(int cod
 int sep_static_form(const saber_hip_sep* sp);      // the executor's static choice: a form code, or 0 = two launches
 void net_set_sep(saber_hip_net* net, int i, int code);      // api_net_optimize.hip: the site headed by ops[i] on (a valid form code) / off (0)
 // api_chain.hip; y_tail: the tail's output - the tail then runs inside the launch (a stage created with one), null: the blocks only
-int stage_run(saber_hip_chain_stage* st, const void* x, const void* res, void* const* y1, void* const* y2, hipStream_t s, void* y_tail = nullptr);
+// y_head: the second output of the stage's head - the pair then runs inside the launch (a stage created with one), x is the PAIR's input and res is not read
+int stage_run(saber_hip_chain_stage* st, const void* x, const void* res, void* const* y1, void* const* y2, hipStream_t s, void* y_tail = nullptr,
+              void* y_head = nullptr);

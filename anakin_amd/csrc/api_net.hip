@@ -18,7 +18,10 @@ int net_launch(saber_hip_net* net, const NetOp& o, hipStream_t s) {
                 y1[k] = T(ops[3 * k].chain3_y1);
                 y2[k] = T(ops[3 * k].chain3_y2);
             }
-            const int rc = stage_run(o.stage, T(o.in), T(o.chain3_res), y1, y2, s, o.use_tail ? T(ops[3 * o.stage_n].chain3_y1) : nullptr);
+            // (with the head the launch starts from the pair's input - the pair is the op in front - and writes this op's input itself)
+            void* const y_tail = o.use_tail ? T(ops[3 * o.stage_n].chain3_y1) : nullptr;
+            const int rc = o.use_head ? stage_run(o.stage, T(ops[-1].in), nullptr, y1, y2, s, y_tail, T(o.in))
+                                      : stage_run(o.stage, T(o.in), T(o.chain3_res), y1, y2, s, y_tail);
             if (rc == SABER_HIP_RUNTIME_ERROR) {      // an earlier launch of it timed out (conv_stage_coop.hip): block by block from now on
                 ++net->coop_fallbacks;
                 ++g_coop_fallbacks_total;
@@ -46,7 +49,7 @@ int net_launch(saber_hip_net* net, const NetOp& o, hipStream_t s) {
         if (o.conv->gpool) return saber_hip_conv2d_run_gpool(o.conv, T(o.in), T(o.out), T(o.in2), T(o.out2), s);
         return saber_hip_conv2d_run(o.conv, T(o.in), T(o.out), T(o.in2), ws, s);
     case OP_CONV_PAIR:
-        if (o.skip) return SABER_HIP_OK;      // written by the stem launch in front of it (flag 512)
+        if (o.skip) return SABER_HIP_OK;      // written by the stem launch in front of it (flag 512) or by the stage launch behind it (its head)
         return saber_hip_conv2d_run_pair(o.conv, T(o.in), T(o.out), T(o.out2), s);
     case OP_FC:
         if (o.out2 >= 0) return fc_run_softmax(o.fc, T(o.in), (float*)T(o.out), (float*)T(o.out2), ws, s, false);      // flag 4096
@@ -305,6 +308,7 @@ int saber_hip_net_compact_arena(saber_hip_net_t* net, const int* keep, int n_kee
     for (int i = 0; i < nops; ++i) {
         const NetOp& o = net->ops[i];
         if (o.stage) span(i, 3 * o.stage_n + (o.stage->tail ? 2 : 0));      // (with the strided head it may run as its tail)
+        if (o.stage && o.stage->head_a && i > 0) span(i - 1, 2);           // (... and with the pair in front as its head: the launch reads the pair's input)
         if (o.chain3) span(i, 3);
         if (o.chain) span(i, 2);
         if (o.stem_pair) span(i, 2);
@@ -677,6 +681,8 @@ int saber_hip_net_tensor_unwritten(const saber_hip_net_t* net, int id) {
     if (net->tensor_bytes[id] == 0) return 1;      // the edge was removed by saber_hip_net_optimize (it has no storage)
     for (const NetOp& o : net->ops)
         if (((o.chain3 && o.use_chain3) || o.stem_pair || (o.sep && o.use_sep)) && o.out == id) return 1;
+    for (const NetOp& o : net->ops)      // the first block's shortcut while the pair that makes it runs as the stage launch's head: it stays in LDS
+        if (o.stage && o.use_head && o.chain3_res == id) return 1;
     return 0;
 }
 // After a pass has COMPLETED (the caller has synchronised): did one of its cooperative launches - a stage launch, a two-workgroup

@@ -25,11 +25,17 @@ int saber_hip_net_get_choice(saber_hip_net_t* net, int index) {
     if (c && net->ops[index].sep) choice |= (3 << 28) | ((net->ops[index].use_sep ? net->ops[index].sep->form : 0) << 24);
     if (c && net->ops[index].stage && net->ops[index].use_stage) choice |= 1 << 30;      // this op launches its whole stage
     if (c && net->ops[index].stage && net->ops[index].use_tail) choice |= (int)0x80000000u;      // ... and the strided head behind it as the launch's tail
+    // bit 29 on a sibling-pair op (which never leads a chain: bits 24..29 mean nothing else there): the pair runs as the HEAD of the stage launch behind it
+    if (c && net->ops[index].head_of >= 0 && net->ops[net->ops[index].head_of].use_head) choice |= 1 << 29;
     return choice;
 }
 int saber_hip_net_stage_blocks(const saber_hip_net_t* net, int index) {
     if (!net || index < 0 || index >= (int)net->ops.size()) return 0;
     return net->ops[index].stage ? net->ops[index].stage_n : 0;
+}
+int saber_hip_net_stage_head(const saber_hip_net_t* net, int index) {
+    if (!net || index < 1 || index >= (int)net->ops.size() || !net->ops[index].stage) return -1;
+    return net->ops[index - 1].head_of == index ? index - 1 : -1;
 }
 int saber_hip_net_set_choice(saber_hip_net_t* net, int index, int choice) {
     saber_hip_conv* c = net_op_conv(net, index);
@@ -65,12 +71,23 @@ int saber_hip_net_set_choice(saber_hip_net_t* net, int index, int choice) {
     const bool in_stage = o.chain3 && o.skip && !o.stage;
     if (ch && ch == o.chain3) net_set_chain_mode(net, index + 1, (tn || in_stage) ? 2 : net_chain_mode(net, index + 1) == 2 ? 1 : net_chain_mode(net, index + 1));
     else if (ch) net_set_chain_mode(net, index, net_chain_mode(net, index) == 2 ? 2 : (tn ? 1 : 0));   // (also restores the names)
+    const bool stage_was = o.stage && o.use_stage;
     if (o.stage) net_set_stage(net, index, stage_on);      // (a stage head comes before its blocks: set_choices runs in op order)
     if (o.stage) net_set_tail(net, index, tail_on);
+    // the head: the pair's word (the op in front: it came first) decides. A stage that is on takes it at once; one that was off takes the request
+    // its own word finds here - and only then: a stage switched on by itself comes without its head
+    if (o.stage && stage_on && !stage_was) net_set_head(net, index, o.head_req);
+    if (o.stage) o.head_req = false;
+    if (o.head_of >= 0) {
+        const bool head_on = (chain_bits & 32) && !net->shared_device;
+        net->ops[o.head_of].head_req = head_on;
+        net_set_head(net, o.head_of, head_on);
+    }
     if (in_tail) net_set_tail(net, o.tail_of, true);
     if (o.skip) o.name = (o.chain3 && o.use_chain3) ? "conv:(in the stage launch)" : "conv:(in the chain launch)";
     if (o.skip && index > 0 && net->ops[index - 1].tail_of >= 0 && net->ops[net->ops[index - 1].tail_of].use_tail) o.name = "conv:(in the stage launch)";
     if (o.skip && o.kind == OP_CONV_PAIR) o.name = (index > 0 && net->ops[index - 1].stem_pair) ? "conv:(in the stem launch)" : "conv:(in the chain launch)";
+    if (o.skip && o.head_of >= 0 && net->ops[o.head_of].use_head) o.name = "conv:(in the stage launch)";
     if (o.stem_pair) o.name = stem_pair_name(o);
     if (o.sep) net_set_sep(net, index, sep_bits ? tn : (o.use_sep ? o.sep->form : 0));      // (a choice without the bits leaves the site as it is; the names follow)
     if (o.skip && index > 0 && net->ops[index - 1].sep && net->ops[index - 1].use_sep) o.name = "conv:(in the separable launch)";
@@ -253,16 +270,19 @@ int saber_hip_net_autotune(saber_hip_net_t* net, saber_hip_stream_t stream, int 
         if (rc) return rc;
     }
     // stages: the blocks' tuned launches one after the other against the one persistent launch; where the strided head behind the run can be
-    // the launch's tail, the head's ops are timed with them: blocks and head on their own | stage + head | stage with tail
+    // the launch's tail, the head's ops are timed with them: blocks and head on their own | stage + head | stage with tail. Where the sibling
+    // pair in front of the run can be the launch's head, the pair op is timed with every form, and the best stage form then runs once more
+    // with the head: pair + stage | stage with head
     for (size_t i = 0; i < net->ops.size(); ++i) {
         NetOp& H0 = net->ops[i];
         if (!H0.stage || net->shared_device) continue;
         const bool has_tail = H0.stage->tail != nullptr;
+        const bool has_head = saber_hip_net_stage_head(net, (int)i) >= 0;
         const int first = (int)i, last = first + 3 * H0.stage_n - 1 + (has_tail ? 2 : 0);
         hipStream_t s = (hipStream_t)stream;
         auto run_all = [&]() -> int {
             int rc = 0;
-            for (int k = first; k <= last; ++k) rc |= net_launch(net, net->ops[k], s);
+            for (int k = first - (has_head ? 1 : 0); k <= last; ++k) rc |= net_launch(net, net->ops[k], s);
             return rc;
         };
         auto timed = [&](float* t) { return time_enqueued(s, run_all, 20, t); };
@@ -287,6 +307,17 @@ int saber_hip_net_autotune(saber_hip_net_t* net, saber_hip_stream_t stream, int 
             if (*(volatile unsigned*)H0.stage->h_err) ok = false;      // (a launch that did not complete: the site falls back as a whole)
             else if (ok_t && wt < one) one = wt;
             else net_set_tail(net, first, false);
+        }
+        if (ok && one < sep && has_head) {
+            float wh = 0.f;
+            net_set_head(net, first, true);
+            const bool ok_h = timed(&wh) == SABER_HIP_OK && hipStreamSynchronize(s) == hipSuccess && !*(volatile unsigned*)H0.stage->h_err;
+            log_cand(H0.conv, H0.name.substr(5), ok_h ? wh : -1.f);
+            if (*(volatile unsigned*)H0.stage->h_err) ok = false;      // (a launch that did not complete: the site falls back as a whole)
+            // (kept only where it wins by more than 1 %: two cold medians of ONE form differ by up to about that - the log shows the same candidate
+            // at 23.08 and 23.28 us - and a tie keeps the pair's own launch, which needs no other workgroup's arrival)
+            else if (ok_h && wh < one * 0.99f) one = wh;
+            else net_set_head(net, first, false);
         }
         if (!ok || one >= sep) {
             *(volatile unsigned*)H0.stage->h_err = 0u;

@@ -30,7 +30,7 @@ static void net_name_chain(NetOp& A, NetOp& B) {
 // mode of the ops around A = ops[ia] (a 1x1 conv with the fused eltwise): 0 separate launches, 1 A + B chained (A.chain),
 // 2 the 3x3 conv ops[ia - 1] leads the launch (its chain3; with or without B)
 static std::string stage_name(const NetOp& H0) {
-    return "conv:stage_c" + std::to_string(H0.stage->c1) + "_" + std::to_string(H0.stage_n) + "x[conv3x3+chain1x1]_2x16" + (H0.stage->c1 == 256 ? "_coop4" : "") +
+    return std::string(H0.use_head ? "conv:[pair1x1]+stage_c" : "conv:stage_c") + std::to_string(H0.stage->c1) + "_" + std::to_string(H0.stage_n) + "x[conv3x3+chain1x1]_2x16" + (H0.stage->c1 == 256 ? "_coop4" : "") +
            (H0.use_tail ? "+[conv3x3/2+conv1x1]" : "");
 }
 void net_set_chain_mode(saber_hip_net* net, int ia, int mode) {
@@ -77,9 +77,23 @@ void net_set_tail(saber_hip_net* net, int i0, bool on) {
     if (on) net->ops[it + 1].name = "conv:(in the stage launch)";
     if (H0.use_stage) H0.name = stage_name(H0);
 }
+// The sibling pair in front of the stage headed by ops[i0] inside / outside the stage launch. Inside: the pair op launches nothing, the
+// stage head's launch reads the pair's input and writes the pair's second output (its own input); the first - the shortcut - is not written.
+void net_set_head(saber_hip_net* net, int i0, bool on) {
+    NetOp& H0 = net->ops[i0];
+    if (!H0.stage || !H0.stage->head_a || i0 < 1 || net->ops[i0 - 1].head_of != i0) return;
+    NetOp& P = net->ops[i0 - 1];
+    on = on && H0.use_stage;
+    if (on == H0.use_head) return;
+    H0.use_head = on;
+    P.skip = on;
+    P.name = on ? std::string("conv:(in the stage launch)") : std::string("conv:") + P.conv->algo_name;
+    if (H0.use_stage) H0.name = stage_name(H0);
+}
 void net_set_stage(saber_hip_net* net, int i0, bool on) {
     NetOp& H0 = net->ops[i0];
     if (!H0.stage) return;
+    if (!on) net_set_head(net, i0, false);      // (switching a stage ON never switches its head on: that takes the pair's own choice word)
     if (!on) net_set_tail(net, i0, false);
     for (int k = 0; k < H0.stage_n; ++k) {
         if (on || H0.use_stage) net_set_chain_mode(net, i0 + 3 * k + 1, 2);
@@ -503,12 +517,33 @@ int saber_hip_net_optimize(saber_hip_net_t* net, int flags) {
                     ops[jt].chain3->c1 == 256 && ops[jt].chain3->c3->d.stride_h == 2 && ops[jt].in == ops[pl].chain3_y2 &&
                     ops[jt].chain3_res == ops[pl].chain3_y1 && ops[jt].chain3_y1 >= 0)
                     tail = ops[jt].chain3;
-                if (tail && saber_hip_conv2d_stage_create_tail(run.data(), (int)run.size(), tail, &st) != SABER_HIP_OK) tail = nullptr;
-                if (tail || saber_hip_conv2d_stage_create(run.data(), (int)run.size(), &st) == SABER_HIP_OK) {
+                // the sibling pair directly in front of a C = 256 run (res4a_branch1 / res4a_branch2a) whose two outputs are the first block's
+                // shortcut and 3x3 input and have no other reader: the launch's head. The site is formed, the head stays OFF until the pair's
+                // choice word (bit 29), the autotuner or a selector asks for it.
+                const saber_hip_conv *head_a = nullptr, *head_b = nullptr;
+                if (i >= 1 && run[0]->c1 == 256 && ops[i - 1].kind == OP_CONV_PAIR && !ops[i - 1].skip && !ops[i - 1].lane && ops[i - 1].conv &&
+                    ops[i - 1].conv->pair_src_a && ops[i - 1].conv->pair_src_b && !(i >= 3 && ops[i - 3].chain3 && ops[i - 3].chain3->b2)) {
+                    const NetOp& P = ops[i - 1];
+                    const int t_res = ops[i].chain3_res, t_x = ops[i].in;
+                    auto readers = [&](int t) {
+                        int r = 0;
+                        for (const NetOp& o : ops) r += (o.in == t) + (o.in2 == t);
+                        return r;
+                    };
+                    const bool fwd = P.out == t_res && P.out2 == t_x, rev = P.out == t_x && P.out2 == t_res;
+                    if ((fwd || rev) && t_res != t_x && readers(t_res) == 1 && readers(t_x) == 1) {
+                        head_a = fwd ? P.conv->pair_src_a : P.conv->pair_src_b;
+                        head_b = fwd ? P.conv->pair_src_b : P.conv->pair_src_a;
+                    }
+                }
+                if (head_a && saber_hip_conv2d_stage_create_head(run.data(), (int)run.size(), tail, head_a, head_b, &st) != SABER_HIP_OK) head_a = head_b = nullptr;
+                if (!head_a && tail && saber_hip_conv2d_stage_create_tail(run.data(), (int)run.size(), tail, &st) != SABER_HIP_OK) tail = nullptr;
+                if (head_a || tail || saber_hip_conv2d_stage_create(run.data(), (int)run.size(), &st) == SABER_HIP_OK) {
                     net->owned_stages.push_back(st);
                     ops[i].stage = st;
                     ops[i].stage_n = (int)run.size();
                     if (tail) ops[jt].tail_of = (int)i;
+                    if (head_a) ops[i - 1].head_of = (int)i;
                     int before = 0;
                     for (size_t k = 0; k < run.size(); ++k) before += 3 - (ops[i + 3 * k].skip + ops[i + 3 * k + 1].skip + ops[i + 3 * k + 2].skip);
                     if (tail) before += 2 - (ops[jt].skip + ops[jt + 1].skip);

@@ -31,7 +31,7 @@
 
 namespace saber_mi355x {
 
-template <int MAXB, bool TAIL>
+template <int MAXB, bool TAIL, bool HEAD>
 __global__ __launch_bounds__(512) void conv_stage4_c256_kernel(const Stage4KArgs<MAXB> ka) {
     constexpr int C1 = 256, K1 = 1024, K2 = 256, NW = 8;
     constexpr int F0 = 18, F1 = 8, F2 = 8;                   // 1 KB weight fragments per wave and phase
@@ -143,12 +143,13 @@ __global__ __launch_bounds__(512) void conv_stage4_c256_kernel(const Stage4KArgs
     };
     const int nall = ka.nblk + (TAIL ? 1 : 0);                // blocks + the tail: what the last ordinary block prefetches and waits for
 
+    v4i fr[F0 + 2];
+    if constexpr (!HEAD) {
     // ---- entry: the first block's halo, shortcut tile and constants by DMA; its first 20 weight fragments ------------------------
     dma_halo(ka.x, false);
     lds_dma16((const char*)ka.res + (size_t)pt * K1 + q * K1Q + tc * 16, tile + wave * 64);
     dma_prm(ka.blk[0]);
     asm volatile("" ::: "memory");
-    v4i fr[F0 + 2];
     {
         const v4i* wsb = stream_of(ka.blk[0], FB);
 #pragma unroll
@@ -160,6 +161,132 @@ __global__ __launch_bounds__(512) void conv_stage4_c256_kernel(const Stage4KArgs
     wait_vm_older_than<F0 + 2>();                             // everything older than the fragments: this wave's DMA
     __builtin_amdgcn_s_barrier();
     SABER_TL(1);
+    } else {
+        // ================= head: the sibling pair in front of the run (res4a_branch1: 1x1, 512 -> 1024, s8 = block 0's shortcut; res4a_branch2a:
+        // 1x1, 512 -> 256 = block 0's 3x3 input) on this tile's 32 pixels, INSTEAD of the three entry loads. ka.x is the pair's input
+        // [N][H][W][512], ka.head_y the second conv's own output tensor, blk[-1] the pair's constants (prm1 / prm2: the two convs', in_u8:
+        // their input, relu1 | relu2 / out_u8_2: their epilogues) and its stream of 16 + 4 fragments per (quarter, wave). The shortcut tile
+        // never leaves LDS (phase A writes `tile` where block 0's phase 1 reads it); the 3x3 input reaches the neighbours the way every block's
+        // y2 does: the head is block "-1" of the edge protocol below.
+        constexpr int C0 = 512, CH0 = C0 / 16, XPC = CH0 + 1;          // the pair's input channels; LDS pitch (chunks) of a pixel: 32 + 1 padding
+        constexpr int XCH = (32 * XPC + 63) / 64 * 64;
+        constexpr int FA = 2 * (C0 / 64), FH = (C0 / 64) / 2;          // fragments per wave: 16 (2 accumulators x 8 k-steps) + 4 (half of K)
+        static_assert(XCH <= YCH && FA + FH == F0 + 2, "the head's tile fits ptile, its fragments the entry registers");
+        const StageBlk Bh = ka.blk[-1];
+        v4i* const xt = ptile;                                        // (idle until block 0's phase 2)
+        for (int i = wave; i < XCH / 64; i += NW) {
+            const int L = i * 64 + lane;
+            const int px = L / XPC, cc = L - px * XPC;
+            bool okp;
+            const int pp_ = pix(px & 31, okp);
+            const char* src = (px < 32 && cc < CH0) ? (const char*)ka.x + ((size_t)pp_ * C0 + cc * 16) : (const char*)ka.zero;
+            lds_dma16(src, xt + i * 64);
+        }
+        dma_prm(Bh);
+        asm volatile("" ::: "memory");
+        {
+            const v4i* wsb = stream_of(Bh, FA + FH);
+#pragma unroll
+            for (int r = 0; r < FA + FH; ++r) {
+                fr[r] = wsb[r * 64];
+                asm volatile("" ::: "memory");                   // issue order = consumption order
+            }
+        }
+        wait_vm_older_than<FA + FH>();                            // everything older than the fragments: this wave's DMA
+        __builtin_amdgcn_s_barrier();
+        SABER_TL(12);
+        const v4i z = {0, 0, 0, 0};
+        const int xmask = Bh.in_u8 ? (int)0x80808080u : 0;
+        // ---- phase A: the shortcut conv, 32 channels per wave and both tile rows per fragment -> `tile` (s8, phase 1's swizzle) ----
+        {
+            const int cg = wave * 32 + fq * 8;               // within this quarter: 8 consecutive channels of pixel (row, frow)
+            const v4i* pp = prm1 + (cg / 4) * 3;
+            v4i acc[2][2];
+#pragma unroll
+            for (int m = 0; m < 2; ++m)
+#pragma unroll
+                for (int mf = 0; mf < 2; ++mf) acc[m][mf] = pp[mf * 3 + 2];
+#pragma unroll
+            for (int ks = 0; ks < C0 / 64; ++ks)
+#pragma unroll
+                for (int m = 0; m < 2; ++m) {
+                    v4i bo = xt[(m * 16 + frow) * XPC + ks * 4 + fq];
+                    bo.x ^= xmask; bo.y ^= xmask; bo.z ^= xmask; bo.w ^= xmask;
+                    acc[m][0] = mma_step(fr[ks * 2], bo, acc[m][0]);
+                    acc[m][1] = mma_step(fr[ks * 2 + 1], bo, acc[m][1]);
+                }
+            const float lo1 = Bh.relu1 ? 0.f : -3.0e38f;
+#pragma unroll
+            for (int m = 0; m < 2; ++m) {
+                c2i o;
+                o.x = (int)chain_out_pack(acc[m][0], z, __builtin_bit_cast(v4f, pp[1]), __builtin_bit_cast(v4f, pp[0]), lo1, 128.f, 0x80808080u);
+                o.y = (int)chain_out_pack(acc[m][1], z, __builtin_bit_cast(v4f, pp[4]), __builtin_bit_cast(v4f, pp[3]), lo1, 128.f, 0x80808080u);
+                *(c2i*)((char*)tile + ((m * 16 + frow) * CPRW + ((cg / 16) ^ frow)) * 16 + (fq & 1) * 8) = o;
+            }
+        }
+        SABER_TL(13);
+        // block 0's first 20 fragments where a block requests its successor's: 16 behind phase A, the registers phase B reads behind it
+        const v4i* const ws0 = stream_of(ka.blk[0], FB);
+#pragma unroll
+        for (int r = 0; r < FA; ++r) {
+            fr[r] = ws0[r * 64];
+            asm volatile("" ::: "memory");
+        }
+        // ---- phase B: the 3x3 input's conv, 16 channels x half of K per wave; halves summed in LDS -> its own output tensor ----
+        {
+            const int c2 = nt * 16 + fq * 4;                 // within this quarter
+            const v4i* pp = prm2 + (c2 / 4) * 3;
+            v4i acc0 = kh ? z : pp[2], acc1 = acc0;
+#pragma unroll
+            for (int j = 0; j < FH; ++j) {
+                v4i b0 = xt[frow * XPC + (kh * FH + j) * 4 + fq];
+                v4i b1 = xt[(16 + frow) * XPC + (kh * FH + j) * 4 + fq];
+                b0.x ^= xmask; b0.y ^= xmask; b0.z ^= xmask; b0.w ^= xmask;
+                b1.x ^= xmask; b1.y ^= xmask; b1.z ^= xmask; b1.w ^= xmask;
+                acc0 = mma_step(fr[FA + j], b0, acc0);
+                acc1 = mma_step(fr[FA + j], b1, acc1);
+            }
+#pragma unroll
+            for (int r = FA; r < FA + FH; ++r) {
+                fr[r] = ws0[r * 64];
+                asm volatile("" ::: "memory");
+            }
+            if (kh) {
+                red[(nt * 2 + 0) * 64 + lane] = acc0;
+                red[(nt * 2 + 1) * 64 + lane] = acc1;
+            }
+            asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+            __builtin_amdgcn_s_barrier();
+            if (!kh) {
+                const v4i r0 = red[(nt * 2 + 0) * 64 + lane], r1 = red[(nt * 2 + 1) * 64 + lane];
+                acc0.x += r0.x; acc0.y += r0.y; acc0.z += r0.z; acc0.w += r0.w;
+                acc1.x += r1.x; acc1.y += r1.y; acc1.z += r1.z; acc1.w += r1.w;
+                const float lo2 = Bh.relu2 ? 0.f : -3.0e38f;
+                const float off2 = Bh.out_u8_2 ? 0.f : 128.f;
+                const unsigned xm2 = Bh.out_u8_2 ? 0u : 0x80808080u;
+                const unsigned o0 = chain_out_pack(acc0, z, __builtin_bit_cast(v4f, pp[1]), __builtin_bit_cast(v4f, pp[0]), lo2, off2, xm2);
+                const unsigned o1 = chain_out_pack(acc1, z, __builtin_bit_cast(v4f, pp[1]), __builtin_bit_cast(v4f, pp[0]), lo2, off2, xm2);
+                if (ok0) *(unsigned*)((char*)ka.head_y + (size_t)p0 * K2 + q * K2Q + c2) = o0;
+                if (ok1) *(unsigned*)((char*)ka.head_y + (size_t)p1 * K2 + q * K2Q + c2) = o1;
+            }
+        }
+        SABER_TL(14);
+        // ---- the hand-over between two blocks (below), with the head as block -1: it arrives on the parity word block 1 uses ----
+        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+        __builtin_amdgcn_s_barrier();                                // (every wave is also done with the head's constants and input tile)
+        unsigned long long* const e_h = e_up + 1;
+        if (wave == 0 && lane == 0) {
+            (void)__hip_atomic_fetch_add(e_h, 1ull, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+            (void)__hip_atomic_fetch_add(e_h + 16, 1ull, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+        }
+        dma_prm(ka.blk[0]);
+        if (wave == 0) coop_wait_mask2(e_h, ty > 0 ? 7ull : 3ull, e_h + 16, ty + 1 < ka.tiles_per_img ? 7ull : 3ull, ka.err);
+        __builtin_amdgcn_s_barrier();
+        dma_halo(ka.head_y, true);
+        wait_vm_older_than<0>();
+        __builtin_amdgcn_s_barrier();
+        SABER_TL(1);
+    }
 
     StageBlk B = ka.blk[0];                                  // (by value: scalar registers for the whole block)
     for (int k = 0; k < ka.nblk; ++k) {
@@ -355,6 +482,10 @@ __global__ __launch_bounds__(512) void conv_stage4_c256_kernel(const Stage4KArgs
             // apart - could re-arrive at a shared edge before this row had sampled it at its multiple of 8, and the mask test would never pass
             // (round-4 advisor finding). A row cannot reach block k + 2's arrival before its neighbour has PASSED block k's wait (its block
             // k + 1 needs the neighbour's block-k + 1 rows), so the word of block k's parity stays at its multiple until everybody has seen it.
+            // With a head (HEAD) there is one more instance in front: block "-1", on the word of odd blocks. The argument is the same one step
+            // earlier: a row reaches block 1's arrival - the next on that word - only after its block 1, which needs the neighbour's block-0 rows,
+            // and the neighbour arrives with those only after it has PASSED the head's wait. Every instance still adds 8 (4 at the image's
+            // top and bottom edge) to its word, with or without a head or a tail: the counters stay never-reset.
             unsigned long long* const e_k = e_up + (k & 1);
             if (wave == 0 && lane == 0) {
                 (void)__hip_atomic_fetch_add(e_k, 1ull, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
@@ -731,19 +862,23 @@ static hipError_t launch_stage1(const Stage4KArgs<MAXB>& ka, hipStream_t s) {
 hipError_t launch_conv_stage1_c128(const Stage4KArgs<STAGE4_SHORT>& a, hipStream_t s) { return launch_stage1(a, s); }
 hipError_t launch_conv_stage1_c128(const Stage4KArgs<STAGE4_LONG>& a, hipStream_t s) { return launch_stage1(a, s); }
 template <int MAXB>
-static hipError_t launch_stage4(const Stage4KArgs<MAXB>& ka, bool tail, hipStream_t s) {
+static hipError_t launch_stage4(const Stage4KArgs<MAXB>& ka, bool tail, bool head, hipStream_t s) {
     // tail: blk[nblk] holds the strided head's constants, y1[nblk] is its output (two blocks at least: an image per XCD, W <= 16)
     if (tail && (ka.nblk < 2 || ka.nblk + 1 > MAXB || !ka.y1[ka.nblk])) return hipErrorInvalidValue;
+    // head: blk[-1] holds the sibling pair's constants, x is ITS input, head_y its second output (an image per XCD: the edge counters)
+    if (head && (!ka.per_image || !ka.img_ctr || ka.tiles_x != 1 || !ka.head_y)) return hipErrorInvalidValue;
     if (ka.nblk <= 0 || ka.nblk > MAXB || ka.N <= 0 || !ka.blk || !ka.grp_ctr || !ka.xch || !ka.xcc ||
         (ka.nblk > 1 && (!ka.per_image || !ka.img_ctr || ka.tiles_x != 1)))
         return hipErrorInvalidValue;
     const int tiles = ka.N * ka.tiles_per_img;
     const dim3 grid(ka.per_image ? (ka.N + 7) / 8 * ka.tiles_per_img * 4 * 8 : (tiles + 7) / 8 * 32), block(512);
-    if (tail) hipLaunchKernelGGL((conv_stage4_c256_kernel<MAXB, true>), grid, block, 0, s, ka);
-    else hipLaunchKernelGGL((conv_stage4_c256_kernel<MAXB, false>), grid, block, 0, s, ka);
+    if (head && tail) hipLaunchKernelGGL((conv_stage4_c256_kernel<MAXB, true, true>), grid, block, 0, s, ka);
+    else if (head) hipLaunchKernelGGL((conv_stage4_c256_kernel<MAXB, false, true>), grid, block, 0, s, ka);
+    else if (tail) hipLaunchKernelGGL((conv_stage4_c256_kernel<MAXB, true, false>), grid, block, 0, s, ka);
+    else hipLaunchKernelGGL((conv_stage4_c256_kernel<MAXB, false, false>), grid, block, 0, s, ka);
     return hipGetLastError();
 }
-hipError_t launch_conv_stage4(const Stage4KArgs<STAGE4_SHORT>& a, bool tail, hipStream_t s) { return launch_stage4(a, tail, s); }
-hipError_t launch_conv_stage4(const Stage4KArgs<STAGE4_LONG>& a, bool tail, hipStream_t s) { return launch_stage4(a, tail, s); }
+hipError_t launch_conv_stage4(const Stage4KArgs<STAGE4_SHORT>& a, bool tail, bool head, hipStream_t s) { return launch_stage4(a, tail, head, s); }
+hipError_t launch_conv_stage4(const Stage4KArgs<STAGE4_LONG>& a, bool tail, bool head, hipStream_t s) { return launch_stage4(a, tail, head, s); }
 
 }  // namespace saber_mi355x

@@ -199,13 +199,18 @@ struct Stage4KArgs {
     int per_image;                     // 1: workgroup b -> image (b / 8 / wpi) * 8 + b % 8 (required for nblk > 1); 0: tiles round-robin
     void* y1[MAXB];                    // per block [M][1024] s8: the eltwise output (the operator's own output tensor)
     void* y2[MAXB];                    // per block [M][256] s8 / u8: the second 1x1 conv's output = the next block's 3x3 input
+    void* head_y;                      // with a head: the pair's second output [M][256] = the first block's 3x3 input (x is then the pair's input)
 };
 constexpr int STAGE4_SHORT = 8, STAGE4_LONG = 24;
 // tail: behind the nblk blocks the strided head that follows the stage in ResNet (conv 3x3 / stride 2 -> conv 1x1 + eltwise, shortcut = the
 // last block's y1 sub-sampled by 2) runs in the same launch: blk[nblk] = its constants (wstream: the 18 + 8 fragments of the first two convs
 // per (quarter, wave); prm2 unused but readable), y1[nblk] = its output [N][ceil(H/2)][ceil(W/2)][1024] s8. Needs nblk >= 2, nblk + 1 <= MAXB.
-hipError_t launch_conv_stage4(const Stage4KArgs<STAGE4_SHORT>& a, bool tail, hipStream_t s);
-hipError_t launch_conv_stage4(const Stage4KArgs<STAGE4_LONG>& a, bool tail, hipStream_t s);
+// head: in FRONT of the blocks the sibling pair of 1x1 convs that feeds the first block (res4a_branch1: 512 -> 1024, s8 = the shortcut;
+// res4a_branch2a: 512 -> 256 = the 3x3 input) runs in the same launch: x = the pair's input [N][H][W][512], res is not read and the shortcut
+// tensor not written (it stays in LDS), head_y = the second conv's output, blk[-1] = the pair's constants (wstream: 16 + 4 fragments
+// per (quarter, wave); prm1 / prm2 the two convs'; prm0 unused but readable; in_u8, relu1, relu2, out_u8_2). Needs an image per XCD.
+hipError_t launch_conv_stage4(const Stage4KArgs<STAGE4_SHORT>& a, bool tail, bool head, hipStream_t s);
+hipError_t launch_conv_stage4(const Stage4KArgs<STAGE4_LONG>& a, bool tail, bool head, hipStream_t s);
 // the res3 stage (C = 128): one workgroup per tile, an image per XCD, nblk >= 2; grp_ctr / xch unused; tiles_x in {1, 2, 4}
 hipError_t launch_conv_stage1_c128(const Stage4KArgs<STAGE4_SHORT>& a, hipStream_t s);
 hipError_t launch_conv_stage1_c128(const Stage4KArgs<STAGE4_LONG>& a, hipStream_t s);

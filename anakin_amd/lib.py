@@ -30,6 +30,7 @@ SYMBOLS = [
     "saber_hip_conv2d_chain_run3",
     "saber_hip_conv2d_chain_set_tile", "saber_hip_conv2d_chain_get_tile",
     "saber_hip_conv2d_stage_create", "saber_hip_conv2d_stage_destroy", "saber_hip_conv2d_stage_run", "saber_hip_conv2d_stage_create_tail", "saber_hip_conv2d_stage_run_tail",
+    "saber_hip_conv2d_stage_create_head", "saber_hip_conv2d_stage_run_head",
     "saber_hip_conv2d_stem_pair_create", "saber_hip_conv2d_stem_pair_destroy", "saber_hip_conv2d_stem_pair_run",
     "saber_hip_conv2d_sep_create", "saber_hip_conv2d_sep_run", "saber_hip_conv2d_sep_set_tile", "saber_hip_conv2d_sep_get_tile",
     "saber_hip_conv2d_sep_algo", "saber_hip_conv2d_sep_destroy",
@@ -42,7 +43,7 @@ SYMBOLS = [
     "saber_hip_transpose_nchw_to_nhwc_f32", "saber_hip_transpose_nhwc_to_nchw_f32",
     "saber_hip_quantize_flat_s8", "saber_hip_eltwise_sum_i8", "saber_hip_eltwise_sum_f32", "saber_hip_relu_f32", "saber_hip_activation_f32", "saber_hip_prelu_f32",
     "saber_hip_pool_out_dim", "saber_hip_pool_out_dim2", "saber_hip_pool2d_i8_nhwc", "saber_hip_pool2d_f32", "saber_hip_pool2d_f32_from_i8", "saber_hip_pool2d_f32_from_i8_q", "saber_hip_fc_run_q", "saber_hip_fc_run_softmax", "saber_hip_softmax_f32",
-    "saber_hip_net_add_pool_f32_from_i8_q", "saber_hip_net_add_fc_q", "saber_hip_net_optimize", "saber_hip_net_num_launches", "saber_hip_net_tensor_unwritten", "saber_hip_net_get_choice", "saber_hip_net_set_choice", "saber_hip_net_stage_blocks", "saber_hip_net_time_op_in_pass", "saber_hip_net_status", "saber_hip_net_inject_coop_error", "saber_hip_net_coop_fallbacks", "saber_hip_coop_fallbacks_total",
+    "saber_hip_net_add_pool_f32_from_i8_q", "saber_hip_net_add_fc_q", "saber_hip_net_optimize", "saber_hip_net_num_launches", "saber_hip_net_tensor_unwritten", "saber_hip_net_get_choice", "saber_hip_net_set_choice", "saber_hip_net_stage_blocks", "saber_hip_net_stage_head", "saber_hip_net_time_op_in_pass", "saber_hip_net_status", "saber_hip_net_inject_coop_error", "saber_hip_net_coop_fallbacks", "saber_hip_coop_fallbacks_total",
     "saber_hip_net_create", "saber_hip_net_add_tensor", "saber_hip_net_add_conv", "saber_hip_net_add_fc",
     "saber_hip_net_add_quantize", "saber_hip_net_add_dequantize", "saber_hip_net_add_transpose_in_f32", "saber_hip_net_add_eltwise_i8",
     "saber_hip_net_add_eltwise_f32", "saber_hip_net_add_pool_i8", "saber_hip_net_add_pool_f32",
@@ -136,6 +137,8 @@ def load():
     lib.saber_hip_conv2d_stage_run.argtypes = [P, P, P, C.POINTER(P), C.POINTER(P), P]
     lib.saber_hip_conv2d_stage_create_tail.argtypes = [C.POINTER(P), I, P, C.POINTER(P)]
     lib.saber_hip_conv2d_stage_run_tail.argtypes = [P, P, P, C.POINTER(P), C.POINTER(P), P, P]
+    lib.saber_hip_conv2d_stage_create_head.argtypes = [C.POINTER(P), I, P, P, P, C.POINTER(P)]
+    lib.saber_hip_conv2d_stage_run_head.argtypes = [P, P, P, C.POINTER(P), C.POINTER(P), P, P]
     lib.saber_hip_conv2d_stem_pair_create.argtypes = [P, P, P, C.POINTER(P)]
     lib.saber_hip_conv2d_stem_pair_destroy.argtypes = [P]
     lib.saber_hip_conv2d_stem_pair_destroy.restype = None
@@ -165,6 +168,7 @@ def load():
     lib.saber_hip_fc_destroy.argtypes = [P]
     lib.saber_hip_net_optimize.argtypes = [P, I]
     lib.saber_hip_net_stage_blocks.argtypes = [P, I]
+    lib.saber_hip_net_stage_head.argtypes = [P, I]
     lib.saber_hip_net_status.argtypes = [P]
     lib.saber_hip_net_inject_coop_error.argtypes = [P]
     lib.saber_hip_net_coop_fallbacks.argtypes = [P]

@@ -338,14 +338,21 @@ class SaberChainStage:
     chain i + 1 reads chain i's two outputs. dispatch(x, res, y1s, y2s): chain 0's inputs, every chain's two output tensors. The
     outputs hold the bits of dispatching the chains (= the operators, net.cpp:417-509) one after the other.
     tail: the strided head behind the run (SaberConvChain(a, None, conv3x3) with a stride-2 conv3x3 and a shortcut sub-sampled by 2;
-    saber_hip_conv2d_stage_create_tail); dispatch(..., y_tail) then runs it inside the launch, dispatch without y_tail the blocks only."""
+    saber_hip_conv2d_stage_create_tail); dispatch(..., y_tail) then runs it inside the launch, dispatch without y_tail the blocks only.
+    head: (a, b), the sibling pair in front of the run - two plain 1x1 SaberConv2D over one 512-channel tensor, a writing chain 0's shortcut
+    (1024 channels, s8) and b its 3x3 input (saber_hip_conv2d_stage_create_head); dispatch_head(x_head, y_head_b, y1s, y2s[, y_tail]) then
+    runs them inside the launch (a's output is not written), dispatch(...) the stage without them."""
 
-    def __init__(self, chains, tail=None):
+    def __init__(self, chains, tail=None, head=None):
         self.chains = list(chains)                   # keep them alive: the stage borrows their weights
         self.tail = tail
+        self.head = head
         arr = (C.c_void_p * len(chains))(*[c.h for c in chains])
         self.h = C.c_void_p()
-        if tail is None:
+        if head is not None:
+            L.check(L.load().saber_hip_conv2d_stage_create_head(arr, len(chains), tail.h if tail is not None else None, head[0].h, head[1].h,
+                                                                C.byref(self.h)))
+        elif tail is None:
             L.check(L.load().saber_hip_conv2d_stage_create(arr, len(chains), C.byref(self.h)))
         else:
             L.check(L.load().saber_hip_conv2d_stage_create_tail(arr, len(chains), tail.h, C.byref(self.h)))
@@ -358,6 +365,12 @@ class SaberChainStage:
             L.check(L.load().saber_hip_conv2d_stage_run(self.h, _p(x), _p(res), a, b, _stream()))
         else:
             L.check(L.load().saber_hip_conv2d_stage_run_tail(self.h, _p(x), _p(res), a, b, _p(y_tail), _stream()))
+
+    def dispatch_head(self, x_head, y_head_b, y1s, y2s, y_tail=None):
+        n = len(self.chains)
+        a = (C.c_void_p * n)(*[t.data_ptr() for t in y1s])
+        b = (C.c_void_p * n)(*[t.data_ptr() for t in y2s])
+        L.check(L.load().saber_hip_conv2d_stage_run_head(self.h, _p(x_head), _p(y_head_b), a, b, _p(y_tail) if y_tail is not None else None, _stream()))
 
     def __del__(self):
         try:
@@ -890,6 +903,29 @@ class Net:
             if sel:
                 v = ((ch[i] | (1 << 31)) if on else (ch[i] & ~(1 << 31))) & 0xffffffff
                 ch[i] = v - (1 << 32) if v >> 31 else v
+        self.set_choices(ch)
+
+    def heads(self):
+        """[(op index of the sibling pair, op index of the stage head)] of the stages that currently run the pair in front of them as the
+        launch's head (bit 29 of the PAIR op's choice word; conv_stage_coop.hip)"""
+        lib = L.load()
+        ch = self.choices()
+        out = []
+        for i, _, on in self.stages():
+            p = int(lib.saber_hip_net_stage_head(self.h, i))
+            if on and p >= 0 and (ch[p] >> 29) & 1:
+                out.append((p, i))
+        return out
+
+    def select_heads(self, on):
+        """the head of every selected stage that has one on / off (what saber_hip_net_autotune decides by timing). Switching a stage off
+        switches its head off; switching one on (select_stages) does not switch its head on."""
+        lib = L.load()
+        ch = self.choices()
+        for i, _, sel in self.stages():
+            p = int(lib.saber_hip_net_stage_head(self.h, i))
+            if sel and p >= 0:
+                ch[p] = (ch[p] | (1 << 29)) if on else (ch[p] & ~(1 << 29))
         self.set_choices(ch)
 
     def time_ops(self, iters=20):

@@ -259,6 +259,17 @@ int saber_hip_conv2d_stage_create_tail(saber_hip_chain_t* const* chains, int n, 
 int saber_hip_conv2d_stage_run_tail(saber_hip_chain_stage_t* stage, const void* x, const void* res, void* const* y1, void* const* y2,
                                     void* y_tail, saber_hip_stream_t stream);
 
+/* ... with a HEAD: the sibling pair in front of the run in ResNet (res4a_branch1 / res4a_branch2a) = two plain 1x1 / stride 1 / pad 0 INT8
+ * convs over ONE tensor of 512 channels, head_a writing the first block's shortcut (1024 channels, s8) and head_b its 3x3 input (256 channels,
+ * the dtype that conv reads). _run_head runs them inside the same launch: x_head is the pair's input, y_head_b head_b's own output tensor
+ * (written with the bits of saber_hip_conv2d_run on head_b); head_a's output stays on the CU and is NOT written. tail / y_tail as above, or
+ * NULL. _stage_run / _run_tail on such a stage run it without the head. Needs an image per XCD; anything else about the head is refused
+ * with SABER_HIP_INVALID_VALUE and a message of its own. The convs are not owned. */
+int saber_hip_conv2d_stage_create_head(saber_hip_chain_t* const* chains, int n, saber_hip_chain_t* tail, const saber_hip_conv_t* head_a,
+                                       const saber_hip_conv_t* head_b, saber_hip_chain_stage_t** out);
+int saber_hip_conv2d_stage_run_head(saber_hip_chain_stage_t* stage, const void* x_head, void* y_head_b, void* const* y1, void* const* y2,
+                                    void* y_tail, saber_hip_stream_t stream);
+
 /* The ResNet stem with its first two consumers in ONE launch: `stem` (an INT8 conv with saber_hip_conv2d_set_pooling's fused 3x3 /
  * stride-2 max pooling, 64 output channels: SaberConv2DPooling<AK_INT8>, saber_conv_pooling.cpp:60-160) followed, on the workgroup's
  * pooled pixels, by the two 1x1 / stride-1 INT8 convs `a` and `b` that read the pooled tensor (res2a's branch1 and branch2a; 64 -> k,
@@ -549,6 +560,9 @@ int saber_hip_net_inject_coop_error(saber_hip_net_t* net);
 /* > 0: op `index` heads a stage of that many blocks (flag 256); bit 30 of its saber_hip_net_get_choice / _set_choice value says
  * whether the stage launch is selected */
 int saber_hip_net_stage_blocks(const saber_hip_net_t* net, int index);
+/* the index of the sibling-pair op that can run as the HEAD of the stage headed by op `index` (always index - 1), or -1. Whether it does is
+ * bit 29 of THAT op's choice word (saber_hip_net_get_choice / set_choice); a stage that is off has its head off. */
+int saber_hip_net_stage_head(const saber_hip_net_t* net, int index);
 /* kernel launches of one forward pass (ops minus the ones absorbed into a chain launch) */
 int saber_hip_net_num_launches(const saber_hip_net_t* net);
 /* 1 when tensor `id` is never written: the output edge of a 3x3 conv currently running inside a conv3x3 + chain launch, or an

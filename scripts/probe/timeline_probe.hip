@@ -168,7 +168,7 @@ int main(int argc, char** argv) {
             // 3 past wait 1, 4 1x1 + eltwise done, y1 stored, arrival 2, 5 past wait 2, 6 y2 stored, 7 past the last image barrier +
             // the next halo landed
             const int tiles4 = n * ((hw + 1) / 2);
-            std::vector<StageBlk> hb(5);
+            std::vector<StageBlk> hb(6);      // [0]: the head's constants (blk[-1] of a launch with a head), [1..5]: the blocks'
             for (auto& B : hb) {
                 memset(&B, 0, sizeof B);
                 B.wstream = a.wstream; B.prm0 = a.prm0; B.prm1 = a.prm1; B.prm2 = a.prm2;
@@ -176,11 +176,11 @@ int main(int argc, char** argv) {
                 B.in0_u8 = 1; B.relu0 = 1; B.in_u8 = 1; B.relu1 = 0; B.res_relu = 1; B.relu2 = 1; B.out_u8_2 = 1;
             }
             StageBlk* dblk;
-            CK(hipMalloc((void**)&dblk, sizeof(StageBlk) * 5));
-            CK(hipMemcpy(dblk, hb.data(), sizeof(StageBlk) * 5, hipMemcpyHostToDevice));
+            CK(hipMalloc((void**)&dblk, sizeof(StageBlk) * 6));
+            CK(hipMemcpy(dblk, hb.data(), sizeof(StageBlk) * 6, hipMemcpyHostToDevice));
             Stage4KArgs<STAGE4_SHORT> sk;
             memset(&sk, 0, sizeof sk);
-            sk.x = a.x; sk.res = a.res; sk.zero = zero; sk.blk = dblk;
+            sk.x = a.x; sk.res = a.res; sk.zero = zero; sk.blk = dblk + 1;
             sk.grp_ctr = (unsigned long long*)dalloc((size_t)tiles4 * 32 * 8, 0);
             sk.img_ctr = (unsigned long long*)dalloc((size_t)n * ((hw + 1) / 2 + 1) * 16 * 8, 0);
             sk.xch = dalloc((size_t)tiles4 * 32 * c, 0);
@@ -194,13 +194,19 @@ int main(int argc, char** argv) {
             }
             sk.nblk = 1; sk.per_image = 0;
             snprintf(nm, sizeof nm, "stage4 C=256 14x14 b%d 1 block, tiles over XCDs", n);
-            run(P, nm, (tiles4 + 7) / 8 * 32, 8, [&] { launch_conv_stage4(sk, P.st); });
+            run(P, nm, (tiles4 + 7) / 8 * 32, 8, [&] { launch_conv_stage4(sk, false, false, P.st); });
             sk.per_image = 1;
             snprintf(nm, sizeof nm, "stage4 C=256 14x14 b%d 1 block, image per XCD", n);
-            run(P, nm, (n + 7) / 8 * sk.tiles_per_img * 32, 8, [&] { launch_conv_stage4(sk, P.st); });
+            run(P, nm, (n + 7) / 8 * sk.tiles_per_img * 32, 8, [&] { launch_conv_stage4(sk, false, false, P.st); });
             sk.nblk = 5;
             snprintf(nm, sizeof nm, "stage4 C=256 14x14 b%d 5 blocks, image per XCD", n);
-            run(P, nm, (n + 7) / 8 * sk.tiles_per_img * 32, 8, [&] { launch_conv_stage4(sk, P.st); });
+            run(P, nm, (n + 7) / 8 * sk.tiles_per_img * 32, 8, [&] { launch_conv_stage4(sk, false, false, P.st); });
+            // ... and with the sibling pair in front (1x1, 512 -> 1024 | 256) as the launch's head: 12 the pair's input tile, constants and 20
+            // fragments landed, 13 the 16-fragment phase (the shortcut tile) done, 14 the 4-fragment phase done and its output stored,
+            // 1 past the edge barrier + block 0's halo landed; 2..7 as above (of the last block)
+            sk.x = dalloc((size_t)M * 512, 1); sk.res = nullptr; sk.head_y = dalloc((size_t)M * c, 0);
+            snprintf(nm, sizeof nm, "stage4 C=256 14x14 b%d 5 blocks + head, image per XCD", n);
+            run(P, nm, (n + 7) / 8 * sk.tiles_per_img * 32, 15, [&] { launch_conv_stage4(sk, false, true, P.st); });
             unsigned errs = 0;
             CK(hipMemcpy(&errs, ck.coop_err, 4, hipMemcpyDeviceToHost));
             printf("    coop error word: %u\n", errs);
