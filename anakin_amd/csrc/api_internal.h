@@ -381,48 +381,61 @@ struct ColdScope {
 // op-list executor
 namespace saber_api {
 enum OpKind { OP_CONV, OP_CONV_PAIR, OP_FC, OP_QUANT, OP_DEQUANT, OP_TRANSPOSE_IN, OP_ELT_I8, OP_ELT_F32, OP_POOL_I8, OP_POOL_F32, OP_POOL_F32_I8, OP_FC_Q, OP_SOFTMAX, OP_RELU_F32, OP_ACT_F32 };
+// What an op launches in the current selection: DERIVED from the sites' decisions by net_resolve (api_net_optimize.hip), never set elsewhere
+enum Launch { LAUNCH_NONE, LAUNCH_OWN, LAUNCH_CHAIN, LAUNCH_CHAIN3, LAUNCH_STAGE, LAUNCH_STEM_PAIR, LAUNCH_SEP };
+// A SITE is a group of adjacent ops that can run as one launch. The op that heads a site holds the site's object and its DECISION (*_on: stored
+// as asked by the net_set_* setters and read back by saber_hip_net_get_choice; a decision is never changed to express what another site
+// does); what every op launches, which ops launch nothing and every conv / pair / fc / softmax op's name follow from the decisions in
+// net_resolve alone.
 struct NetOp {
     OpKind kind;
     std::string name;
     saber_hip_conv* conv = nullptr;
     saber_hip_fc* fc = nullptr;
     int in = -1, in2 = -1, out = -1, out2 = -1;
+    // derived (net_resolve): this op's launch; LAUNCH_NONE = `skip`: ops[absorbed_by]'s launch covers it
+    Launch launch = LAUNCH_OWN;
+    int absorbed_by = -1;
+    bool skip = false;
+    std::string res_note;      // "+res/<stride>" behind the name of a conv that reads its residual strided (flag 64), until a selection is applied to the op
     // conv1x1 chain (saber_hip_net_optimize flag 16): this conv and the NEXT op (a 1x1 conv reading its output) run as one
-    // launch while use_chain is set; the next op carries `skip` and launches nothing
+    // launch while chain_on is set
     saber_hip_chain* chain = nullptr;
     int chain_out = -1;
-    bool use_chain = false, skip = false;
-    // ... with the block's 3x3 conv in front (flag 32): THIS op is that 3x3 conv, the next two are the chain; while use_chain3
-    // is set it launches all three (its own output edge is then not written) and both followers carry `skip`
+    bool chain_on = false;
+    // ... with the block's 3x3 conv in front (flag 32): THIS op is that 3x3 conv, the next two are the chain; while led_on
+    // is set it launches all three (its own output edge is then not written)
     saber_hip_chain* chain3 = nullptr;
     int chain3_res = -1, chain3_y1 = -1, chain3_y2 = -1;
-    int chain3_y3 = -1;      // strided head + sibling pair (flag 1024): the pair's second output; the pair op (ops[i + 2]) carries `skip`
-    bool use_chain3 = false;
-    // ... and a RUN of such 3x3-led C = 256 chains (flag 256): THIS op is the first block's 3x3 conv; while use_stage is set it launches
-    // all stage_n chains (3 * stage_n ops, the others carry `skip`) as one persistent launch (saber_hip_conv2d_stage_run)
+    int chain3_y3 = -1;      // strided head + sibling pair (flag 1024): the pair's second output; the launch covers the pair op (ops[i + 2]) too
+    bool led_on = false;
+    // ... and a RUN of such 3x3-led C = 256 chains (flag 256): THIS op is the first block's 3x3 conv; while stage_on is set it launches
+    // all stage_n chains (3 * stage_n ops) as one persistent launch (saber_hip_conv2d_stage_run)
     saber_hip_chain_stage* stage = nullptr;
     int stage_n = 0;
-    bool use_stage = false;
+    bool stage_on = false;
+    // (names only: a stage that goes off leaves its blocks' 3x3 convs under the names they had inside the launch until a word or a chain mode
+    // of their own arrives - what the executor has always reported after a fallback; kept so that every op name stays what it was)
+    bool stage_name_kept = false;
     // ... with the strided head behind the run as the launch's TAIL (the stage was created with one): the two ops behind the last block -
-    // ops[3 * stage_n] (its 3x3 conv, tail_of = the index of THIS op) and the 1x1 conv behind it - carry `skip` while use_tail is set;
-    // only ever set together with use_stage. tail_mode: the head's own chain mode while the tail is off (net_set_chain_mode)
-    bool use_tail = false;
-    int tail_of = -1, tail_mode = 0;
+    // ops[3 * stage_n] (its 3x3 conv, tail_of = the index of THIS op) and the 1x1 conv behind it - are covered while tail_on is set and
+    // the stage is on; the strided head's own led_on stays underneath
+    bool tail_on = false;
+    int tail_of = -1;
     // ... and with the sibling pair in front of the run as the launch's HEAD (the stage was created with one): the OP_CONV_PAIR op ops[-1]
-    // (head_of = the index of THIS op) carries `skip` while use_head is set and its first output - this op's chain3_res - is not written;
-    // only ever set together with use_stage, and never by switching the stage on. head_req: the pair's choice word asked for the head
-    // while the stage was off (set_choices runs in op order: the stage head's word comes next and consumes it)
-    bool use_head = false, head_req = false;
+    // (head_of = the index of THIS op) is covered while head_on is set and the stage is on; its first output - this op's chain3_res - is
+    // then not written. Switching the stage on never sets it; switching the stage off clears it
+    bool head_on = false;
     int head_of = -1;
-    // the fused stem conv + pooling with the sibling pair that reads the pooled tensor (flag 512): THIS op is the stem conv, the next
-    // op (the pair, `skip`) launches nothing; stem_y1 / stem_y2 are the pair's outputs and this op's own output edge is not written
+    // the fused stem conv + pooling with the sibling pair that reads the pooled tensor (flag 512): THIS op is the stem conv and always covers
+    // the next op (the pair); stem_y1 / stem_y2 are the pair's outputs and this op's own output edge is not written
     saber_hip_stem_pair* stem_pair = nullptr;
     int stem_y1 = -1, stem_y2 = -1;
-    // a depthwise 3x3 conv and the 1x1 conv behind it (flag 16384, SABER_HIP_NET_SEPARABLE): THIS op is the depthwise conv, the next op is the
-    // pointwise one and carries `skip` while use_sep is set; this op's own output edge is then not written, sep_out is the pointwise output
+    // a depthwise 3x3 conv and the 1x1 conv behind it (flag 16384, SABER_HIP_NET_SEPARABLE): THIS op is the depthwise conv; while sep_on is
+    // set its launch covers the pointwise op behind it, this op's own output edge is not written and sep_out is the pointwise output
     saber_hip_sep* sep = nullptr;
     int sep_out = -1;
-    bool use_sep = false;
+    bool sep_on = false;
     int lane = 0;            // 0: caller's stream, 1: the net's side stream (graph::Lane, operator_func.h:103-114)
     bool record = false;     // an op on the other lane consumes this op's output: record an event after it
     int p[16] = {0};
@@ -502,7 +515,6 @@ bool b3_tile_ok(const saber_hip_conv* op, int tile, int ks);
 int dw_static_form(const saber_hip_conv* op);      // api_conv.hip: create's choice among the depthwise forms
 int group_static_form(const saber_hip_conv* op);      // api_conv.hip: create's choice among the direct kernel (0) and the grouped 3x3 forms
 constexpr long DW_STRIP_MIN_LANES = 150000;     // (lanes = channel vectors x output pixels. Measured, profiles/dw3x3/README.md: at 200 704 lanes and above the strip form is the faster one for both element types, at 100 352 and below the one-pixel form)
-std::string stem_pair_name(const saber_api::NetOp& o);      // api_net_optimize.hip
 void conv_fill_args(const saber_hip_conv* op, saber_mi355x::ConvKArgs& a, const void* x, void* y, const void* res);   // api_conv.hip
 int stem_pool_args(const saber_hip_conv* op, const void* x, void* y, void* workspace, hipStream_t s, saber_mi355x::ConvKArgs* a);   // api_conv.hip
 bool xcd_round_robin();      // api_conv.hip: workgroups 8 apart in a 1-D grid share an XCD on the current device (probed once)
@@ -518,12 +530,16 @@ int net_launch(saber_hip_net* net, const NetOp& o, hipStream_t s);      // api_n
 bool fc_softmax_ok(const saber_hip_fc* fc, bool quantised_input = false);      // api_ops.hip: the INT8 small-batch fc kernel can normalise its own logits (fc_small.hip)
 int fc_run_softmax(saber_hip_fc* fc, const void* x, float* y, float* prob, void* workspace, hipStream_t s, bool quantised_input);
 int fc_softmax_prepare(saber_hip_fc* fc);        // ... allocates the arrival counter (not under stream capture)
-void net_set_chain_mode(saber_hip_net* net, int ia, int mode);      // api_net_optimize.hip
-int net_chain_mode(const saber_hip_net* net, int ia);      // api_net_optimize.hip
-// the stage headed by ops[i0] (NetOp::stage) on / off: on forces every block's 3x3-led chain form and makes ops[i0] launch them all
-void net_set_stage(saber_hip_net* net, int i0, bool on);   // api_net_optimize.hip (on: with its tail, where it has one; off: both)
-void net_set_head(saber_hip_net* net, int i0, bool on);    // api_net_optimize.hip: the head of the stage headed by ops[i0]; stays off while the stage is off
-void net_set_tail(saber_hip_net* net, int i0, bool on);    // api_net_optimize.hip: the tail of the stage headed by ops[i0]; stays off while the stage is off
+// sites (api_net_optimize.hip): each setter stores decisions and calls net_resolve, the one place that derives launch / absorbed_by / skip and the names
+void net_resolve(saber_hip_net* net);
+void net_drop_graph(saber_hip_net* net);      // api_net.hip: a captured hipGraph holds the old selection / addresses
+// the ops around A = ops[ia] (a 1x1 conv with the fused eltwise): 0 separate launches, 1 A + the next op chained, 2 the 3x3 conv ops[ia - 1] leads the launch
+void net_set_chain_mode(saber_hip_net* net, int ia, int mode);
+int net_chain_mode(const saber_hip_net* net, int ia);
+// the stage headed by ops[i0] (NetOp::stage) on / off: on puts every block into its 3x3-led form and brings the tail (not the head); off takes both
+void net_set_stage(saber_hip_net* net, int i0, bool on);
+void net_set_head(saber_hip_net* net, int i0, bool on);    // the head of the stage headed by ops[i0]; in effect only while the stage is on
+void net_set_tail(saber_hip_net* net, int i0, bool on);    // the tail of the stage headed by ops[i0]; in effect only while the stage is on
 // chain forms (api_chain.hip)
 ChainForm chain_form(const saber_hip_chain* ch, int code);      // the table: what `code` means for this chain, code 0 if nothing
 bool chain_form_valid(const saber_hip_chain* ch, int code);      // the form exists for this chain and its stream is packed

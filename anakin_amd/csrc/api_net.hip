@@ -4,13 +4,20 @@
 #include <atomic>
 static std::atomic<int> g_coop_fallbacks_total{0};      // every net of the process (saber_hip_coop_fallbacks_total)
 
+void net_drop_graph(saber_hip_net* net) {
+    if (net->exec) (void)hipGraphExecDestroy(net->exec);
+    if (net->graph) (void)hipGraphDestroy(net->graph);
+    net->exec = nullptr;
+    net->graph = nullptr;
+}
 int net_launch(saber_hip_net* net, const NetOp& o, hipStream_t s) {
     auto T = [&](int id) -> void* { return net->ptr(id); };
     void* ws = net->arena + net->ws_off;
     switch (o.kind) {
     case OP_CONV:
-        if (o.skip) return SABER_HIP_OK;      // written by the previous op's chain launch
-        if (o.stage && o.use_stage) {         // this op's and the next stage_n - 1 blocks' chains in one persistent launch
+        switch (o.launch) {
+        case LAUNCH_NONE: return SABER_HIP_OK;      // written by the launch of ops[o.absorbed_by]
+        case LAUNCH_STAGE: {                  // this op's and the next stage_n - 1 blocks' chains in one persistent launch
             void* y1[saber_mi355x::STAGE4_LONG];
             void* y2[saber_mi355x::STAGE4_LONG];
             const NetOp* ops = &o;            // (the ops of a net are contiguous: block k's 3x3 conv is ops[3 * k])
@@ -19,24 +26,19 @@ int net_launch(saber_hip_net* net, const NetOp& o, hipStream_t s) {
                 y2[k] = T(ops[3 * k].chain3_y2);
             }
             // (with the head the launch starts from the pair's input - the pair is the op in front - and writes this op's input itself)
-            void* const y_tail = o.use_tail ? T(ops[3 * o.stage_n].chain3_y1) : nullptr;
-            const int rc = o.use_head ? stage_run(o.stage, T(ops[-1].in), nullptr, y1, y2, s, y_tail, T(o.in))
-                                      : stage_run(o.stage, T(o.in), T(o.chain3_res), y1, y2, s, y_tail);
+            void* const y_tail = o.tail_on ? T(ops[3 * o.stage_n].chain3_y1) : nullptr;
+            const int rc = o.head_on ? stage_run(o.stage, T(ops[-1].in), nullptr, y1, y2, s, y_tail, T(o.in))
+                                     : stage_run(o.stage, T(o.in), T(o.chain3_res), y1, y2, s, y_tail);
             if (rc == SABER_HIP_RUNTIME_ERROR) {      // an earlier launch of it timed out (conv_stage_coop.hip): block by block from now on
                 ++net->coop_fallbacks;
                 ++g_coop_fallbacks_total;
                 net_set_stage(net, (int)(&o - net->ops.data()), false);
-                if (net->exec) {      // (the captured graph holds the stage launch)
-                    (void)hipGraphExecDestroy(net->exec);
-                    (void)hipGraphDestroy(net->graph);
-                    net->exec = nullptr;
-                    net->graph = nullptr;
-                }
+                net_drop_graph(net);      // (the captured graph holds the stage launch)
             }
             return rc;
         }
-        if (o.stem_pair) return saber_hip_conv2d_stem_pair_run(o.stem_pair, T(o.in), nullptr, T(o.stem_y1), T(o.stem_y2), ws, s);
-        if (o.chain3 && o.use_chain3) {
+        case LAUNCH_STEM_PAIR: return saber_hip_conv2d_stem_pair_run(o.stem_pair, T(o.in), nullptr, T(o.stem_y1), T(o.stem_y2), ws, s);
+        case LAUNCH_CHAIN3: {
             const int rc = saber_hip_conv2d_chain_run3(o.chain3, T(o.in), T(o.chain3_res), T(o.chain3_y1), T(o.chain3_y2), T(o.chain3_y3), s);
             if (rc == SABER_HIP_RUNTIME_ERROR) {      // (a cooperating-workgroup chain reporting its failed earlier launch)
                 ++net->coop_fallbacks;
@@ -44,8 +46,10 @@ int net_launch(saber_hip_net* net, const NetOp& o, hipStream_t s) {
             }
             return rc;
         }
-        if (o.chain && o.use_chain) return saber_hip_conv2d_chain_run(o.chain, T(o.in), T(o.in2), T(o.out), T(o.chain_out), s);
-        if (o.sep && o.use_sep) return saber_hip_conv2d_sep_run(o.sep, T(o.in), nullptr, T(o.sep_out), s);      // the depthwise edge stays in LDS
+        case LAUNCH_CHAIN: return saber_hip_conv2d_chain_run(o.chain, T(o.in), T(o.in2), T(o.out), T(o.chain_out), s);
+        case LAUNCH_SEP: return saber_hip_conv2d_sep_run(o.sep, T(o.in), nullptr, T(o.sep_out), s);      // the depthwise edge stays in LDS
+        case LAUNCH_OWN: break;
+        }
         if (o.conv->gpool) return saber_hip_conv2d_run_gpool(o.conv, T(o.in), T(o.out), T(o.in2), T(o.out2), s);
         return saber_hip_conv2d_run(o.conv, T(o.in), T(o.out), T(o.in2), ws, s);
     case OP_CONV_PAIR:
@@ -111,12 +115,7 @@ int saber_hip_net_bind_tensor(saber_hip_net_t* net, int id, void* ptr) {
     if (net->finalized && !net->tensor_ext[id]) return fail(SABER_HIP_INVALID_VALUE, "bind_tensor: an arena tensor cannot become external after finalize");
     if (net->finalized && !ptr) return fail(SABER_HIP_INVALID_VALUE, "bind_tensor: an external tensor has no arena slot to fall back to after finalize");
     net->tensor_ext[id] = ptr;
-    if (net->exec) {   // a captured hipGraph holds the old address
-        (void)hipGraphExecDestroy(net->exec);
-        (void)hipGraphDestroy(net->graph);
-        net->exec = nullptr;
-        net->graph = nullptr;
-    }
+    net_drop_graph(net);      // a captured hipGraph holds the old address
     return SABER_HIP_OK;
 }
 int saber_hip_net_tensor_of_ptr(const saber_hip_net_t* net, const void* ptr) {
@@ -314,7 +313,6 @@ int saber_hip_net_compact_arena(saber_hip_net_t* net, const int* keep, int n_kee
         if (o.stem_pair) span(i, 2);
         if (o.sep) span(i, 2);      // (the one launch reads the depthwise conv's input while it writes the pointwise conv's output)
         if ((o.kind == OP_FC || o.kind == OP_FC_Q) && o.out2 >= 0) span(i, 2);
-        if (i + 1 < nops && net->ops[i + 1].skip) span(i, 2);      // (whatever else made the follower silent)
     }
     for (int i = 0; i < nops; ++i) {
         const NetOp& o = net->ops[i];
@@ -374,12 +372,7 @@ int saber_hip_net_compact_arena(saber_hip_net_t* net, const int* keep, int n_kee
     for (int t = 0; t < nt; ++t)
         if (!net->tensor_ext[t]) net->tensor_off[t] = off[t];
     net->compacted = true;
-    if (net->exec) {
-        (void)hipGraphExecDestroy(net->exec);
-        (void)hipGraphDestroy(net->graph);
-        net->exec = nullptr;
-        net->graph = nullptr;
-    }
+    net_drop_graph(net);
     return SABER_HIP_OK;
 }
 int saber_hip_net_arena_compacted(const saber_hip_net_t* net) { return net && net->compacted ? 1 : 0; }
@@ -506,10 +499,7 @@ static bool net_coop_error_pending(const saber_hip_net* net) {      // host read
 }
 int saber_hip_net_capture(saber_hip_net_t* net, saber_hip_stream_t stream) {
     hipStream_t s = (hipStream_t)stream;
-    if (net->exec) (void)hipGraphExecDestroy(net->exec);
-    if (net->graph) (void)hipGraphDestroy(net->graph);
-    net->exec = nullptr;
-    net->graph = nullptr;
+    net_drop_graph(net);
     // a cooperative launch of an EARLIER pass that failed is dealt with before anything is recorded (the sites fall back, the caller
     // hears about it): inside the capture the site's own check would switch kernels while the stream is capturing
     if (net_coop_error_pending(net)) return saber_hip_net_status(net);
@@ -518,12 +508,7 @@ int saber_hip_net_capture(saber_hip_net_t* net, saber_hip_stream_t stream) {
     hipError_t e = hipStreamEndCapture(s, &net->graph);
     if (rc == SABER_HIP_OK && e != hipSuccess) rc = hip_fail(e, "hipStreamEndCapture");
     if (rc == SABER_HIP_OK && (e = hipGraphInstantiate(&net->exec, net->graph, nullptr, nullptr, 0)) != hipSuccess) rc = hip_fail(e, "hipGraphInstantiate");
-    if (rc != SABER_HIP_OK) {      // no half-built graph survives a failed capture
-        if (net->exec) (void)hipGraphExecDestroy(net->exec);
-        if (net->graph) (void)hipGraphDestroy(net->graph);
-        net->exec = nullptr;
-        net->graph = nullptr;
-    }
+    if (rc != SABER_HIP_OK) net_drop_graph(net);      // no half-built graph survives a failed capture
     return rc;
 }
 int saber_hip_net_replay(saber_hip_net_t* net, saber_hip_stream_t stream) {
@@ -559,14 +544,9 @@ int saber_hip_net_op_work(const saber_hip_net_t* net, int index, double* bytes, 
     switch (o.kind) {
     case OP_CONV:
         if (o.skip) return SABER_HIP_OK;
-        conv_work(o.conv, *bytes, *flops);
-        if (o.stem_pair) {      // + the pair's work (the algorithmic bytes of the separate ops, like the chains')
-            conv_work(net->ops[index + 1].conv, *bytes, *flops);
-        } else if (o.chain3 && o.use_chain3) {
-            for (int j = index + 1; j < (int)net->ops.size() && net->ops[j].skip; ++j) conv_work(net->ops[j].conv, *bytes, *flops);
-        } else if ((o.chain && o.use_chain) || (o.sep && o.use_sep)) {
-            if (index + 1 < (int)net->ops.size() && net->ops[index + 1].skip) conv_work(net->ops[index + 1].conv, *bytes, *flops);
-        }
+        conv_work(o.conv, *bytes, *flops);      // + the work of the ops behind it that its launch covers (the algorithmic bytes of the separate ops)
+        for (int j = index + 1; j < (int)net->ops.size(); ++j)
+            if (net->ops[j].absorbed_by == index) conv_work(net->ops[j].conv, *bytes, *flops);
         return SABER_HIP_OK;
     case OP_CONV_PAIR:
         if (!o.skip) conv_work(o.conv, *bytes, *flops);
@@ -679,23 +659,18 @@ int saber_hip_net_time_ops(saber_hip_net_t* net, saber_hip_stream_t stream, int 
 int saber_hip_net_tensor_unwritten(const saber_hip_net_t* net, int id) {
     if (id < 0 || id >= (int)net->tensor_bytes.size()) return 0;
     if (net->tensor_bytes[id] == 0) return 1;      // the edge was removed by saber_hip_net_optimize (it has no storage)
-    for (const NetOp& o : net->ops)
-        if (((o.chain3 && o.use_chain3) || o.stem_pair || (o.sep && o.use_sep)) && o.out == id) return 1;
-    for (const NetOp& o : net->ops)      // the first block's shortcut while the pair that makes it runs as the stage launch's head: it stays in LDS
-        if (o.stage && o.use_head && o.chain3_res == id) return 1;
+    for (const NetOp& o : net->ops) {
+        const Launch by = o.skip ? net->ops[o.absorbed_by].launch : o.launch;      // the launch that covers this op
+        if (o.out == id && (o.launch == LAUNCH_CHAIN3 || o.launch == LAUNCH_STEM_PAIR || o.launch == LAUNCH_SEP || (o.chain3 && by == LAUNCH_STAGE))) return 1;
+        // the first block's shortcut while the pair that makes it runs as the stage launch's head: it stays in LDS
+        if (o.launch == LAUNCH_STAGE && o.head_on && o.chain3_res == id) return 1;
+    }
     return 0;
 }
 // After a pass has COMPLETED (the caller has synchronised): did one of its cooperative launches - a stage launch, a two-workgroup
 // chain - find its workgroups on different XCDs or time out in a hand-off (its outputs are then not valid)? The pinned error
 // words are read and cleared, the affected sites fall back to their single-workgroup launches for good, a captured graph is dropped.
 // SABER_HIP_RUNTIME_ERROR tells the caller to run the pass again. (Without this call the next launch of the site reports it.)
-static void net_drop_graph(saber_hip_net* net) {
-    if (!net->exec) return;
-    (void)hipGraphExecDestroy(net->exec);
-    (void)hipGraphDestroy(net->graph);
-    net->exec = nullptr;
-    net->graph = nullptr;
-}
 int saber_hip_net_status(saber_hip_net_t* net) {
     if (!net || !net->finalized) return fail(SABER_HIP_INVALID_VALUE, "net not finalized");
     int bad = 0;
@@ -703,7 +678,7 @@ int saber_hip_net_status(saber_hip_net_t* net) {
         NetOp& o = net->ops[i];
         if (o.stage && o.stage->h_err && *(volatile unsigned*)o.stage->h_err) {
             *(volatile unsigned*)o.stage->h_err = 0u;
-            if (o.use_stage) net_set_stage(net, (int)i, false);
+            if (o.stage_on) net_set_stage(net, (int)i, false);
             ++bad;
         }
         saber_hip_chain* ch = o.chain3;
@@ -720,6 +695,7 @@ int saber_hip_net_status(saber_hip_net_t* net) {
     if (!bad) return SABER_HIP_OK;
     net->coop_fallbacks += bad;
     g_coop_fallbacks_total += bad;
+    net_resolve(net);      // (a chain that fell back to its plain form has another name)
     net_drop_graph(net);
     return fail(SABER_HIP_RUNTIME_ERROR, "a cooperative launch of the last pass did not complete (workgroups on different XCDs, or a hand-off "
                 "timed out: another kernel held the CUs); its outputs are not valid - those sites now launch block by block: run the pass again");
@@ -729,7 +705,7 @@ int saber_hip_net_status(saber_hip_net_t* net) {
 int saber_hip_net_inject_coop_error(saber_hip_net_t* net) {
     if (!net) return fail(SABER_HIP_INVALID_VALUE, "null argument");
     for (NetOp& o : net->ops)
-        if (o.stage && o.use_stage && o.stage->h_err) { *(volatile unsigned*)o.stage->h_err = 1u; return SABER_HIP_OK; }
+        if (o.stage && o.stage_on && o.stage->h_err) { *(volatile unsigned*)o.stage->h_err = 1u; return SABER_HIP_OK; }
     for (NetOp& o : net->ops) {
         if (o.stage && o.stage->h_err) { *(volatile unsigned*)o.stage->h_err = 1u; return SABER_HIP_OK; }
         if (o.chain3 && o.chain3->h_coop_err) { *(volatile unsigned*)o.chain3->h_coop_err = 1u; return SABER_HIP_OK; }
@@ -743,8 +719,7 @@ int saber_hip_net_num_launches(const saber_hip_net_t* net) {
 }
 void saber_hip_net_destroy(saber_hip_net_t* net) {
     if (!net) return;
-    if (net->exec) (void)hipGraphExecDestroy(net->exec);
-    if (net->graph) (void)hipGraphDestroy(net->graph);
+    net_drop_graph(net);
     if (net->arena) (void)hipFree(net->arena);
     for (saber_hip_stem_pair* sp : net->owned_stem_pairs) saber_hip_conv2d_stem_pair_destroy(sp);
     for (saber_hip_chain_stage* st : net->owned_stages) saber_hip_conv2d_stage_destroy(st);

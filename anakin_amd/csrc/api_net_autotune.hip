@@ -17,16 +17,15 @@ static saber_hip_conv* net_op_conv(saber_hip_net* net, int index) {
 int saber_hip_net_get_choice(saber_hip_net_t* net, int index) {
     saber_hip_conv* c = net_op_conv(net, index);
     int choice = (c && !c->pool_fused && (c->algo <= ALGO_IGEMM_F32 || dw_ok(c) || group_ok(c))) ? saber_hip_conv2d_get_tile(c) : 0;
-    if (c && net->ops[index].chain) choice |= (1 << 28) | ((net->ops[index].use_chain ? net->ops[index].chain->form.code : 0) << 24);
-    // (a strided head that currently runs as its stage's tail reports the mode it has on its own)
-    const bool in_tail = c && net->ops[index].tail_of >= 0 && net->ops[net->ops[index].tail_of].use_tail;
-    const bool led = net->ops[index].chain3 && (in_tail ? net->ops[index].tail_mode == 2 : net->ops[index].use_chain3);
-    if (c && net->ops[index].chain3) choice |= (1 << 29) | ((led ? net->ops[index].chain3->form.code : 0) << 24);
-    if (c && net->ops[index].sep) choice |= (3 << 28) | ((net->ops[index].use_sep ? net->ops[index].sep->form : 0) << 24);
-    if (c && net->ops[index].stage && net->ops[index].use_stage) choice |= 1 << 30;      // this op launches its whole stage
-    if (c && net->ops[index].stage && net->ops[index].use_tail) choice |= (int)0x80000000u;      // ... and the strided head behind it as the launch's tail
+    if (!c) return choice;
+    const NetOp& o = net->ops[index];
+    if (o.chain) choice |= (1 << 28) | ((o.chain_on ? o.chain->form.code : 0) << 24);
+    if (o.chain3) choice |= (1 << 29) | ((o.led_on ? o.chain3->form.code : 0) << 24);      // (a strided head reports its own decision while it runs as a tail)
+    if (o.sep) choice |= (3 << 28) | ((o.sep_on ? o.sep->form : 0) << 24);
+    if (o.stage && o.stage_on) choice |= 1 << 30;      // this op launches its whole stage
+    if (o.stage && o.stage_on && o.tail_on) choice |= (int)0x80000000u;      // ... and the strided head behind it as the launch's tail
     // bit 29 on a sibling-pair op (which never leads a chain: bits 24..29 mean nothing else there): the pair runs as the HEAD of the stage launch behind it
-    if (c && net->ops[index].head_of >= 0 && net->ops[net->ops[index].head_of].use_head) choice |= 1 << 29;
+    if (o.head_of >= 0 && net->ops[o.head_of].stage_on && net->ops[o.head_of].head_on) choice |= 1 << 29;
     return choice;
 }
 int saber_hip_net_stage_blocks(const saber_hip_net_t* net, int index) {
@@ -60,43 +59,24 @@ int saber_hip_net_set_choice(saber_hip_net_t* net, int index, int choice) {
     if (sep_bits && tn && !sep_form_valid(o.sep, tn)) return saber_hip_conv2d_sep_set_tile(o.sep, tn);      // (its status and message)
     int rc = choice ? saber_hip_conv2d_set_tile(c, choice) : SABER_HIP_OK;
     if (rc) return rc;
-    // a strided head inside its stage's launch (the stage head came first and decided that): its own mode is restored underneath
-    const bool in_tail = o.tail_of >= 0 && net->ops[o.tail_of].use_tail;
-    if (in_tail) net_set_tail(net, o.tail_of, false);
-    o.name = std::string(o.kind == OP_FC || o.kind == OP_FC_Q ? "fc:" : "conv:") + c->algo_name;
-    if ((o.kind == OP_FC || o.kind == OP_FC_Q) && o.out2 >= 0) o.name += fc_softmax_ok(o.fc, o.kind == OP_FC_Q) ? "+softmax" : " | softmax_f32";
+    o.res_note.clear();
+    o.stage_name_kept = false;
     if (ch && tn) (void)saber_hip_conv2d_chain_set_tile(ch, tn);
     // (a block inside a selected stage - its head came first - stays in the 3x3-led mode the stage launch stands for, whatever form the word
-    // recorded while the stage was off: its followers must not launch beside the stage)
-    const bool in_stage = o.chain3 && o.skip && !o.stage;
-    if (ch && ch == o.chain3) net_set_chain_mode(net, index + 1, (tn || in_stage) ? 2 : net_chain_mode(net, index + 1) == 2 ? 1 : net_chain_mode(net, index + 1));
-    else if (ch) net_set_chain_mode(net, index, net_chain_mode(net, index) == 2 ? 2 : (tn ? 1 : 0));   // (also restores the names)
-    const bool stage_was = o.stage && o.use_stage;
-    if (o.stage) net_set_stage(net, index, stage_on);      // (a stage head comes before its blocks: set_choices runs in op order)
+    // recorded while the stage was off: its followers must not launch beside the stage. A strided head that runs as a tail is no such block:
+    // its own decision is stored underneath.)
+    const bool in_stage = o.chain3 && o.skip && !o.stage && o.tail_of < 0;
+    const int mode = ch ? net_chain_mode(net, ch == o.chain3 ? index + 1 : index) : 0;
+    if (ch && ch == o.chain3) net_set_chain_mode(net, index + 1, (tn || in_stage) ? 2 : std::min(mode, 1));
+    else if (ch) net_set_chain_mode(net, index, mode == 2 ? 2 : (tn ? 1 : 0));
+    // a stage head comes before its blocks and after the pair in front of it (set_choices runs in op order): a stage that was off takes the
+    // head the pair's word asked for - and only then: a stage switched on by itself comes without its head
+    if (o.stage) net_set_stage(net, index, stage_on);
     if (o.stage) net_set_tail(net, index, tail_on);
-    // the head: the pair's word (the op in front: it came first) decides. A stage that is on takes it at once; one that was off takes the request
-    // its own word finds here - and only then: a stage switched on by itself comes without its head
-    if (o.stage && stage_on && !stage_was) net_set_head(net, index, o.head_req);
-    if (o.stage) o.head_req = false;
-    if (o.head_of >= 0) {
-        const bool head_on = (chain_bits & 32) && !net->shared_device;
-        net->ops[o.head_of].head_req = head_on;
-        net_set_head(net, o.head_of, head_on);
-    }
-    if (in_tail) net_set_tail(net, o.tail_of, true);
-    if (o.skip) o.name = (o.chain3 && o.use_chain3) ? "conv:(in the stage launch)" : "conv:(in the chain launch)";
-    if (o.skip && index > 0 && net->ops[index - 1].tail_of >= 0 && net->ops[net->ops[index - 1].tail_of].use_tail) o.name = "conv:(in the stage launch)";
-    if (o.skip && o.kind == OP_CONV_PAIR) o.name = (index > 0 && net->ops[index - 1].stem_pair) ? "conv:(in the stem launch)" : "conv:(in the chain launch)";
-    if (o.skip && o.head_of >= 0 && net->ops[o.head_of].use_head) o.name = "conv:(in the stage launch)";
-    if (o.stem_pair) o.name = stem_pair_name(o);
-    if (o.sep) net_set_sep(net, index, sep_bits ? tn : (o.use_sep ? o.sep->form : 0));      // (a choice without the bits leaves the site as it is; the names follow)
-    if (o.skip && index > 0 && net->ops[index - 1].sep && net->ops[index - 1].use_sep) o.name = "conv:(in the separable launch)";
-    if (net->exec) {
-        (void)hipGraphExecDestroy(net->exec);
-        (void)hipGraphDestroy(net->graph);
-        net->exec = nullptr;
-        net->graph = nullptr;
-    }
+    if (o.head_of >= 0) net_set_head(net, o.head_of, (chain_bits & 32) && !net->shared_device);
+    if (sep_bits) net_set_sep(net, index, tn);      // (a choice without the bits leaves the site as it is)
+    net_resolve(net);      // (the names follow the kernel selection)
+    net_drop_graph(net);
     return SABER_HIP_OK;
 }
 
@@ -111,7 +91,7 @@ static int net_consolidate_kernels(saber_hip_net* net, hipStream_t s) {
         if (e[0] == '1') return SABER_HIP_OK;
     struct Site { int op; unsigned long long key; ConvSel choice; };
     auto conv_of = [&](const NetOp& o) -> saber_hip_conv* {
-        if (o.skip || (o.chain && o.use_chain) || (o.chain3 && o.use_chain3) || (o.stage && o.use_stage) || (o.sep && o.use_sep)) return nullptr;
+        if (o.launch != LAUNCH_OWN) return nullptr;
         if (o.kind != OP_CONV && o.kind != OP_CONV_PAIR) return nullptr;
         if (net->reproducible_fp32 && o.conv && !o.conv->is_i8) return nullptr;      // flag 8192: this pass moves no FP32 op either
         return (o.conv && !o.conv->pool_fused && o.conv->algo <= ALGO_IGEMM_F32) ? o.conv : nullptr;
@@ -170,7 +150,7 @@ static int net_consolidate_kernels(saber_hip_net* net, hipStream_t s) {
             if (rc) return rc;
             if (best < base2 * 0.996f) {
                 (void)sel_set(c, best_c);
-                net->ops[cur.op].name = std::string("conv:") + c->algo_name;
+                net_resolve(net);
                 sites = collect();
             }
         }
@@ -182,12 +162,7 @@ int saber_hip_net_autotune(saber_hip_net_t* net, saber_hip_stream_t stream, int 
     if (net->inplace_external)
         return fail(SABER_HIP_INVALID_VALUE, "autotune: an in-place sum of this captured list accumulates into a tensor of the caller's that the "
                     "list itself never writes - timing passes would change it (run the pass that writes it inside the capture)");
-    if (net->exec) {   // a captured graph holds the OLD kernel selections: drop it, the caller captures again
-        (void)hipGraphExecDestroy(net->exec);
-        (void)hipGraphDestroy(net->graph);
-        net->exec = nullptr;
-        net->graph = nullptr;
-    }
+    net_drop_graph(net);      // a captured graph holds the OLD kernel selections: the caller captures again
     auto T = [&](int id) -> void* { return net->ptr(id); };
     ColdScope scope;
     // flush size between timed repetitions: a net whose tensor arena exceeds the 256 MB Infinity Cache finds its weights in no cache
@@ -207,7 +182,6 @@ int saber_hip_net_autotune(saber_hip_net_t* net, saber_hip_stream_t stream, int 
         if (o.kind == OP_CONV_PAIR) {
             int rc = saber_hip_conv2d_autotune_pair(o.conv, T(o.in), T(o.out), T(o.out2), stream, iters);
             if (rc) return rc;
-            o.name = std::string("conv:") + o.conv->algo_name;
             continue;
         }
         saber_hip_conv* c = o.kind == OP_CONV ? o.conv : ((o.kind == OP_FC || o.kind == OP_FC_Q) ? o.fc->conv : nullptr);
@@ -220,10 +194,9 @@ int saber_hip_net_autotune(saber_hip_net_t* net, saber_hip_stream_t stream, int 
         }
         int rc = saber_hip_conv2d_autotune(c, xin, T(o.out), T(o.in2), net->arena + net->ws_off, stream, iters);
         if (rc) return rc;
-        o.name = std::string(o.kind == OP_CONV ? "conv:" : "fc:") + c->algo_name;
-        if ((o.kind == OP_FC || o.kind == OP_FC_Q) && o.out2 >= 0) o.name += fc_softmax_ok(o.fc, o.kind == OP_FC_Q) ? "+softmax" : " | softmax_f32";
-        if (o.stem_pair) o.name = stem_pair_name(o);
+        o.res_note.clear();
     }
+    net_resolve(net);      // (the names of the tuned selections)
     const char* log_env = std::getenv("SABER_HIP_AUTOTUNE_LOG");
     const bool log_cands = g_cold && log_env && log_env[0] == '1';      // every timed chain / stage candidate, in the per-op tuner's format
     auto log_cand = [&](const saber_hip_conv* c, const std::string& name, float t) {

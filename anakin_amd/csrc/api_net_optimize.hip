@@ -16,112 +16,135 @@
 // New ops are re-created from the originals' quantised weights / scales / bias and owned by the net. Call before
 // saber_hip_net_finalize. Returns the number of launches removed, or a negative status.
 // ------------------------------------------------------------------------------------------------
-static void net_name_chain(NetOp& A, NetOp& B) {
-    if (A.skip) {
-        A.name = B.name = "conv:(in the chain launch)";
-    } else if (A.use_chain) {
-        A.name = "conv:" + chain_form_name(A.chain);
-        B.name = "conv:(in the chain launch)";
-    } else {
-        A.name = std::string("conv:") + A.conv->algo_name;
-        B.name = std::string("conv:") + B.conv->algo_name;
+// Sites: decisions in, derived state out. net_resolve is the only writer of NetOp::launch / absorbed_by / skip and - once the sites are formed -
+// of every conv / pair / fc / softmax op's name. Priority: a selected stage covers its blocks, its tail and its head when those are on; below
+// that a led chain covers the two ops behind it (the 1x1 chain head and its follower, or the pair); below that the 1x1 chain and the separable
+// launch cover the next op. The stem pair and fc + softmax are unconditional. Called when a decision (or a kernel selection, for the names)
+// changes - never per pass.
+void net_resolve(saber_hip_net* net) {
+    std::vector<NetOp>& ops = net->ops;
+    const int n = (int)ops.size();
+    enum { IN_CHAIN, IN_STAGE, IN_STEM, IN_SEP };
+    static const char* const covered[] = {"conv:(in the chain launch)", "conv:(in the stage launch)", "conv:(in the stem launch)", "conv:(in the separable launch)"};
+    std::vector<int> in(n, IN_CHAIN);
+    for (NetOp& o : ops) {
+        o.launch = LAUNCH_OWN;
+        o.absorbed_by = -1;
+    }
+    auto absorb = [&](int j, int by, int what) {
+        ops[j].launch = LAUNCH_NONE;
+        ops[j].absorbed_by = by;
+        in[j] = what;
+    };
+    for (int i = 0; i < n; ++i) {
+        NetOp& o = ops[i];
+        if (o.launch == LAUNCH_NONE) continue;      // (an earlier op's launch covers it, whatever it could head itself)
+        if ((o.kind == OP_FC || o.kind == OP_FC_Q) && o.out2 >= 0) {
+            for (int j = i + 1; j < n; ++j)
+                if (ops[j].kind == OP_SOFTMAX && ops[j].out == o.out2) { absorb(j, i, IN_CHAIN); break; }
+        }
+        if (o.kind != OP_CONV || i + 1 >= n) continue;
+        if (o.stage && o.stage_on) {
+            o.launch = LAUNCH_STAGE;
+            for (int k = 0; k < o.stage_n; ++k) {      // (a block's followers keep the name they have behind their own 3x3 conv)
+                if (k) absorb(i + 3 * k, i, IN_STAGE);
+                absorb(i + 3 * k + 1, i, IN_CHAIN);
+                absorb(i + 3 * k + 2, i, IN_CHAIN);
+            }
+            if (o.tail_on)
+                for (int j = i + 3 * o.stage_n; j < i + 3 * o.stage_n + 2; ++j) absorb(j, i, IN_STAGE);
+            if (o.head_on) absorb(i - 1, i, IN_STAGE);
+        } else if (o.stem_pair) {
+            o.launch = LAUNCH_STEM_PAIR;
+            absorb(i + 1, i, IN_STEM);
+        } else if (o.chain3 && o.led_on) {
+            o.launch = LAUNCH_CHAIN3;
+            absorb(i + 1, i, IN_CHAIN);
+            if (o.chain3->b || o.chain3->b2) absorb(i + 2, i, IN_CHAIN);
+        } else if (o.chain && o.chain_on) {
+            o.launch = LAUNCH_CHAIN;
+            absorb(i + 1, i, IN_CHAIN);
+        } else if (o.sep && o.sep_on) {
+            o.launch = LAUNCH_SEP;
+            absorb(i + 1, i, IN_SEP);
+        }
+    }
+    for (int i = 0; i < n; ++i) {
+        NetOp& o = ops[i];
+        o.skip = o.launch == LAUNCH_NONE;
+        if (o.kind == OP_SOFTMAX) {
+            o.name = o.skip ? "softmax_f32 (in the fc launch)" : "softmax_f32";
+        } else if (o.kind == OP_FC || o.kind == OP_FC_Q) {
+            o.name = std::string("fc:") + o.fc->conv->algo_name;
+            if (o.out2 >= 0) o.name += fc_softmax_ok(o.fc, o.kind == OP_FC_Q) ? "+softmax" : " | softmax_f32";
+        } else if (o.kind == OP_CONV || o.kind == OP_CONV_PAIR) {
+            const std::string own = o.conv->algo_name;
+            const bool kept = o.stage_name_kept && !o.skip;      // (NetOp::stage_name_kept: shown as it was inside the stage launch)
+            switch (kept ? (o.stage ? LAUNCH_STAGE : LAUNCH_NONE) : o.launch) {
+            case LAUNCH_NONE: o.name = covered[kept ? IN_STAGE : in[i]]; break;
+            case LAUNCH_OWN: o.name = "conv:" + own + o.res_note; break;
+            case LAUNCH_CHAIN: o.name = "conv:" + chain_form_name(o.chain); break;
+            case LAUNCH_CHAIN3: o.name = "conv:" + chain_form_name(o.chain3); break;
+            case LAUNCH_SEP: o.name = std::string("conv:") + saber_hip_conv2d_sep_algo(o.sep); break;
+            case LAUNCH_STEM_PAIR: o.name = "conv:" + own + "+pair1x1_" + std::to_string(o.stem_pair->a->d.k) + "+" + std::to_string(o.stem_pair->b->d.k); break;
+            case LAUNCH_STAGE:
+                o.name = std::string(o.head_on && !kept ? "conv:[pair1x1]+stage_c" : "conv:stage_c") + std::to_string(o.stage->c1) + "_" + std::to_string(o.stage_n) + "x[conv3x3+chain1x1]_2x16" +
+                         (o.stage->c1 == 256 ? "_coop4" : "") + (o.tail_on && !kept ? "+[conv3x3/2+conv1x1]" : "");
+                break;
+            }
+        }
     }
 }
-// mode of the ops around A = ops[ia] (a 1x1 conv with the fused eltwise): 0 separate launches, 1 A + B chained (A.chain),
-// 2 the 3x3 conv ops[ia - 1] leads the launch (its chain3; with or without B)
-static std::string stage_name(const NetOp& H0) {
-    return std::string(H0.use_head ? "conv:[pair1x1]+stage_c" : "conv:stage_c") + std::to_string(H0.stage->c1) + "_" + std::to_string(H0.stage_n) + "x[conv3x3+chain1x1]_2x16" + (H0.stage->c1 == 256 ? "_coop4" : "") +
-           (H0.use_tail ? "+[conv3x3/2+conv1x1]" : "");
-}
+// The setters store decisions and resolve. ops[ia] = A, a 1x1 conv with the fused eltwise: mode 0 separate launches, 1 A + the next op chained,
+// 2 the 3x3 conv ops[ia - 1] leads the launch. A led chain switches the 1x1 chain behind it on as well: that is what runs when it goes off again.
 void net_set_chain_mode(saber_hip_net* net, int ia, int mode) {
     NetOp& A = net->ops[ia];
     NetOp* H = (ia > 0 && net->ops[ia - 1].chain3) ? &net->ops[ia - 1] : nullptr;
-    if (mode == 2 && !H) mode = 1;
-    if (mode == 1 && !A.chain) mode = 0;
-    NetOp* B = A.chain ? &net->ops[ia + 1] : nullptr;
-    A.use_chain = mode == 1 || (mode == 2 && H->chain3->b && !H->chain3->b2);
-    if (B) B->skip = mode == 1 || (mode == 2 && H->chain3->b);
-    A.skip = mode == 2;
-    if (H && H->chain3->b2) {      // strided head + sibling pair: the pair op behind A launches nothing while the chain runs
-        NetOp& P = net->ops[ia + 1];
-        P.skip = mode == 2;
-        P.name = mode == 2 ? "conv:(in the chain launch)" : std::string("conv:") + P.conv->algo_name;
-    }
-    if (H) {
-        H->use_chain3 = mode == 2;
-        H->name = "conv:" + (mode == 2 ? chain_form_name(H->chain3) : std::string(H->conv->algo_name));
-    }
-    if (B) net_name_chain(A, *B);
-    else A.name = A.skip ? "conv:(in the chain launch)" : std::string("conv:") + A.conv->algo_name;
-    if (H && H->stage && H->use_stage) H->name = stage_name(*H);      // (an active stage keeps its names: set_choice comes through here)
-    else if (H && H->skip) H->name = "conv:(in the stage launch)";
-}
-// The stage headed by ops[i0] on / off. On: every block runs its 3x3-led chain form (mode 2), ops[i0] launches them all and the
-// other blocks' 3x3 convs carry `skip` too. Off: the blocks' chains launch one by one again (mode 2, their own tile codes).
-std::string stem_pair_name(const NetOp& o) {
-    return std::string("conv:") + o.conv->algo_name + "+pair1x1_" + std::to_string(o.stem_pair->a->d.k) + "+" + std::to_string(o.stem_pair->b->d.k);
-}
-// The strided head behind the stage headed by ops[i0] inside / outside the stage launch. Inside: its two ops launch nothing (like a
-// block's they are in chain mode 2: the 3x3 conv's edge is not written), the stage head's launch writes the 1x1 conv's output.
-void net_set_tail(saber_hip_net* net, int i0, bool on) {
-    NetOp& H0 = net->ops[i0];
-    if (!H0.stage || !H0.stage->tail) return;
-    const int it = i0 + 3 * H0.stage_n;
-    NetOp& Ht = net->ops[it];
-    on = on && H0.use_stage;
-    if (on == H0.use_tail) return;
-    if (on) Ht.tail_mode = net_chain_mode(net, it + 1);
-    H0.use_tail = on;
-    Ht.skip = on;
-    net_set_chain_mode(net, it + 1, on ? 2 : Ht.tail_mode);
-    if (on) net->ops[it + 1].name = "conv:(in the stage launch)";
-    if (H0.use_stage) H0.name = stage_name(H0);
-}
-// The sibling pair in front of the stage headed by ops[i0] inside / outside the stage launch. Inside: the pair op launches nothing, the
-// stage head's launch reads the pair's input and writes the pair's second output (its own input); the first - the shortcut - is not written.
-void net_set_head(saber_hip_net* net, int i0, bool on) {
-    NetOp& H0 = net->ops[i0];
-    if (!H0.stage || !H0.stage->head_a || i0 < 1 || net->ops[i0 - 1].head_of != i0) return;
-    NetOp& P = net->ops[i0 - 1];
-    on = on && H0.use_stage;
-    if (on == H0.use_head) return;
-    H0.use_head = on;
-    P.skip = on;
-    P.name = on ? std::string("conv:(in the stage launch)") : std::string("conv:") + P.conv->algo_name;
-    if (H0.use_stage) H0.name = stage_name(H0);
-}
-void net_set_stage(saber_hip_net* net, int i0, bool on) {
-    NetOp& H0 = net->ops[i0];
-    if (!H0.stage) return;
-    if (!on) net_set_head(net, i0, false);      // (switching a stage ON never switches its head on: that takes the pair's own choice word)
-    if (!on) net_set_tail(net, i0, false);
-    for (int k = 0; k < H0.stage_n; ++k) {
-        if (on || H0.use_stage) net_set_chain_mode(net, i0 + 3 * k + 1, 2);
-        NetOp& Hk = net->ops[i0 + 3 * k];
-        if (k) {
-            Hk.skip = on;
-            if (on) Hk.name = "conv:(in the stage launch)";
-        }
-    }
-    H0.use_stage = on;
-    if (on) net_set_tail(net, i0, true);
-    if (on) H0.name = stage_name(H0);
+    if (H) H->led_on = mode == 2;
+    if (H) H->stage_name_kept = false;
+    A.chain_on = A.chain && mode >= 1;
+    A.res_note.clear();
+    net_resolve(net);
 }
 int net_chain_mode(const saber_hip_net* net, int ia) {
     const NetOp& A = net->ops[ia];
-    return A.skip ? 2 : (A.use_chain ? 1 : 0);
+    return (ia > 0 && net->ops[ia - 1].chain3 && net->ops[ia - 1].led_on) ? 2 : (A.chain_on ? 1 : 0);
 }
-// The separable site headed by ops[i] (NetOp::sep): code = a valid form of the pair -> the one launch with that form, the pointwise op behind
-// it launches nothing and the depthwise edge is not written; 0 -> the two ops launch on their own again.
+void net_set_tail(saber_hip_net* net, int i0, bool on) {
+    NetOp& H0 = net->ops[i0];
+    if (!H0.stage || !H0.stage->tail) return;
+    H0.tail_on = on;
+    net_resolve(net);
+}
+void net_set_head(saber_hip_net* net, int i0, bool on) {
+    NetOp& H0 = net->ops[i0];
+    if (!H0.stage || !H0.stage->head_a || i0 < 1 || net->ops[i0 - 1].head_of != i0) return;
+    H0.head_on = on;
+    net_resolve(net);
+}
+// On: every block goes into its 3x3-led form (and stays there when the stage goes off again) and the tail comes with the stage; the head does
+// not - that takes the pair's own choice word, the autotuner or a selector. Off: tail and head go with it.
+void net_set_stage(saber_hip_net* net, int i0, bool on) {
+    NetOp& H0 = net->ops[i0];
+    if (!H0.stage) return;
+    if (on || H0.stage_on)
+        for (int k = 0; k < H0.stage_n; ++k) {
+            net->ops[i0 + 3 * k].led_on = true;
+            net->ops[i0 + 3 * k].stage_name_kept = !on;
+            net->ops[i0 + 3 * k + 1].chain_on = net->ops[i0 + 3 * k + 1].chain != nullptr;
+        }
+    if (on) H0.tail_on = H0.stage->tail != nullptr;
+    if (!on) H0.tail_on = H0.head_on = false;
+    H0.stage_on = on;
+    net_resolve(net);
+}
+// The separable site headed by ops[i] (NetOp::sep): code = a valid form of the pair -> the one launch with that form; 0 -> the two ops launch on their own again.
 void net_set_sep(saber_hip_net* net, int i, int code) {
     NetOp& D = net->ops[i];
     if (!D.sep || i + 1 >= (int)net->ops.size()) return;
-    NetOp& P = net->ops[i + 1];
     if (code && saber_hip_conv2d_sep_set_tile(D.sep, code) != SABER_HIP_OK) code = 0;
-    D.use_sep = code != 0;
-    P.skip = D.use_sep;
-    D.name = std::string("conv:") + (D.use_sep ? saber_hip_conv2d_sep_algo(D.sep) : D.conv->algo_name.c_str());
-    P.name = D.use_sep ? std::string("conv:(in the separable launch)") : std::string("conv:") + P.conv->algo_name;
+    D.sep_on = code != 0;
+    net_resolve(net);
 }
 static int clone_conv_i8(const saber_hip_conv* src, const saber_hip_conv_desc& d, saber_hip_conv** out) {
     int rc = saber_hip_conv2d_create(&d, out);
@@ -153,6 +176,11 @@ int saber_hip_net_optimize(saber_hip_net_t* net, int flags) {
         for (size_t i = 0; i < ops.size(); ++i)
             if (!dead[i]) c += (ops[i].in == t) + (ops[i].in2 == t);
         return c;
+    };
+    auto readers = [&](int t) {      // ... over the list as it stands (after the compaction below: every op)
+        int r = 0;
+        for (const NetOp& o : ops) r += (o.in == t) + (o.in2 == t);
+        return r;
     };
     auto producer = [&](int t, int before) {   // last live op before `before` that writes tensor t
         for (int i = before - 1; i >= 0; --i)
@@ -200,7 +228,6 @@ int saber_hip_net_optimize(saber_hip_net_t* net, int flags) {
                 ops[p].conv = fused;
                 ops[p].in2 = tr;
                 ops[p].out = e.out;
-                ops[p].name = std::string("conv:") + fused->algo_name;
                 dead[i] = 1;
                 net->tensor_bytes[tc] = 0;   // the conv's own output edge no longer exists
                 ++removed;
@@ -238,7 +265,7 @@ int saber_hip_net_optimize(saber_hip_net_t* net, int flags) {
             net->owned.push_back(fused);
             ops[c].conv = fused;
             ops[c].in2 = q.in;
-            ops[c].name = std::string("conv:") + fused->algo_name + "+res/" + std::to_string(q.p[8]);
+            ops[c].res_note = "+res/" + std::to_string(q.p[8]);
             dead[i] = 1;
             net->tensor_bytes[q.out] = 0;
             ++removed;
@@ -268,7 +295,6 @@ int saber_hip_net_optimize(saber_hip_net_t* net, int flags) {
             ops[p].conv = fused;
             const int dead_t = ops[p].out;
             ops[p].out = q.out;
-            ops[p].name = std::string("conv:") + fused->algo_name;
             dead[i] = 1;
             net->tensor_bytes[dead_t] = 0;
             ++removed;
@@ -302,7 +328,6 @@ int saber_hip_net_optimize(saber_hip_net_t* net, int flags) {
                 ops[i].conv = pair;
                 ops[i].out2 = ops[j].out;
                 if (swapped) std::swap(ops[i].out, ops[i].out2);
-                ops[i].name = std::string("conv:") + pair->algo_name;
                 dead[j] = 1;
                 ++removed;
                 break;
@@ -356,7 +381,6 @@ int saber_hip_net_optimize(saber_hip_net_t* net, int flags) {
             net->owned.push_back(fused);
             ops[p].conv = fused;
             ops[p].out2 = q.out;
-            ops[p].name = std::string("conv:") + fused->algo_name;
             dead[i] = 1;
             ++removed;
         }
@@ -375,20 +399,16 @@ int saber_hip_net_optimize(saber_hip_net_t* net, int flags) {
             NetOp& P = ops[i + 1];
             if (S.kind != OP_CONV || !S.conv || !S.conv->pool_fused || S.lane || S.in2 >= 0 || S.out2 >= 0 || S.stem_pair) continue;
             if (P.kind != OP_CONV_PAIR || !P.conv || P.lane || P.in != S.out || !P.conv->pair_src_a || !P.conv->pair_src_b) continue;
-            int readers = 0;
-            for (const NetOp& o : ops) readers += (o.in == S.out) + (o.in2 == S.out);
-            if (readers != 1) continue;
+            if (readers(S.out) != 1) continue;
             saber_hip_stem_pair* sp = nullptr;
             if (saber_hip_conv2d_stem_pair_create(S.conv, P.conv->pair_src_a, P.conv->pair_src_b, &sp) != SABER_HIP_OK) continue;
             net->owned_stem_pairs.push_back(sp);
             S.stem_pair = sp;
             S.stem_y1 = P.out;
             S.stem_y2 = P.out2;
-            S.name = stem_pair_name(S);
-            P.skip = true;
-            P.name = "conv:(in the stem launch)";
             ++removed;
         }
+        net_resolve(net);      // (the pairs now covered are no site's op below)
     }
     // A chain launch reads and writes the tensors of SEVERAL ops (chain3_res / chain_out / chain3_y1 / chain3_y2), while the
     // cross-lane event ordering of saber_hip_net_run only follows the launching op's own in / in2 / out / out2: in a
@@ -410,9 +430,7 @@ int saber_hip_net_optimize(saber_hip_net_t* net, int flags) {
                 D.stem_pair || P.chain || P.chain3 || P.stem_pair || P.sep || D.in2 >= 0 || P.in2 >= 0 || D.out2 >= 0 || P.out2 >= 0 || P.in != D.out)
                 continue;
             if (!D.conv->is_i8 || !dw_ok(D.conv)) continue;
-            int readers = 0;
-            for (const NetOp& o : ops) readers += (o.in == D.out) + (o.in2 == D.out);
-            if (readers != 1) continue;
+            if (readers(D.out) != 1) continue;
             saber_hip_sep* sp = nullptr;
             if (saber_hip_conv2d_sep_create(D.conv, P.conv, &sp) != SABER_HIP_OK) continue;      // not a pair the kernel takes
             net->owned_seps.push_back(sp);
@@ -437,7 +455,7 @@ int saber_hip_net_optimize(saber_hip_net_t* net, int flags) {
             A.chain = ch;
             A.chain_out = B.out;
             net_set_chain_mode(net, (int)i, ch->c1 <= 256 ? 1 : 0);      // default until the autotuner has timed both forms
-            if (A.use_chain) ++removed;
+            if (A.chain_on) ++removed;
         }
     }
     // ---- 32: the block's 3x3 conv in front of a chain head, when the head is its only consumer -----------------------
@@ -449,17 +467,15 @@ int saber_hip_net_optimize(saber_hip_net_t* net, int flags) {
             if (!A.chain || Hd.kind != OP_CONV || !Hd.conv || Hd.chain3 || Hd.chain || Hd.skip || Hd.lane || Hd.in2 >= 0 ||
                 A.in != Hd.out)
                 continue;
-            int readers = 0;
-            for (const NetOp& o : ops) readers += (o.in == Hd.out) + (o.in2 == Hd.out);
-            if (readers != 1) continue;
+            if (readers(Hd.out) != 1) continue;
             saber_hip_chain* ch = nullptr;
             if (saber_hip_conv2d_chain_create3(Hd.conv, A.conv, B.conv, &ch) != SABER_HIP_OK) continue;
             net->owned_chains.push_back(ch);
             Hd.chain3 = ch;
             Hd.chain3_res = A.in2; Hd.chain3_y1 = A.out; Hd.chain3_y2 = B.out;
-            const bool was = A.use_chain;
+            const bool was = A.chain_on;
             net_set_chain_mode(net, (int)i + 1, ch->c1 <= 128 ? 2 : (was ? 1 : 0));
-            if (Hd.use_chain3) removed += was ? 1 : 2;
+            if (Hd.led_on) removed += was ? 1 : 2;
         }
         // ... and in front of a fused-eltwise 1x1 conv that heads no chain (the last block of a stage): conv3x3 + conv1x1
         for (size_t i = 0; i + 1 < ops.size(); ++i) {
@@ -468,17 +484,13 @@ int saber_hip_net_optimize(saber_hip_net_t* net, int flags) {
             if (A.chain || A.skip || A.kind != OP_CONV || !A.conv || A.conv->d.res_mode != SABER_HIP_RES_ELTWISE || A.in2 < 0 || A.lane ||
                 Hd.kind != OP_CONV || !Hd.conv || Hd.chain3 || Hd.chain || Hd.skip || Hd.lane || Hd.in2 >= 0 || A.in != Hd.out)
                 continue;
-            int readers = 0;
-            for (const NetOp& o : ops) readers += (o.in == Hd.out) + (o.in2 == Hd.out);
-            if (readers != 1) continue;
+            if (readers(Hd.out) != 1) continue;
             saber_hip_chain* ch = nullptr;
             // 1024: ... and the sibling pair that is the only reader of A's output (the next stage's branch1 / branch2a) joins the launch
             NetOp* P = (flags & 1024) && i + 2 < ops.size() ? &ops[i + 2] : nullptr;
             if (P && (P->kind != OP_CONV_PAIR || P->lane || P->skip || P->in != A.out || !P->conv || !P->conv->pair_src_a || !P->conv->pair_src_b)) P = nullptr;
             if (P) {
-                int rd = 0;
-                for (const NetOp& o : ops) rd += (o.in == A.out) + (o.in2 == A.out);
-                if (rd != 1 || saber_hip_conv2d_chain_create3_pair(Hd.conv, A.conv, const_cast<saber_hip_conv*>(P->conv->pair_src_a),
+                if (readers(A.out) != 1 || saber_hip_conv2d_chain_create3_pair(Hd.conv, A.conv, const_cast<saber_hip_conv*>(P->conv->pair_src_a),
                                                                    const_cast<saber_hip_conv*>(P->conv->pair_src_b), &ch) != SABER_HIP_OK)
                     P = nullptr;
             }
@@ -487,7 +499,7 @@ int saber_hip_net_optimize(saber_hip_net_t* net, int flags) {
             Hd.chain3 = ch;
             Hd.chain3_res = A.in2; Hd.chain3_y1 = A.out; Hd.chain3_y2 = P ? P->out : -1; Hd.chain3_y3 = P ? P->out2 : -1;
             net_set_chain_mode(net, (int)i + 1, ch->c1 <= 128 ? 2 : 0);
-            if (Hd.use_chain3) removed += P ? 2 : 1;
+            if (Hd.led_on) removed += P ? 2 : 1;
         }
     }
     // ---- 256: runs of 3x3-led C = 256 (or C = 128) chains whose blocks feed each other (ResNet's res4 / res3 stage) -> one persistent launch
@@ -525,11 +537,6 @@ int saber_hip_net_optimize(saber_hip_net_t* net, int flags) {
                     ops[i - 1].conv->pair_src_a && ops[i - 1].conv->pair_src_b && !(i >= 3 && ops[i - 3].chain3 && ops[i - 3].chain3->b2)) {
                     const NetOp& P = ops[i - 1];
                     const int t_res = ops[i].chain3_res, t_x = ops[i].in;
-                    auto readers = [&](int t) {
-                        int r = 0;
-                        for (const NetOp& o : ops) r += (o.in == t) + (o.in2 == t);
-                        return r;
-                    };
                     const bool fwd = P.out == t_res && P.out2 == t_x, rev = P.out == t_x && P.out2 == t_res;
                     if ((fwd || rev) && t_res != t_x && readers(t_res) == 1 && readers(t_x) == 1) {
                         head_a = fwd ? P.conv->pair_src_a : P.conv->pair_src_b;
@@ -570,9 +577,6 @@ int saber_hip_net_optimize(saber_hip_net_t* net, int flags) {
             if (F.kind == OP_FC && F.fc->pre_quant) continue;      // (a quantise-on-entry pre-pass: two launches already)
             if (!fc_softmax_ok(F.fc, F.kind == OP_FC_Q) || fc_softmax_prepare(F.fc) != SABER_HIP_OK) continue;
             F.out2 = S.out;
-            F.name = std::string("fc:") + F.fc->conv->algo_name + "+softmax";
-            S.skip = true;
-            S.name = "softmax_f32 (in the fc launch)";
             ++removed;
         }
     }
@@ -587,6 +591,7 @@ int saber_hip_net_optimize(saber_hip_net_t* net, int flags) {
                 if (ch && ch->form.placement) ch->form = chain_form_plain(ch);
         }
     }
+    net_resolve(net);
     // the shared workspace only has to cover the surviving ops
     net->ws_bytes = 0;
     for (const NetOp& o : ops) {
