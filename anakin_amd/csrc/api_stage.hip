@@ -164,6 +164,19 @@ int img_conv_run(saber_hip_conv* op, const void* x, void* y, const void* res, vo
     if (!st) return fail(SABER_HIP_INVALID_VALUE, "image-resident kernel selected without its buffers (set_tile / autotune build them)");
     const StagePhase& p = st->phases[0];
     if (!x || !y || (p.elt && !res) || (p.pool_t >= 0 && !y_pool)) return fail(SABER_HIP_INVALID_VALUE, "null tensor");
+    if (p.pool_t >= 0 && op->d.kh == 1 && conv1x1_gpool_ok(p.cin, p.cout, st->h * st->w)) {
+        // 1x1 512 -> 2048 + global pooling (stage_xcd_type {4, 2, 0}): the kernel of its own, same weights and constants
+        GpoolKArgs g;
+        std::memset(&g, 0, sizeof g);
+        g.x = x; g.y = y; g.res = p.elt ? res : nullptr; g.y_pool = y_pool;
+        g.w = st->d_w.p + (size_t)p.w_chunk * 16; g.prm = st->d_prm.p + (size_t)p.prm_chunk * 16; g.zero = zero_page();
+        g.n_img = st->n_img; g.hw = st->h * st->w; g.cout = p.cout;
+        g.in_u8 = p.in_u8; g.relu = p.relu; g.out_u8 = p.out_u8; g.elt = p.elt; g.res_relu = p.res_relu;
+        g.coeff_conv = p.coeff_conv; g.scale_conv = p.scale_conv; g.coeff_res = p.coeff_res; g.scale_res = p.scale_res;
+        g.pool_idiv = p.pool_idiv;
+        HIP_TRY(launch_conv1x1_gpool(g, stream));
+        return SABER_HIP_OK;
+    }
     StageKArgs k;
     std::memset(&k, 0, sizeof k);
     k.phases = (const StagePhase*)st->d_phases.p;

@@ -14,7 +14,9 @@
 
 namespace saber_mi355x {
 
-// KSW: 64-byte k-steps per wave (reduction = 4 waves x KSW x 64, zero padded weights beyond Kg)
+typedef unsigned v4u __attribute__((ext_vector_type(4)));
+
+// KSW: 64-byte k-steps per wave (reduction = NW waves x KSW x 64, zero padded weights beyond Kg); NW = 4, with SM 8
 // SM (round 5, round-4 verdict item 2 ii): the Softmax operator that follows the fc (saber_softmax.cpp role; softmax_f32_kernel's
 // arithmetic per row: max, exp(x - max), sum, divide) in the SAME launch - the fc's 63 workgroups each hold 16 of an image's 1000 logits,
 // so the workgroup that arrives LAST on a device-wide counter normalises the rows (one wave per row, 16 logits per lane, wave shuffles).
@@ -35,9 +37,16 @@ struct FcSoftmaxTail {
 // form is the guide's "sc1 payload -> asm vmcnt(0) -> device-scope counter, sc0 sc1 loads on the reader" (MI355X_MICROARCH.md, valid forms).
 // ONE launch of an fc object may be in flight at a time (the counter word belongs to the object): the reference's contract - an impl
 // instance is never called concurrently (threading) - and a Net's / plan's launches are stream-ordered.
+// The SM form runs 512 threads: eight waves split the reduction, and under the tail wave w normalises rows w and w + 8 one after the
+// other - at batch <= 8 ONE row, 16 logits, 16 expf and 16 divisions per lane instead of two rows (the tail is one workgroup on one CU
+// while the rest of the chip is idle: its VALU work is serial time). Lane <-> column map (lane + 64 i), order of the sum (lane-sequential,
+// then the butterfly 32 .. 1), expf and the division are the four-wave form's: the bits of prob are too. Where the row pitch allows it
+// the logits leave as ONE 16-byte write-through store per lane instead of four 4-byte ones (a dword sc1 store costs ~6x a dwordx4's
+// time per byte, and the arrival waits for them): the guide's hand-off table, first row, allows 4-, 8- and 16-byte sc1 stores.
 template <int KSW, bool SM, bool FENCED = false>
 __device__ __forceinline__ void fc_i8_small_body(const ConvKArgs& a, const FcSoftmaxTail& t) {
-    __shared__ v4i red[3][64];
+    constexpr int NW = SM ? 8 : 4;
+    __shared__ v4i red[NW - 1][64];
     __shared__ unsigned last_flag;
     SABER_TL_DECL;
     SABER_TL(0);
@@ -74,9 +83,8 @@ __device__ __forceinline__ void fc_i8_small_body(const ConvKArgs& a, const FcSof
     __syncthreads();
     SABER_TL(3);
     if (wave == 0) {
-        acc += red[0][lane];
-        acc += red[1][lane];
-        acc += red[2][lane];
+#pragma unroll
+        for (int w = 0; w < NW - 1; ++w) acc += red[w][lane];
         // lane: output channels kb..kb+3 of batch row frow
         if (frow < a.M && kb < a.K) {
             float out[4];
@@ -89,8 +97,14 @@ __device__ __forceinline__ void fc_i8_small_body(const ConvKArgs& a, const FcSof
             }
             float* y = (float*)a.y + (size_t)frow * a.K + kb;
             if constexpr (SM) {
-                for (int r = 0; r < 4; ++r)
-                    if (kb + r < a.K) __hip_atomic_store(y + r, out[r], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);      // write-through
+                if (kb + 4 <= a.K && (a.K & 3) == 0) {      // one 16-byte write-through (sc1) store
+                    const __amdgpu_buffer_rsrc_t yr = __builtin_amdgcn_make_buffer_rsrc(a.y, 0, 0xffffffff, 0x00020000);
+                    const v4f o4 = {out[0], out[1], out[2], out[3]};
+                    __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(v4u, o4), yr, (int)(((unsigned)frow * (unsigned)a.K + (unsigned)kb) * 4u), 0, 16);
+                } else {
+                    for (int r = 0; r < 4; ++r)
+                        if (kb + r < a.K) __hip_atomic_store(y + r, out[r], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);      // write-through
+                }
             } else if (kb + 4 <= a.K && (a.K & 3) == 0) {
                 *(float4*)y = make_float4(out[0], out[1], out[2], out[3]);
             } else {
@@ -125,43 +139,34 @@ __device__ __forceinline__ void fc_i8_small_body(const ConvKArgs& a, const FcSof
         SABER_TL(5);
         if (tid == 0) __hip_atomic_store(t.ctr, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);      // for the next launch
         constexpr int PER = 16;                                   // logits per lane: rows of up to 1024 (checked by the launcher)
-        // a wave normalises rows wave, wave + 4 (, + 8, + 12): two rows at a time, BOTH rows' 32 loads in flight before the first use - the
-        // tail is one memory round trip per pair (the first version walked its rows one after the other: 4.5 us for two rows per wave,
-        // profiles/r05/timeline_tail.txt)
-        for (int row0 = wave; row0 < a.M; row0 += 8) {
-            const int row1 = row0 + 4;
-            const bool has1 = row1 < a.M;
-            const float* y0 = (const float*)a.y + (size_t)row0 * a.K;
-            const float* y1 = (const float*)a.y + (size_t)(has1 ? row1 : row0) * a.K;
-            float v0[PER], v1[PER];
+        // wave w normalises rows w and w + 8, one after the other: a row's 16 loads are in flight together, and at batch <= 8 every wave
+        // has one row (the four-wave form held two rows per wave, 32 loads / expf / divisions per lane: profiles/tail/README.md)
+        for (int row = wave; row < a.M; row += NW) {
+            const float* y0 = (const float*)a.y + (size_t)row * a.K;
+            float v[PER];
 #pragma unroll
             for (int i = 0; i < PER; ++i) {
                 const int c = lane + 64 * i;
                 const int cc = c < a.K ? c : a.K - 1;             // (unconditional loads: all in flight together)
-                v0[i] = __hip_atomic_load(y0 + cc, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-                v1[i] = __hip_atomic_load(y1 + cc, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+                v[i] = __hip_atomic_load(y0 + cc, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
             }
-            auto normalise = [&](float (&v)[PER], int row) {
-                float mx = -3.4e38f;
+            float mx = -3.4e38f;
 #pragma unroll
-                for (int i = 0; i < PER; ++i) mx = lane + 64 * i < a.K ? fmaxf(mx, v[i]) : mx;
+            for (int i = 0; i < PER; ++i) mx = lane + 64 * i < a.K ? fmaxf(mx, v[i]) : mx;
 #pragma unroll
-                for (int o = 32; o > 0; o >>= 1) mx = fmaxf(mx, __shfl_xor(mx, o, 64));
-                float sum = 0.f;
+            for (int o = 32; o > 0; o >>= 1) mx = fmaxf(mx, __shfl_xor(mx, o, 64));
+            float sum = 0.f;
 #pragma unroll
-                for (int i = 0; i < PER; ++i) {
-                    v[i] = lane + 64 * i < a.K ? expf(v[i] - mx) : 0.f;
-                    sum += v[i];
-                }
+            for (int i = 0; i < PER; ++i) {
+                v[i] = lane + 64 * i < a.K ? expf(v[i] - mx) : 0.f;
+                sum += v[i];
+            }
 #pragma unroll
-                for (int o = 32; o > 0; o >>= 1) sum += __shfl_xor(sum, o, 64);
-                float* pr = t.prob + (size_t)row * a.K;
+            for (int o = 32; o > 0; o >>= 1) sum += __shfl_xor(sum, o, 64);
+            float* pr = t.prob + (size_t)row * a.K;
 #pragma unroll
-                for (int i = 0; i < PER; ++i)
-                    if (lane + 64 * i < a.K) pr[lane + 64 * i] = v[i] / sum;
-            };
-            normalise(v0, row0);
-            if (has1) normalise(v1, row1);
+            for (int i = 0; i < PER; ++i)
+                if (lane + 64 * i < a.K) pr[lane + 64 * i] = v[i] / sum;
         }
         SABER_TL(6);
         SABER_TL_FLUSH();
@@ -172,7 +177,7 @@ __global__ __launch_bounds__(256) void fc_i8_small_kernel(const ConvKArgs a) {
     fc_i8_small_body<KSW, false>(a, FcSoftmaxTail{nullptr, nullptr});
 }
 template <int KSW, bool FENCED>
-__global__ __launch_bounds__(256) void fc_i8_small_softmax_kernel(const ConvKArgs a, const FcSoftmaxTail t) {
+__global__ __launch_bounds__(512) void fc_i8_small_softmax_kernel(const ConvKArgs a, const FcSoftmaxTail t) {
     fc_i8_small_body<KSW, true, FENCED>(a, t);
 }
 
@@ -467,14 +472,15 @@ hipError_t launch_fc_i8_small(const ConvKArgs& a, hipStream_t s) {
 bool fc_i8_small_softmax_ok(int m, int c, int kg_pad, int k) { return fc_i8_small_ok(m, c, kg_pad) && k >= 1 && k <= 1024; }
 hipError_t launch_fc_i8_small_softmax(const ConvKArgs& a, float* prob, unsigned* ctr, hipStream_t s) {
     if (!fc_i8_small_softmax_ok(a.M, a.C, a.Kg_pad, a.K) || !prob || !ctr) return hipErrorInvalidValue;
-    const int ksw = (a.C + 255) / 256;
-    dim3 grid((a.K + 15) / 16), block(256);
+    const int ksw = (a.C + 255) / 256 / 2;      // k-steps per wave of the eight: the reductions accepted are those of four waves x 2, 4, 8, 16
+    if (((a.C + 255) / 256) & 1) return hipErrorInvalidValue;
+    dim3 grid((a.K + 15) / 16), block(512);
     const FcSoftmaxTail t{prob, ctr};
     static const bool fenced = [] { const char* e = std::getenv("SABER_HIP_FC_SOFTMAX_FENCED"); return e && e[0] == '1'; }();
 #define SABER_FC_CASE(n) case n: if (fenced) hipLaunchKernelGGL((fc_i8_small_softmax_kernel<n, true>), grid, block, 0, s, a, t); \
                                  else hipLaunchKernelGGL((fc_i8_small_softmax_kernel<n, false>), grid, block, 0, s, a, t); break;
     switch (ksw) {      // (ResNet's 2048- and VGG's 4096-long reductions and their neighbours; other lengths run the two launches)
-        SABER_FC_CASE(2) SABER_FC_CASE(4) SABER_FC_CASE(8) SABER_FC_CASE(16)
+        SABER_FC_CASE(1) SABER_FC_CASE(2) SABER_FC_CASE(4) SABER_FC_CASE(8)
     default: return hipErrorInvalidValue;
     }
 #undef SABER_FC_CASE

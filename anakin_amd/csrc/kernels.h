@@ -249,6 +249,23 @@ hipError_t launch_stage_xcd(const StageKArgs& a, size_t lds_bytes, hipStream_t s
 // the same phase code as an ordinary kernel: ONE conv (a.phases[0]), grid = n_img x 32 workgroups - workgroup (img, c) computes
 // output channels [c * 16 NT, (c + 1) * 16 NT) of image img with the whole image in LDS and its weight slice in registers
 hipError_t launch_img_conv(const StageKArgs& a, size_t lds_bytes, hipStream_t s);
+// ONE 1x1 conv 512 -> (1537 .. 2048) channels on <= 64 pixels per image (+ eltwise) with the global average pooling of its output
+// (conv1x1_gpool.hip): everything by value, no phase table. w / prm: the stage packing of that conv (nt = 4, 2 k-steps per wave)
+struct GpoolKArgs {
+    const void* x;               // [n_img][hw][512] 8-bit
+    void* y;                     // [n_img][hw][cout] 8-bit
+    const void* res;             // eltwise: [n_img][hw][cout] s8
+    void* y_pool;                // [n_img][cout] 8-bit of y's dtype
+    const void* w;
+    const void* prm;
+    const void* zero;            // >= 16 zero bytes
+    int n_img, hw, cout;
+    int in_u8, relu, out_u8, elt, res_relu;
+    float coeff_conv, scale_conv, coeff_res, scale_res;
+    float pool_idiv;
+};
+bool conv1x1_gpool_ok(int cin, int cout, int hw);
+hipError_t launch_conv1x1_gpool(const GpoolKArgs& a, hipStream_t s);
 
 // hipcc fetches kernel arguments lazily with scalar loads and places each load near its first use; every batch that is
 // issued after an `s_waitcnt lgkmcnt(0)` is one more DEPENDENT round trip (~0.2-0.25 us, measured) before the kernel's

@@ -333,7 +333,11 @@ __global__ __launch_bounds__(256) void img_conv_kernel(const StageKArgs a) {
     cx.hw = a.H * a.W;
     cx.img0 = (int)(blockIdx.x >> 5);
     cx.img_step = 1 << 30;
+#ifdef SABER_TIMELINE
+    cx.tr = saber_tl_buf ? saber_tl_buf + (size_t)blockIdx.x * 16 : nullptr;      // (scripts/probe/timeline_probe.hip: the phase's stamps 0 .. 7)
+#else
     cx.tr = nullptr;
+#endif
     const int frow = threadIdx.x & 15;
 #pragma unroll
     for (int m = 0; m < 4; ++m) {

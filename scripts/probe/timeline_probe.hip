@@ -29,6 +29,8 @@ __device__ unsigned long long* saber_tl_buf = nullptr;
 #include "../../anakin_amd/csrc/conv1x1_chain.hip"
 #include "../../anakin_amd/csrc/conv_chain_coop.hip"
 #include "../../anakin_amd/csrc/conv_stage_coop.hip"
+#include "../../anakin_amd/csrc/stage_xcd.hip"
+#include "../../anakin_amd/csrc/conv1x1_gpool.hip"
 namespace saber_mi355x {
 void tile_dims(int tile, int* bm_k, int* bn_pix) {
     static const int d[TILE_COUNT][2] = {{32, 32}, {64, 32}, {64, 64}, {128, 64}, {64, 128}, {128, 128}};
@@ -285,6 +287,41 @@ int main(int argc, char** argv) {
             }
             run(P, g.name, blocks, 6, [&] { launch_conv1x1_chain(a, g.c, K1, g.w3 == 2 ? 0 : g.c, tn, 4, split, g.w3 ? 1 : 0, P.st); });
         }
+        return 0;
+    }
+    if (argc > 1 && !strcmp(argv[1], "gpool")) {
+        // res5c_branch2c + res5c + pool5 at batch 8 (1x1 512 -> 2048 on 7x7, eltwise, global average pooling): the stage's phase body behind
+        // an ordinary grid (img_conv_kernel; stamps 0 entry, 1 phase record read, 2 weights + constants requested, 3 (no barrier), 4 image DMA
+        // issued, 5 everything landed, 6 MFMAs done, 7 partial sums exchanged, y and pool stored) against the kernel of its own
+        // (conv1x1_gpool_kernel; 0 entry, 1 all loads requested, 2 landed + barrier, 3 MFMAs done, 4 y stored, 5 pool stored)
+        const int N = 8, HW = 49, CO = 2048;
+        void* x = dalloc((size_t)N * HW * 512, -1);
+        void* res = dalloc((size_t)N * HW * CO, -1);
+        void* y = dalloc((size_t)N * HW * CO, 0);
+        void* yp = dalloc((size_t)N * CO, 0);
+        void* w = dalloc((size_t)CO * 512, -1);
+        void* prm = dalloc((size_t)CO * 12, 0);
+        StagePhase ph;
+        memset(&ph, 0, sizeof ph);
+        ph.type = 3; ph.cin = 512; ph.cout = CO; ph.in_t = 0; ph.out_t = 1; ph.res_t = 2; ph.in_u8 = 1; ph.elt = 1; ph.res_relu = 1;
+        ph.coeff_conv = 20.f; ph.scale_conv = 0.05f; ph.coeff_res = 20.f; ph.scale_res = 0.04f; ph.reload = 1;
+        ph.pch = 33; ph.mg_pch = (unsigned)((0x100000000ull + 32) / 33); ph.red_chunk = ((HW + 1) * 33 + 63) / 64 * 64;
+        ph.pool_t = 3; ph.pool_idiv = 1.f / HW;
+        void* dph;
+        CK(hipMalloc(&dph, sizeof ph));
+        CK(hipMemcpy(dph, &ph, sizeof ph, hipMemcpyHostToDevice));
+        StageKArgs k;
+        memset(&k, 0, sizeof k);
+        k.phases = (const StagePhase*)dph; k.weights = w; k.prm = prm; k.zero = zero; k.n_phases = 1; k.n_img = N; k.H = k.W = 7;
+        k.t[0] = x; k.t[1] = y; k.t[2] = res; k.t[3] = yp;
+        const size_t lds = ((size_t)ph.red_chunk + 4 * 4 * 4 * 64 + 4 * 4 * 4) * 16;
+        run(P, "img_conv_kernel 1x1 512->2048 +elt +gpool b8", N * 32, 8, [&] { (void)launch_img_conv(k, lds, P.st); });
+        GpoolKArgs g;
+        memset(&g, 0, sizeof g);
+        g.x = x; g.y = y; g.res = res; g.y_pool = yp; g.w = w; g.prm = prm; g.zero = zero; g.n_img = N; g.hw = HW; g.cout = CO;
+        g.in_u8 = 1; g.elt = 1; g.res_relu = 1; g.coeff_conv = 20.f; g.scale_conv = 0.05f; g.coeff_res = 20.f; g.scale_res = 0.04f;
+        g.pool_idiv = 1.f / HW;
+        run(P, "conv1x1_gpool_kernel 512->2048 +elt +gpool b8", N * 32, 6, [&] { (void)launch_conv1x1_gpool(g, P.st); });
         return 0;
     }
     if (!stem_only) {   // ---- fc1000 of ResNet50, batch 8: phases 0 entry, 1 loads issued, 2 MFMAs done, 3 after the reduce barrier, 4 stored
