@@ -6,6 +6,7 @@
 //   api_autotune.hip      per-op and per-pair autotuner (cold-L2 timing loop, kernel-reuse preference)
 //   api_ops.hip           fc, INT8 / FP32 GEMM, the streaming operators' wrappers
 //   api_chain.hip         conv1x1 chains (two / three convs in one launch): the table of launch forms, stream repacking, create / run
+//   api_ir.hip            inverted-residual blocks (1x1 expand + depthwise 3x3 + 1x1 project in one launch): eligibility, repacking, create / run
 //   api_sep.hip           separable pairs (depthwise 3x3 + pointwise 1x1 in one launch): eligibility, repacking, create / run
 //   api_net.hip           op-list executor: arena, lanes, hipGraph capture / replay, in-pass timing
 //   api_net_optimize.hip  executor-level fusions (saber_hip_net_optimize)
@@ -278,6 +279,19 @@ struct saber_hip_sep {
     std::string name;               // "sep_dw3x3_pw_i8_<form>" of the selected form
 };
 
+// an inverted-residual block - 1x1 expand, depthwise 3x3, 1x1 project (+ the eltwise sum with the block's input) INT8 convs - in one launch
+// (conv_ir.hip); refers to the three ops, owns both fragment streams, the depthwise weights and every constant table as they were when it was
+// created
+struct saber_hip_ir {
+    saber_hip_conv* expand = nullptr;
+    saber_hip_conv* dw = nullptr;
+    saber_hip_conv* project = nullptr;
+    int form = 0;                   // the selected row of conv_ir.hip's form table (its code)
+    DevBuf<uint8_t> d_we, d_eprm, d_wdw, d_wp, d_pprm;
+    DevBuf<float> d_dw_bias, d_dw_scale;
+    std::string name;               // "ir_expand_dw_project_i8_<form>" of the selected form
+};
+
 struct saber_hip_fc {
     saber_hip_fc_desc d;
     saber_hip_conv* conv = nullptr;
@@ -382,7 +396,7 @@ struct ColdScope {
 namespace saber_api {
 enum OpKind { OP_CONV, OP_CONV_PAIR, OP_FC, OP_QUANT, OP_DEQUANT, OP_TRANSPOSE_IN, OP_ELT_I8, OP_ELT_F32, OP_POOL_I8, OP_POOL_F32, OP_POOL_F32_I8, OP_FC_Q, OP_SOFTMAX, OP_RELU_F32, OP_ACT_F32 };
 // What an op launches in the current selection: DERIVED from the sites' decisions by net_resolve (api_net_optimize.hip), never set elsewhere
-enum Launch { LAUNCH_NONE, LAUNCH_OWN, LAUNCH_CHAIN, LAUNCH_CHAIN3, LAUNCH_STAGE, LAUNCH_STEM_PAIR, LAUNCH_SEP };
+enum Launch { LAUNCH_NONE, LAUNCH_OWN, LAUNCH_CHAIN, LAUNCH_CHAIN3, LAUNCH_STAGE, LAUNCH_STEM_PAIR, LAUNCH_SEP, LAUNCH_IR };
 // A SITE is a group of adjacent ops that can run as one launch. The op that heads a site holds the site's object and its DECISION (*_on: stored
 // as asked by the net_set_* setters and read back by saber_hip_net_get_choice; a decision is never changed to express what another site
 // does); what every op launches, which ops launch nothing and every conv / pair / fc / softmax op's name follow from the decisions in
@@ -436,6 +450,12 @@ struct NetOp {
     saber_hip_sep* sep = nullptr;
     int sep_out = -1;
     bool sep_on = false;
+    // an inverted-residual block (flag 32768, SABER_HIP_NET_INVERTED_RESIDUAL): THIS op is the 1x1 expand conv, the next two are the depthwise
+    // 3x3 and the 1x1 project conv; while ir_on is set its launch covers both, this op's and the depthwise op's output edges are not written
+    // and ir_out is the project op's output
+    saber_hip_ir* ir = nullptr;
+    int ir_out = -1;
+    bool ir_on = false;
     int lane = 0;            // 0: caller's stream, 1: the net's side stream (graph::Lane, operator_func.h:103-114)
     bool record = false;     // an op on the other lane consumes this op's output: record an event after it
     int p[16] = {0};
@@ -483,6 +503,7 @@ struct saber_hip_net {
     std::vector<saber_hip_chain_stage*> owned_stages;
     std::vector<saber_hip_stem_pair*> owned_stem_pairs;
     std::vector<saber_hip_sep*> owned_seps;
+    std::vector<saber_hip_ir*> owned_irs;
 };
 
 // Op-list capture (api_capture.hip; saber_hip_capture_begin / _end): while g_capture is set on the calling thread every
@@ -553,6 +574,12 @@ bool sep_form_valid(const saber_hip_sep* sp, int code);      // the form exists 
 void for_each_sep_form(const saber_hip_sep* sp, const std::function<void(int code)>& fn);      // its forms, in the autotuner's candidate order
 int sep_static_form(const saber_hip_sep* sp);      // the executor's static choice: a form code, or 0 = two launches
 void net_set_sep(saber_hip_net* net, int i, int code);      // api_net_optimize.hip: the site headed by ops[i] on (a valid form code) / off (0)
+// inverted-residual blocks (api_ir.hip)
+bool conv_ir_ok(const saber_hip_conv* expand, const saber_hip_conv* dw, const saber_hip_conv* project, std::string* why);      // a block conv_ir.hip can run
+bool ir_form_valid(const saber_hip_ir* ir, int code);      // the form exists for this block
+void for_each_ir_form(const saber_hip_ir* ir, const std::function<void(int code)>& fn);      // its forms, in the autotuner's candidate order
+int ir_static_form(const saber_hip_ir* ir);      // the executor's static choice: a form code, or 0 = three launches
+void net_set_ir(saber_hip_net* net, int i, int code);      // api_net_optimize.hip: the site headed by ops[i] on (a valid form code) / off (0)
 // api_chain.hip; y_tail: the tail's output - the tail then runs inside the launch (a stage created with one), null: the blocks only
 // y_head: the second output of the stage's head - the pair then runs inside the launch (a stage created with one), x is the PAIR's input and res is not read
 int stage_run(saber_hip_chain_stage* st, const void* x, const void* res, void* const* y1, void* const* y2, hipStream_t s, void* y_tail = nullptr,

@@ -48,6 +48,7 @@ int net_launch(saber_hip_net* net, const NetOp& o, hipStream_t s) {
         }
         case LAUNCH_CHAIN: return saber_hip_conv2d_chain_run(o.chain, T(o.in), T(o.in2), T(o.out), T(o.chain_out), s);
         case LAUNCH_SEP: return saber_hip_conv2d_sep_run(o.sep, T(o.in), nullptr, T(o.sep_out), s);      // the depthwise edge stays in LDS
+        case LAUNCH_IR: return saber_hip_conv2d_ir_run(o.ir, T(o.in), nullptr, nullptr, T(o.ir_out), s);      // both inner edges stay in LDS
         case LAUNCH_OWN: break;
         }
         if (o.conv->gpool) return saber_hip_conv2d_run_gpool(o.conv, T(o.in), T(o.out), T(o.in2), T(o.out2), s);
@@ -312,12 +313,13 @@ int saber_hip_net_compact_arena(saber_hip_net_t* net, const int* keep, int n_kee
         if (o.chain) span(i, 2);
         if (o.stem_pair) span(i, 2);
         if (o.sep) span(i, 2);      // (the one launch reads the depthwise conv's input while it writes the pointwise conv's output)
+        if (o.ir) span(i, 3);       // (the one launch reads the expand conv's input - the residual too - while it writes the project conv's output)
         if ((o.kind == OP_FC || o.kind == OP_FC_Q) && o.out2 >= 0) span(i, 2);
     }
     for (int i = 0; i < nops; ++i) {
         const NetOp& o = net->ops[i];
         const int rd[] = {o.in, o.in2, o.chain3_res};
-        const int wr[] = {o.out, o.out2, o.chain_out, o.chain3_y1, o.chain3_y2, o.chain3_y3, o.stem_y1, o.stem_y2, o.sep_out};
+        const int wr[] = {o.out, o.out2, o.chain_out, o.chain3_y1, o.chain3_y2, o.chain3_y3, o.stem_y1, o.stem_y2, o.sep_out, o.ir_out};
         auto touch = [&](int t) {
             if (t < 0 || t >= nt) return;
             first[t] = std::min(first[t], g_lo[i]);
@@ -474,7 +476,7 @@ int saber_hip_net_set_lane(saber_hip_net_t* net, int index, int lane) {
     if (index < 0 || index >= (int)net->ops.size() || lane < 0 || lane > 1) return fail(SABER_HIP_INVALID_VALUE, "bad op index / lane");
     if (net->lanes_ready) return fail(SABER_HIP_INVALID_VALUE, "lanes are fixed after the first run");
     for (const NetOp& o : net->ops)
-        if (lane && (o.chain || o.chain3 || o.stem_pair || o.sep))
+        if (lane && (o.chain || o.chain3 || o.stem_pair || o.sep || o.ir))
             return fail(SABER_HIP_INVALID_VALUE, "the net has launches that span several ops' tensors (conv1x1 chains, the stem pair, separable sites): lanes must be assigned before saber_hip_net_optimize");
     if (lane) {   // both lanes share the arena's single workspace: an op that uses it stays on the main lane
         const NetOp& o = net->ops[index];
@@ -662,6 +664,8 @@ int saber_hip_net_tensor_unwritten(const saber_hip_net_t* net, int id) {
     for (const NetOp& o : net->ops) {
         const Launch by = o.skip ? net->ops[o.absorbed_by].launch : o.launch;      // the launch that covers this op
         if (o.out == id && (o.launch == LAUNCH_CHAIN3 || o.launch == LAUNCH_STEM_PAIR || o.launch == LAUNCH_SEP || (o.chain3 && by == LAUNCH_STAGE))) return 1;
+        // both inner edges of an inverted-residual block while its one launch is selected: the expand op's and the depthwise op's outputs
+        if (o.out == id && (o.launch == LAUNCH_IR || (o.skip && by == LAUNCH_IR && (int)(&o - net->ops.data()) == o.absorbed_by + 1))) return 1;
         // the first block's shortcut while the pair that makes it runs as the stage launch's head: it stays in LDS
         if (o.launch == LAUNCH_STAGE && o.head_on && o.chain3_res == id) return 1;
     }
@@ -725,6 +729,7 @@ void saber_hip_net_destroy(saber_hip_net_t* net) {
     for (saber_hip_chain_stage* st : net->owned_stages) saber_hip_conv2d_stage_destroy(st);
     for (saber_hip_chain* c : net->owned_chains) saber_hip_conv2d_chain_destroy(c);
     for (saber_hip_sep* sp : net->owned_seps) saber_hip_conv2d_sep_destroy(sp);
+    for (saber_hip_ir* ir : net->owned_irs) saber_hip_conv2d_ir_destroy(ir);
     for (saber_hip_conv* c : net->owned) saber_hip_conv2d_destroy(c);
     for (hipEvent_t e : net->ev_op)
         if (e) (void)hipEventDestroy(e);

@@ -13,7 +13,11 @@ static saber_hip_conv* net_op_conv(saber_hip_net* net, int index) {
 }
 // bits 0..23: saber_hip_conv2d_get_tile of the op; chain heads add bit 28 (a chain decision is recorded) and the chain's
 // pixel fragments in bits 24..27 (0: run as two launches). A depthwise op never heads a chain: bits 28 AND 29 together on it say that a
-// separable decision is recorded (flag 16384), bits 24..27 then hold the separable launch's form code (0: two launches)
+// separable decision is recorded (flag 16384), bits 24..27 then hold the separable launch's form code (0: two launches).
+// Bit 31 WITHOUT bit 30 on the 1x1 expand op of an inverted-residual site (flag 32768): a block decision is recorded, bits 24..27 hold the block
+// launch's form code (0: three launches). No op reports that pattern otherwise: bit 31 is the tail bit of a stage head and comes only with
+// bit 30, a plain 1x1 conv without residual heads no chain (bit 28), leads none (bit 29) and is no depthwise op (28 and 29) - and a word
+// with bit 31 but not bit 30 changed nothing on any op before the flag existed.
 int saber_hip_net_get_choice(saber_hip_net_t* net, int index) {
     saber_hip_conv* c = net_op_conv(net, index);
     int choice = (c && !c->pool_fused && (c->algo <= ALGO_IGEMM_F32 || dw_ok(c) || group_ok(c))) ? saber_hip_conv2d_get_tile(c) : 0;
@@ -22,6 +26,7 @@ int saber_hip_net_get_choice(saber_hip_net_t* net, int index) {
     if (o.chain) choice |= (1 << 28) | ((o.chain_on ? o.chain->form.code : 0) << 24);
     if (o.chain3) choice |= (1 << 29) | ((o.led_on ? o.chain3->form.code : 0) << 24);      // (a strided head reports its own decision while it runs as a tail)
     if (o.sep) choice |= (3 << 28) | ((o.sep_on ? o.sep->form : 0) << 24);
+    if (o.ir) choice |= (int)0x80000000u | ((o.ir_on ? o.ir->form : 0) << 24);
     if (o.stage && o.stage_on) choice |= 1 << 30;      // this op launches its whole stage
     if (o.stage && o.stage_on && o.tail_on) choice |= (int)0x80000000u;      // ... and the strided head behind it as the launch's tail
     // bit 29 on a sibling-pair op (which never leads a chain: bits 24..29 mean nothing else there): the pair runs as the HEAD of the stage launch behind it
@@ -38,6 +43,16 @@ int saber_hip_net_stage_head(const saber_hip_net_t* net, int index) {
 }
 int saber_hip_net_set_choice(saber_hip_net_t* net, int index, int choice) {
     saber_hip_conv* c = net_op_conv(net, index);
+    // the block decision this choice carries (bit 31 without bit 30 on the expand op of a site); a code with no form for that block is refused
+    // before anything changes. An expand op on the direct path (Cin % 16 == 8) has no selection of its own: the decision is all its word holds
+    const bool ir_bits = c && net->ops[index].ir && ((unsigned)choice >> 30) == 2u;
+    const int ir_tn = (choice >> 24) & 15;
+    if (ir_bits && ir_tn && !ir_form_valid(net->ops[index].ir, ir_tn)) return saber_hip_conv2d_ir_set_tile(net->ops[index].ir, ir_tn);      // (its status and message)
+    if (ir_bits && !(choice & 0xffffff)) {
+        net_set_ir(net, index, ir_tn);
+        net_drop_graph(net);
+        return SABER_HIP_OK;
+    }
     if (!c || !choice || c->pool_fused || (c->algo > ALGO_IGEMM_F32 && !dw_ok(c) && !group_ok(c))) return SABER_HIP_OK;
     if (net->reproducible_fp32 && !c->is_i8) return SABER_HIP_OK;      // flag 8192: a restored selection does not move FP32 ops either
     if (net->ops[index].kind == OP_CONV_PAIR && index > 0 && net->ops[index - 1].stem_pair) return SABER_HIP_OK;      // no kernel of its own (flag 512)
@@ -75,6 +90,7 @@ int saber_hip_net_set_choice(saber_hip_net_t* net, int index, int choice) {
     if (o.stage) net_set_tail(net, index, tail_on);
     if (o.head_of >= 0) net_set_head(net, o.head_of, (chain_bits & 32) && !net->shared_device);
     if (sep_bits) net_set_sep(net, index, tn);      // (a choice without the bits leaves the site as it is)
+    if (ir_bits) net_set_ir(net, index, ir_tn);
     net_resolve(net);      // (the names follow the kernel selection)
     net_drop_graph(net);
     return SABER_HIP_OK;
@@ -324,6 +340,30 @@ int saber_hip_net_autotune(saber_hip_net_t* net, saber_hip_stream_t stream, int 
             if (rt == SABER_HIP_OK && us < best) { best = us; best_code = code; }
         });
         net_set_sep(net, (int)i, best_code);
+        rc = run_all();   // every written output holds the selected form's result
+        if (rc) return rc;
+    }
+    // inverted-residual sites (flag 32768): the three tuned launches against every form of the one launch, cold L2, on the real tensors
+    for (size_t i = 0; i + 2 < net->ops.size(); ++i) {
+        NetOp& E = net->ops[i];
+        if (!E.ir) continue;
+        hipStream_t s = (hipStream_t)stream;
+        auto run_all = [&]() -> int { return net_launch(net, net->ops[i], s) | net_launch(net, net->ops[i + 1], s) | net_launch(net, net->ops[i + 2], s); };
+        auto timed = [&](float* t) { return time_enqueued(s, run_all, 20, t); };
+        float best = 0.f;
+        int best_code = 0;
+        net_set_ir(net, (int)i, 0);
+        int rc = timed(&best);
+        if (rc) return rc;
+        log_cand(E.conv, "separate", best);
+        for_each_ir_form(E.ir, [&](int code) {
+            float us = -1.f;
+            net_set_ir(net, (int)i, code);
+            const int rt = timed(&us);
+            log_cand(E.conv, E.name.substr(5), us);
+            if (rt == SABER_HIP_OK && us < best) { best = us; best_code = code; }
+        });
+        net_set_ir(net, (int)i, best_code);
         rc = run_all();   // every written output holds the selected form's result
         if (rc) return rc;
     }

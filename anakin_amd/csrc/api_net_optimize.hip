@@ -24,8 +24,9 @@
 void net_resolve(saber_hip_net* net) {
     std::vector<NetOp>& ops = net->ops;
     const int n = (int)ops.size();
-    enum { IN_CHAIN, IN_STAGE, IN_STEM, IN_SEP };
-    static const char* const covered[] = {"conv:(in the chain launch)", "conv:(in the stage launch)", "conv:(in the stem launch)", "conv:(in the separable launch)"};
+    enum { IN_CHAIN, IN_STAGE, IN_STEM, IN_SEP, IN_IR };
+    static const char* const covered[] = {"conv:(in the chain launch)", "conv:(in the stage launch)", "conv:(in the stem launch)", "conv:(in the separable launch)",
+                                          "conv:(in the inverted-residual launch)"};
     std::vector<int> in(n, IN_CHAIN);
     for (NetOp& o : ops) {
         o.launch = LAUNCH_OWN;
@@ -67,6 +68,10 @@ void net_resolve(saber_hip_net* net) {
         } else if (o.sep && o.sep_on) {
             o.launch = LAUNCH_SEP;
             absorb(i + 1, i, IN_SEP);
+        } else if (o.ir && o.ir_on && i + 2 < n) {      // (no op of an inverted-residual site belongs to another site: formed that way)
+            o.launch = LAUNCH_IR;
+            absorb(i + 1, i, IN_IR);
+            absorb(i + 2, i, IN_IR);
         }
     }
     for (int i = 0; i < n; ++i) {
@@ -86,6 +91,7 @@ void net_resolve(saber_hip_net* net) {
             case LAUNCH_CHAIN: o.name = "conv:" + chain_form_name(o.chain); break;
             case LAUNCH_CHAIN3: o.name = "conv:" + chain_form_name(o.chain3); break;
             case LAUNCH_SEP: o.name = std::string("conv:") + saber_hip_conv2d_sep_algo(o.sep); break;
+            case LAUNCH_IR: o.name = std::string("conv:") + saber_hip_conv2d_ir_algo(o.ir); break;
             case LAUNCH_STEM_PAIR: o.name = "conv:" + own + "+pair1x1_" + std::to_string(o.stem_pair->a->d.k) + "+" + std::to_string(o.stem_pair->b->d.k); break;
             case LAUNCH_STAGE:
                 o.name = std::string(o.head_on && !kept ? "conv:[pair1x1]+stage_c" : "conv:stage_c") + std::to_string(o.stage->c1) + "_" + std::to_string(o.stage_n) + "x[conv3x3+chain1x1]_2x16" +
@@ -146,6 +152,15 @@ void net_set_sep(saber_hip_net* net, int i, int code) {
     D.sep_on = code != 0;
     net_resolve(net);
 }
+// The inverted-residual site headed by ops[i] (NetOp::ir): code = a valid form of the block -> the one launch with that form; 0 -> the three ops launch on
+// their own again.
+void net_set_ir(saber_hip_net* net, int i, int code) {
+    NetOp& E = net->ops[i];
+    if (!E.ir || i + 2 >= (int)net->ops.size()) return;
+    if (code && saber_hip_conv2d_ir_set_tile(E.ir, code) != SABER_HIP_OK) code = 0;
+    E.ir_on = code != 0;
+    net_resolve(net);
+}
 static int clone_conv_i8(const saber_hip_conv* src, const saber_hip_conv_desc& d, saber_hip_conv** out) {
     int rc = saber_hip_conv2d_create(&d, out);
     if (rc) return rc;
@@ -187,10 +202,15 @@ int saber_hip_net_optimize(saber_hip_net_t* net, int flags) {
             if (!dead[i] && (ops[i].out == t || ops[i].out2 == t)) return i;
         return -1;
     };
-    // an op of a separable site (flag 16384 in an earlier call) keeps its conv: the site's object was made from it
+    // an op of an inverted-residual site (flag 32768 in this or an earlier call): the expand op or one of the two behind it
+    auto in_ir = [&](const NetOp& o) {
+        const size_t i = (size_t)(&o - ops.data());
+        return o.ir != nullptr || (i > 0 && i < ops.size() && ops[i - 1].ir != nullptr) || (i > 1 && i < ops.size() && ops[i - 2].ir != nullptr);
+    };
+    // an op of a separable site (flag 16384 in an earlier call) or of an inverted-residual site keeps its conv: the site's object was made from it
     auto in_sep = [&](const NetOp& o) {
         const size_t i = (size_t)(&o - ops.data());
-        return o.sep != nullptr || (i > 0 && i < ops.size() && ops[i - 1].sep != nullptr);
+        return o.sep != nullptr || (i > 0 && i < ops.size() && ops[i - 1].sep != nullptr) || in_ir(o);
     };
     auto plain_i8_conv = [&](const NetOp& o) {
         return !in_sep(o) && o.kind == OP_CONV && o.conv && o.conv->is_i8 && o.conv->weights_set && o.conv->epi == EPI_I8_CONV &&
@@ -251,7 +271,7 @@ int saber_hip_net_optimize(saber_hip_net_t* net, int flags) {
                 if (dead[j]) continue;
                 if (ops[j].out == q.in || ops[j].out2 == q.in) break;            // the pooling's source is rewritten first
                 if (ops[j].in2 == q.out && ops[j].kind == OP_CONV && ops[j].conv && !ops[j].chain && !ops[j].chain3 &&
-                    ops[j].conv->d.res_mode == SABER_HIP_RES_ELTWISE && ops[j].conv->d.res_stride <= 1 && ops[j].lane == q.lane)
+                    ops[j].conv->d.res_mode == SABER_HIP_RES_ELTWISE && ops[j].conv->d.res_stride <= 1 && ops[j].lane == q.lane && !in_ir(ops[j]))
                     c = (int)j;
                 else if (ops[j].in == q.out || ops[j].in2 == q.out) break;       // some other reader
             }
@@ -418,6 +438,41 @@ int saber_hip_net_optimize(saber_hip_net_t* net, int flags) {
     bool two_lanes = false;
     for (const NetOp& o : ops) two_lanes |= o.lane != 0;
     if (two_lanes) flags &= ~(16 | 32);
+    // ---- 32768 (SABER_HIP_NET_INVERTED_RESIDUAL): three consecutive lane-0 ops - a 1x1 expand conv, the depthwise 3x3 conv that alone reads it,
+    // the 1x1 project conv that alone reads that (MobileNet-v2's blocks) - that saber_hip_conv2d_ir_create accepts -> a site of the one-launch
+    // form (conv_ir.hip). Where the project conv carries the fused eltwise (flag 1 ran first) its residual must be the expand conv's input.
+    // All three ops stay; which sites are on is ir_static_form's choice until the autotuner has timed every form against the three launches.
+    // No workgroup of that kernel depends on another: allowed on a shared device. NO OP BELONGS TO TWO SITES: ops that head or follow a chain, a
+    // separable or a stem site are skipped here, and the chain / separable formation below skips the ops a block site holds - so whichever flag
+    // comes later finds the ops taken and counts nothing for them. Counted: the sites formed (each removes two launches while a form is selected).
+    if ((flags & SABER_HIP_NET_INVERTED_RESIDUAL) && !two_lanes) {
+        auto taken = [&](size_t j) {      // heads another site, or is covered by the site of an op in front of it
+            const NetOp& o = ops[j];
+            if (o.chain || o.chain3 || o.stem_pair || o.sep || o.stage || in_ir(o)) return true;
+            if (j > 0 && (ops[j - 1].chain || ops[j - 1].chain3 || ops[j - 1].stem_pair || ops[j - 1].sep)) return true;
+            return j > 1 && ops[j - 2].chain3 != nullptr;
+        };
+        for (size_t i = 0; i + 2 < ops.size(); ++i) {
+            NetOp& E = ops[i];
+            NetOp& D = ops[i + 1];
+            NetOp& P = ops[i + 2];
+            if (E.kind != OP_CONV || D.kind != OP_CONV || P.kind != OP_CONV || !E.conv || !D.conv || !P.conv || E.skip || D.skip || P.skip || E.lane ||
+                D.lane || P.lane || E.in2 >= 0 || D.in2 >= 0 || E.out2 >= 0 || D.out2 >= 0 || P.out2 >= 0 || D.in != E.out || P.in != D.out)
+                continue;
+            if (taken(i) || taken(i + 1) || taken(i + 2)) continue;
+            if (readers(E.out) != 1 || readers(D.out) != 1) continue;
+            const bool elt = P.conv->d.res_mode == SABER_HIP_RES_ELTWISE;
+            if (elt ? P.in2 != E.in : P.in2 >= 0) continue;      // the fused eltwise's residual is the block's input
+            saber_hip_ir* ir = nullptr;
+            if (saber_hip_conv2d_ir_create(E.conv, D.conv, P.conv, &ir) != SABER_HIP_OK) continue;      // not a block the kernel takes
+            net->owned_irs.push_back(ir);
+            E.ir = ir;
+            E.ir_out = P.out;
+            net_set_ir(net, (int)i, ir_static_form(ir));
+            ++removed;
+            i += 2;
+        }
+    }
     // ---- 16384 (SABER_HIP_NET_SEPARABLE): a depthwise 3x3 conv + the 1x1 conv that alone reads it, the NEXT op (MobileNet's separable pairs)
     // -> a site of the one-launch form (conv_sep.hip). Both ops stay; which sites are on is sep_static_form's choice until the autotuner has
     // timed every form against the two launches. No workgroup of that kernel depends on another: allowed on a shared device. Counted: the
@@ -427,7 +482,7 @@ int saber_hip_net_optimize(saber_hip_net_t* net, int flags) {
             NetOp& D = ops[i];
             NetOp& P = ops[i + 1];
             if (D.kind != OP_CONV || P.kind != OP_CONV || !D.conv || !P.conv || D.sep || D.skip || P.skip || D.lane || P.lane || D.chain || D.chain3 ||
-                D.stem_pair || P.chain || P.chain3 || P.stem_pair || P.sep || D.in2 >= 0 || P.in2 >= 0 || D.out2 >= 0 || P.out2 >= 0 || P.in != D.out)
+                D.stem_pair || P.chain || P.chain3 || P.stem_pair || P.sep || in_ir(D) || in_ir(P) || D.in2 >= 0 || P.in2 >= 0 || D.out2 >= 0 || P.out2 >= 0 || P.in != D.out)
                 continue;
             if (!D.conv->is_i8 || !dw_ok(D.conv)) continue;
             if (readers(D.out) != 1) continue;
@@ -446,7 +501,7 @@ int saber_hip_net_optimize(saber_hip_net_t* net, int flags) {
             NetOp& A = ops[i];
             NetOp& B = ops[i + 1];
             if (A.kind != OP_CONV || B.kind != OP_CONV || !A.conv || !B.conv || A.chain || A.skip || B.chain || A.lane || B.lane ||
-                A.chain3 || B.chain3)
+                A.chain3 || B.chain3 || in_ir(A) || in_ir(B))
                 continue;
             if (A.conv->d.res_mode != SABER_HIP_RES_ELTWISE || B.in != A.out || A.in2 < 0 || B.in2 >= 0) continue;
             saber_hip_chain* ch = nullptr;
@@ -482,7 +537,7 @@ int saber_hip_net_optimize(saber_hip_net_t* net, int flags) {
             NetOp& Hd = ops[i];
             NetOp& A = ops[i + 1];
             if (A.chain || A.skip || A.kind != OP_CONV || !A.conv || A.conv->d.res_mode != SABER_HIP_RES_ELTWISE || A.in2 < 0 || A.lane ||
-                Hd.kind != OP_CONV || !Hd.conv || Hd.chain3 || Hd.chain || Hd.skip || Hd.lane || Hd.in2 >= 0 || A.in != Hd.out)
+                Hd.kind != OP_CONV || !Hd.conv || Hd.chain3 || Hd.chain || Hd.skip || Hd.lane || Hd.in2 >= 0 || A.in != Hd.out || in_ir(Hd) || in_ir(A))
                 continue;
             if (readers(Hd.out) != 1) continue;
             saber_hip_chain* ch = nullptr;

@@ -380,6 +380,43 @@ void sep_pw_pack(const int8_t* w_kc, int k, int c, std::vector<uint8_t>& out);  
 hipError_t conv_sep_prepare();      // per device, once: the kernels may use more than 64 KB of LDS
 hipError_t launch_conv_sep(int code, bool in_u8, const SepKArgs& a, hipStream_t s);
 
+// Inverted-residual block (MobileNet-v2): 1x1 expand + depthwise 3x3 + 1x1 linear project (+ the eltwise sum with the block's input) INT8 in
+// one launch (conv_ir.hip). A workgroup owns a tile of output pixels of one image and ALL of Cout; per chunk of 64 expanded channels it
+// expands the tile's input halo on the i8 matrix cores into LDS, runs the depthwise conv from there into LDS and adds one k-step of the
+// project conv to accumulators that live across the chunks. Cin % 8 == 0, 8 <= Cin <= 192, Ce % 16 == 0, Ce <= 1024, Cout % 8 == 0, Cout <= 320.
+struct IrKArgs {
+    const void* x;        // [N][H][W][Cin] s8 | u8
+    const void* we;       // the expand conv's weights in fragment order (ir_pack of [Ce][Cin])
+    const void* eprm;     // its {scale[4], bias'[4], comp[4]} per 4 channels, padded to a multiple of 64 channels
+    const void* wdw;      // the depthwise conv's weights [tap][Ce] s8
+    const float* dw_bias; // its bias' [Ce] (zeros stand for "no bias") and scale [Ce]
+    const float* dw_scale;
+    const void* wp;       // the project conv's weights in fragment order (ir_pack of [Cout][Ce])
+    const void* pprm;     // its {scale[4], bias'[4], comp[4]} per 4 channels, padded to a multiple of 64 channels
+    void* y_e;            // [N][H][W][Ce] u8, or null: the expanded edge is not written
+    void* y_d;            // [N][OH][OW][Ce] u8, or null: the depthwise edge is not written
+    void* y;              // [N][OH][OW][Cout] s8 | u8
+    int N, H, W, Cin, Ce, OH, OW, Cout;
+    int stride;           // of the depthwise conv (1 | 2; pad 1)
+    int th, tw, nf;       // the tile: th x tw output pixels in nf = ceil(th * tw / 16) fragments of 16 (pixel p = row p / tw, column p % tw)
+    int hh, hw, hpf;      // its input halo: ((th - 1) * stride + 3) x ((tw - 1) * stride + 3) pixels in hpf fragments of 16
+    int tiles_x, tiles_per_img;
+    int out_u8, p_relu;   // the project conv's output type and relu (without the eltwise)
+    int elt, res_relu;    // the fused eltwise with x as the residual (s8, Cin == Cout, stride 1); relu after the sum
+    float coeff_conv, scale_conv, coeff_res, scale_res;
+};
+// the launch forms: code 1 .. IR_MAX_CODE -> the tile of a block of this shape, false: no such form for it (or its LDS footprint is above
+// IR_LDS_LIMIT: two workgroups per CU must fit)
+constexpr int IR_MAX_CODE = 7;
+constexpr int IR_MAX_UNITS = 20;      // (64 output channels x 16 pixels) accumulator units per workgroup: 5 per wave
+constexpr size_t IR_LDS_LIMIT = 80 * 1024 - 64;
+struct IrGeom { int th, tw, nf, hh, hw, hpf, tiles_x, tiles_y; size_t lds; };
+const char* conv_ir_form_name(int code);      // "" where the table has no such code
+bool conv_ir_geom(int code, int cin, int ce, int cout, int oh, int ow, int stride, IrGeom* g);
+void ir_pack(const int8_t* w_kc, int k, int c, std::vector<uint8_t>& out);      // [ceil(K / 64)][ceil(C / 64)][4][64 lanes][16], zero beyond K and beyond C
+hipError_t conv_ir_prepare();      // per device, once: the kernels may use more than 64 KB of LDS
+hipError_t launch_conv_ir(int code, bool in_u8, const IrKArgs& a, hipStream_t s);      // sets the tile fields of `a` from the form
+
 // reads `bytes` of device memory through every XCD (autotuning: the timed launch then finds none of its operands in
 // an L2, which is how it runs inside the op list)
 hipError_t launch_l2_flush(const void* buf, size_t bytes, unsigned* sink, hipStream_t s);

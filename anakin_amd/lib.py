@@ -34,6 +34,8 @@ SYMBOLS = [
     "saber_hip_conv2d_stem_pair_create", "saber_hip_conv2d_stem_pair_destroy", "saber_hip_conv2d_stem_pair_run",
     "saber_hip_conv2d_sep_create", "saber_hip_conv2d_sep_run", "saber_hip_conv2d_sep_set_tile", "saber_hip_conv2d_sep_get_tile",
     "saber_hip_conv2d_sep_algo", "saber_hip_conv2d_sep_destroy",
+    "saber_hip_conv2d_ir_create", "saber_hip_conv2d_ir_run", "saber_hip_conv2d_ir_set_tile", "saber_hip_conv2d_ir_get_tile",
+    "saber_hip_conv2d_ir_algo", "saber_hip_conv2d_ir_destroy",
     "saber_hip_conv2d_set_global_pooling", "saber_hip_conv2d_run_gpool",
     "saber_hip_stage_create", "saber_hip_stage_num_tensors", "saber_hip_stage_run", "saber_hip_stage_status", "saber_hip_stage_trace", "saber_hip_stage_destroy",
     "saber_hip_fc_create", "saber_hip_fc_set_weights", "saber_hip_fc_workspace_bytes", "saber_hip_fc_run",
@@ -151,6 +153,14 @@ def load():
     lib.saber_hip_conv2d_sep_algo.restype = C.c_char_p
     lib.saber_hip_conv2d_sep_destroy.argtypes = [P]
     lib.saber_hip_conv2d_sep_destroy.restype = None
+    lib.saber_hip_conv2d_ir_create.argtypes = [P, P, P, C.POINTER(P)]
+    lib.saber_hip_conv2d_ir_run.argtypes = [P, P, P, P, P, P]
+    lib.saber_hip_conv2d_ir_set_tile.argtypes = [P, I]
+    lib.saber_hip_conv2d_ir_get_tile.argtypes = [P]
+    lib.saber_hip_conv2d_ir_algo.argtypes = [P]
+    lib.saber_hip_conv2d_ir_algo.restype = C.c_char_p
+    lib.saber_hip_conv2d_ir_destroy.argtypes = [P]
+    lib.saber_hip_conv2d_ir_destroy.restype = None
     lib.saber_hip_conv2d_set_global_pooling.argtypes = [P]
     lib.saber_hip_conv2d_run_gpool.argtypes = [P, P, P, P, P, P]
     lib.saber_hip_stage_create.argtypes = [C.POINTER(StagePhase), I, C.POINTER(P)]

@@ -434,6 +434,38 @@ class SaberConvSep:
             pass
 
 
+class SaberConvIR:
+    """A 1x1 expand, a depthwise 3x3 and a 1x1 project INT8 conv in ONE launch (saber_hip_conv2d_ir_create): MobileNet-v2's inverted-residual
+    block. dispatch(x, y, y_expand=None, y_dw=None): the inner edges only when they are wanted; where the project conv carries the fused eltwise
+    its residual is x. The outputs hold the bits of dispatching the three operators one after the other (net.cpp:417-509). The object keeps
+    the weights the ops had when it was made."""
+
+    def __init__(self, expand, dw, project):
+        self.ops = (expand, dw, project)             # keep them alive: the object refers to them
+        self.h = C.c_void_p()
+        L.check(L.load().saber_hip_conv2d_ir_create(expand.h, dw.h, project.h, C.byref(self.h)))
+
+    def dispatch(self, x, y, y_expand=None, y_dw=None):
+        L.check(L.load().saber_hip_conv2d_ir_run(self.h, _p(x), _p(y_expand), _p(y_dw), _p(y), _stream()))
+        return y
+
+    def set_tile(self, code):
+        L.check(L.load().saber_hip_conv2d_ir_set_tile(self.h, code))
+
+    def tile(self):
+        return L.load().saber_hip_conv2d_ir_get_tile(self.h)
+
+    def algo(self):
+        return L.load().saber_hip_conv2d_ir_algo(self.h).decode()
+
+    def __del__(self):
+        try:
+            if self.h:
+                L.load().saber_hip_conv2d_ir_destroy(self.h)
+        except Exception:
+            pass
+
+
 class SaberStage:
     """XCD-resident stage (saber_hip_stage_create): `phases` = [(conv, in_slot, out_slot, res_slot | -1), ...] run as ONE
     persistent launch, image i on XCD i % 8; dispatch(tensors) takes the device tensors by slot. Every output slot holds

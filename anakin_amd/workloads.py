@@ -105,6 +105,38 @@ def mobilenet_v1_spec():
     return L
 
 
+def mobilenet_v2_spec():
+    """MobileNet v2 (width 1.0, 224 x 224): conv1 3x3 / 2, 17 inverted-residual blocks `1x1 expand -> 3x3 depthwise -> 1x1 linear project`
+    from the (t, c, n, s) table of the paper, a 1x1 conv 320 -> 1280, global average pooling, fc, softmax. The t = 1 block has no expand
+    conv; expand and depthwise convs have relu, the project conv has none; a block with stride 1 and cin == cout ends in the eltwise sum
+    of the project conv and the block's input, without relu (`block_<stage>_<i>`; the project conv carries `eltwise=<that name>`).
+    The activation is ReLU, NOT ReLU6: that is what the published Caffe MobileNet-v2 has, which the reference's converter and
+    benchmark consume, and the only activation of the INT8 route (saber_hip_act: NONE | RELU, what the x86 path implements)."""
+    L = [dict(kind="conv", name="conv1", src="data", cin=3, cout=32, k=3, stride=2, pad=1, relu=True)]
+    prev, cin = "conv1", 32
+    for si, (t, c, n, s) in enumerate([(1, 16, 1, 1), (6, 24, 2, 2), (6, 32, 3, 2), (6, 64, 4, 2), (6, 96, 3, 1), (6, 160, 3, 2), (6, 320, 1, 1)]):
+        for bi in range(n):
+            tag, stride, ce, src = "conv%d_%d" % (si + 2, bi + 1), (s if bi == 0 else 1), cin * t, prev
+            if t != 1:
+                L.append(dict(kind="conv", name=tag + "_expand", src=src, cin=cin, cout=ce, k=1, stride=1, pad=0, relu=True))
+                src = tag + "_expand"
+            L.append(dict(kind="conv", name=tag + "_dwise", src=src, cin=ce, cout=ce, k=3, stride=stride, pad=1, relu=True, group=ce))
+            L.append(dict(kind="conv", name=tag + "_linear", src=tag + "_dwise", cin=ce, cout=c, k=1, stride=1, pad=0, relu=False))
+            if stride == 1 and cin == c:
+                blk = "block_%d_%d" % (si + 2, bi + 1)
+                L[-1]["eltwise"] = blk
+                L.append(dict(kind="eltwise", name=blk, a=tag + "_linear", b=prev, relu=False))
+                prev = blk
+            else:
+                prev = tag + "_linear"
+            cin = c
+    L.append(dict(kind="conv", name="conv9", src=prev, cin=cin, cout=1280, k=1, stride=1, pad=0, relu=True))
+    L.append(dict(kind="gpool", name="pool9", src="conv9"))
+    L.append(dict(kind="fc", name="fc10", src="pool9", cin=1280, cout=1000))
+    L.append(dict(kind="softmax", name="prob", src="fc10"))
+    return L
+
+
 def conv_macs(spec, hw=224):
     """Algorithmic MACs per image of the conv + fc layers."""
     sizes, total = {"data": hw}, 0
@@ -224,7 +256,7 @@ def fold_bn(w, bias, bn_scale, eps, mean, var, scale_w, scale_b):
 def build_model(name="resnet50", seed=42):
     """Seeded weights: conv ~ N(0, sqrt(2/(C*k*k))), BN gamma U(.5,1.5), beta/mean U(-.1,.1), var U(.5,1.5)."""
     spec = {"resnet50": lambda: resnet_spec(50), "resnet101": lambda: resnet_spec(101), "vgg16": vgg16_spec,
-            "mobilenet_v1": mobilenet_v1_spec, "resnext50_32x4d": resnext_spec}[name]()
+            "mobilenet_v1": mobilenet_v1_spec, "mobilenet_v2": mobilenet_v2_spec, "resnext50_32x4d": resnext_spec}[name]()
     params, raw = {}, {}          # raw: the BatchNorm / Scale blobs before folding (what a model file holds)
     for idx, l in enumerate(spec):
         rng = np.random.default_rng(seed + idx)
@@ -271,7 +303,9 @@ def calibrate(model, x):
             elif kd == "pool":
                 y = Fn.max_pool2d(t[l["src"]], l["win"], l["stride"], l["pad"], ceil_mode=not l.get("floor", False))
             elif kd == "eltwise":
-                y = torch.relu(t[l["a"]] + t[l["b"]])
+                y = t[l["a"]] + t[l["b"]]
+                if l["relu"]:
+                    y = torch.relu(y)
             elif kd == "gpool":
                 y = t[l["src"]].mean((2, 3), keepdim=True)
             elif kd == "fc":
@@ -292,7 +326,7 @@ def _out_hw(h, k, s, p):
 
 
 def build_int8_net(model, scales, batch, hw=224, fuse=True, chain=2, stage=True, stem_pair=True, head_pair=False, shared_device=False,
-                   fc_softmax=True, absorb_pool=True, separable=False, before_finalize=None, **legacy):
+                   fc_softmax=True, absorb_pool=True, separable=False, inverted=False, before_finalize=None, **legacy):
     """ResNet INT8 op list on the device (see the module docstring for the dtype rules): ONE op per reference operator, exactly the list
     `model["spec"]` holds (workloads.framework_spec: what the reference's own optimiser emits) - and, with `fuse`, handed to the C++ host
     side (saber_hip_net_optimize, the product's only executor-level fuser) which finds conv + eltwise, sibling pairs, conv + pooling,
@@ -312,6 +346,10 @@ def build_int8_net(model, scales, batch, hw=224, fuse=True, chain=2, stage=True,
     separable (opt-in): a depthwise 3x3 conv and the 1x1 conv that alone reads it (MobileNet's separable pairs) become sites of the one-launch
     form (flag SABER_HIP_NET_SEPARABLE = 16384, after the flag-15 pass): net.separated counts them. Which sites run fused is the static
     rule's choice, then the autotuner's (profiles/sep/README.md); the default builds exactly the list it built before.
+    inverted (opt-in): a 1x1 expand conv, the depthwise 3x3 conv and the 1x1 project conv behind it (MobileNet-v2's inverted-residual blocks,
+    with the block's fused eltwise sum) become sites of the one-launch form (flag SABER_HIP_NET_INVERTED_RESIDUAL = 32768, after the flag-15
+    pass and BEFORE the separable and chain flags, which skip the ops a block site holds): net.inverted counts them. Which sites run fused is
+    the static rule's choice, then the autotuner's (profiles/ir/README.md); the default builds exactly the list it built before.
     before_finalize (optional): called with the net once the op list has its final form, just before finalize() - the place to bind
     tensors to caller-owned memory (Net.bind; net.tensors maps every edge name to its id).
     (The Python fuser of rounds 1 - 5 lives in tests/py_fuser.py: test infrastructure.)"""
@@ -381,9 +419,11 @@ def build_int8_net(model, scales, batch, hw=224, fuse=True, chain=2, stage=True,
     if shared_device:
         net.optimize(2048)           # (sticks to the net: every later optimize / autotune / set_choices call honours it)
         stage = False
-    net.removed = net.absorbed = net.gpooled = net.stem_paired = net.chained = net.fc_softmaxed = net.separated = 0
+    net.removed = net.absorbed = net.gpooled = net.stem_paired = net.chained = net.fc_softmaxed = net.separated = net.inverted = 0
     if fuse:
         net.removed = net.optimize(15)      # conv + eltwise, sibling pairs, conv + pooling, pool -> fc quantisation
+    if inverted:
+        net.inverted = net.optimize(32768)       # the sites formed (each removes two launches while one of its forms is selected)
     if separable:
         net.separated = net.optimize(16384)      # the sites formed (each removes a launch while one of its forms is selected)
     if fuse:

@@ -301,6 +301,28 @@ int saber_hip_conv2d_sep_get_tile(const saber_hip_sep_t* sep);
 const char* saber_hip_conv2d_sep_algo(const saber_hip_sep_t* sep);
 void saber_hip_conv2d_sep_destroy(saber_hip_sep_t* sep);
 
+/* Inverted-residual block (MobileNet-v2): `expand` = a plain 1x1 / stride-1 INT8 conv with relu and u8 output (Cin % 8 == 0, 8 <= Cin <= 192;
+ * s8 or u8 NHWC input), `dw` = the depthwise 3x3 INT8 conv that reads it (dilation 1, pad 1, stride 1 | 2, relu, u8 out, Ce % 16 == 0,
+ * Ce <= 1024) and `project` = the plain 1x1 / stride-1 INT8 conv that reads that (Cout % 8 == 0, Cout <= 320; RES_NONE with s8 output and no
+ * relu or u8 output and relu - or RES_ELTWISE, s8, res_stride <= 1, eltwise relu on or off, WHERE THE RESIDUAL IS THE BLOCK'S INPUT x: x is
+ * s8, Cin == Cout, stride 1) run as ONE launch (anakin_amd/csrc/conv_ir.hip: ir_expand_dw_project_i8): a workgroup keeps its tile of both
+ * expanded edges in LDS, 64 channels at a time. An executor-level fusion with no counterpart in the reference (framework/core/net/net.cpp:417-509
+ * dispatches one operator at a time). y - and y_expand [n, h, w, Ce] / y_dw [n, oh, ow, Ce] unless they are NULL, in which case that edge is
+ * not written - hold the bits of running the three ops (with the fused eltwise reading x) one after the other. The object refers to the
+ * three ops (they must outlive it) and owns both packed weight streams, the depthwise weights and the parameter tables: it KEEPS THE WEIGHTS
+ * ITS MEMBERS HAD WHEN IT WAS CREATED. Null operands: SABER_HIP_INVALID_VALUE; operands not of this shape, or without weights:
+ * SABER_HIP_UNIMPL. set_tile takes a form code (the table in conv_ir.hip: 1 = 4 x 16 pixel tiles, 2 = 2 x 16, 3 = tiles as wide as an image
+ * of at most 16 columns - the whole or half of a small image); a code without a form for this block returns SABER_HIP_INVALID_VALUE and
+ * changes nothing. algo: "ir_expand_dw_project_i8_<form>". */
+typedef struct saber_hip_ir saber_hip_ir_t;
+int saber_hip_conv2d_ir_create(saber_hip_conv_t* expand, saber_hip_conv_t* dw, saber_hip_conv_t* project, saber_hip_ir_t** out);
+int saber_hip_conv2d_ir_run(saber_hip_ir_t* ir, const void* x, void* y_expand /* may be NULL */, void* y_dw /* may be NULL */, void* y,
+                            saber_hip_stream_t stream);
+int saber_hip_conv2d_ir_set_tile(saber_hip_ir_t* ir, int code);
+int saber_hip_conv2d_ir_get_tile(const saber_hip_ir_t* ir);
+const char* saber_hip_conv2d_ir_algo(const saber_hip_ir_t* ir);
+void saber_hip_conv2d_ir_destroy(saber_hip_ir_t* ir);
+
 /* XCD-resident stage: a run of INT8 convolutions over SMALL feature maps (h * w <= 64 pixels per image: ResNet's res5) as
  * ONE persistent launch. Image i is computed entirely on XCD i % 8 (32 CUs, one workgroup each); the convolutions
  * ("phases") follow each other inside the kernel, separated by an XCD-local barrier where one reads what an earlier one
@@ -539,10 +561,25 @@ int saber_hip_net_add_fc_q(saber_hip_net_t* net, saber_hip_fc_t* op, int in_q_id
  * Ignored in a net with a side lane (as 16 and 32); allowed with SABER_HIP_NET_SHARED_DEVICE (no workgroup depends on another).
  * For THIS flag the return value counts the SITES formed, whether the static rule turns them on or not (a site removes one launch
  * while a form is selected; saber_hip_net_num_launches reports what a pass launches now) - the one exception to the sentence below.
+ * 32768 (SABER_HIP_NET_INVERTED_RESIDUAL; NOT in 255, never implied): three consecutive lane-0 ops - a 1x1 expand conv, the depthwise 3x3 conv
+ * that is the only reader of its output, the 1x1 project conv that is the only reader of that - which saber_hip_conv2d_ir_create accepts
+ * (MobileNet-v2's inverted-residual blocks) -> a site of the one-launch form. Where the project conv carries the fused eltwise (flag 1 ran
+ * first) its residual tensor must be the expand op's input tensor. All three ops stay in the list; while a form is selected the depthwise and
+ * the project op launch nothing and both inner edges are not written (saber_hip_net_tensor_unwritten). Which sites are ON is the static
+ * rule's choice (ir_static_form: measured rows only, profiles/ir/README.md), then saber_hip_net_autotune's, which times every form against
+ * the three tuned launches; saber_hip_net_get_choice of the EXPAND op reports 0x80000000 | (form << 24) | its own selection - bit 31 without
+ * bit 30: a block decision is recorded, form 0 = three launches (bit 31 otherwise comes only with bit 30, on a stage head).
+ * NO OP BELONGS TO TWO SITES: a project conv with the fused eltwise followed by the next block's expand conv is also the pattern of flag 16,
+ * a depthwise conv followed by a project conv that of flag 16384. Pass this flag BEFORE those (anakin_amd.workloads.build_int8_net does):
+ * chain and separable formation skip the ops a block site holds. Passed the other way round, this flag finds those ops taken, forms no
+ * site over them and counts nothing for them; the bytes are the same either way.
+ * Ignored in a net with a side lane; allowed with SABER_HIP_NET_SHARED_DEVICE (no workgroup depends on another). As for 16384 the return
+ * value counts the SITES formed (each removes two launches while a form is selected).
  * Bytes of every surviving edge are unchanged. Returns the number of launches removed (>= 0) or a status < 0. */
 #define SABER_HIP_NET_SHARED_DEVICE 2048
 #define SABER_HIP_NET_REPRODUCIBLE_FP32 8192
 #define SABER_HIP_NET_SEPARABLE 16384
+#define SABER_HIP_NET_INVERTED_RESIDUAL 32768
 int saber_hip_net_optimize(saber_hip_net_t* net, int flags);
 /* How many cooperative launches of this net have reported a failed pass since it was created (each made saber_hip_net_status /
  * the site's next launch return SABER_HIP_RUNTIME_ERROR once and its site fall back to single-workgroup launches): 0 on a net that

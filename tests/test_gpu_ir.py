@@ -1,0 +1,466 @@
+"""Inverted-residual blocks on the GPU: a 1x1 expand, a depthwise 3x3 and a 1x1 project INT8 conv (+ the fused eltwise sum with the block's
+input) in one launch (conv_ir.hip, saber_hip_conv2d_ir_*; saber_hip_net_optimize flag 32768). The oracle is O.conv_i8 -> O.conv_i8(group=Ce)
+-> O.conv_i8 [-> O.eltwise_i8] (tests/ir_util.py): every form of the launch, and the three separate launches, equal it bit for bit on y
+and on both inner edges; MobileNet-v2 runs through the executor on the default path (INT8 and FP32) and with the block sites forced on, with
+the static selection and with the autotuned one."""
+import ctypes as C
+
+import numpy as np
+import pytest
+
+pytestmark = pytest.mark.gpu
+torch = pytest.importorskip("torch")
+
+from anakin_amd import lib as L  # noqa: E402
+from anakin_amd import saber as S  # noqa: E402
+from anakin_amd import workloads as W  # noqa: E402
+from oracle import oracle as O  # noqa: E402
+from tests import dw_util as DU  # noqa: E402
+from tests import guard_util as GU  # noqa: E402
+from tests import int8_probe as P  # noqa: E402
+from tests import ir_util as IU  # noqa: E402
+
+POISON = 77
+NHWC = dict(in_layout=L.NHWC, out_layout=L.NHWC)
+
+
+@pytest.fixture(scope="module", autouse=True)
+def _device():
+    L.require_device()  # fail loudly: no fallback path exists
+
+
+def dev(a):
+    return torch.from_numpy(np.ascontiguousarray(a)).cuda()
+
+
+def host(t):
+    torch.cuda.synchronize()
+    return t.cpu().numpy()
+
+
+def forms_of(ir):
+    """the form codes set_tile accepts for this block (restores the selection)"""
+    keep = ir.tile()
+    lib = L.load()
+    codes = [c for c in range(1, IU.IR_MAX_CODE + 1) if lib.saber_hip_conv2d_ir_set_tile(ir.h, c) == 0]
+    ir.set_tile(keep)
+    return codes
+
+
+def make_block(n, cin, ce, cout, h, w, stride, idt, odt, p_relu, we, be, wse, wd, bd, wsd, wp, bp, wsp, scales, elt=None):
+    """scales = (in, expand, dw, project); elt = (coeff, scale_res, relu) for a project conv with the fused eltwise"""
+    s_in, s_e, s_d, s_p = scales
+    ex = S.SaberConv2D(True).init((n, cin, h, w), S.ConvParam(we, be, 1, (0, 0), (1, 1), (1, 1), True, wse), idt, L.U8, s_in, s_e, **NHWC)
+    dw = S.SaberConv2D(True).init((n, ce, h, w), S.ConvParam(wd, bd, ce, (1, 1), (stride, stride), (1, 1), True, wsd), L.U8, L.U8, s_e, s_d, **NHWC)
+    oh, ow = dw.out_hw
+    prm = S.ConvParam(wp, bp, 1, (0, 0), (1, 1), (1, 1), bool(p_relu), wsp)
+    if elt is not None:
+        prm.res_mode, prm.coeff, prm.scale_res, prm.res_relu = L.RES_ELTWISE, (elt[0], elt[0]), elt[1], bool(elt[2])
+    pr = S.SaberConv2D(True).init((n, ce, oh, ow), prm, L.U8, odt, s_d, s_p, **NHWC)
+    return ex, dw, pr
+
+
+def block_of(cs):
+    cin, ce, cout, h, w, s, _, n = cs.geo
+    elt = (cs.coeff, IU.IN_SCALE, cs.e_relu) if cs.res else None
+    return make_block(n, cin, ce, cout, h, w, s, cs.idt, cs.odt, cs.p_relu, cs.w_e, cs.b_e, None, cs.w_d, cs.b_d, None, cs.w_p, cs.b_p, None,
+                      (IU.IN_SCALE, cs.e_scale, cs.d_scale, cs.p_scale), elt)
+
+
+def run_block(what, ops, x, want_e, want_d, want_y, residual, probe_d=None, probe_y=None, min_forms=1):
+    """THE routine of the block tests: outputs poisoned before each run; the three separate launches and every form equal the oracle bit
+    for bit on y, y_expand and y_dw; y is identical with the inner edges NULL, which are then not written. Returns the form codes."""
+    from tests.test_gpu_int8_probe import check
+
+    def same(got, want, probe, label):
+        if probe is not None:
+            check(probe, got, want, "%s %s" % (what, label))
+        else:
+            assert got.shape == want.shape and got.dtype == want.dtype and np.array_equal(got, want), \
+                (what, label, int(np.count_nonzero(got != want)), want.size)
+    ex, dw, pr = ops
+    xd = dev(x)
+    y_e, y_d, y = ex.new_output(), dw.new_output(), pr.new_output()
+    for t in (y_e, y_d, y):
+        t.fill_(POISON)
+    ex.dispatch(xd, y_e)
+    dw.dispatch(y_e, y_d)
+    pr.dispatch(y_d, y, xd if residual else None)
+    same(host(y_e), want_e, None, "separate launches, y_expand (%s)" % ex.algo())
+    same(host(y_d), want_d, probe_d, "separate launches, y_dw (%s)" % dw.algo())
+    same(host(y), want_y, probe_y, "separate launches, y (%s)" % pr.algo())
+    ir = S.SaberConvIR(ex, dw, pr)
+    codes = forms_of(ir)
+    assert len(codes) >= min_forms, (what, codes)
+    for code in codes:
+        ir.set_tile(code)
+        assert ir.tile() == code and ir.algo().startswith("ir_expand_dw_project_i8_"), (what, code, ir.algo())
+        for t in (y_e, y_d, y):
+            t.fill_(POISON)
+        ir.dispatch(xd, y, y_e, y_d)
+        same(host(y_e), want_e, None, "%s, y_expand" % ir.algo())
+        same(host(y_d), want_d, probe_d, "%s, y_dw" % ir.algo())
+        same(host(y), want_y, probe_y, "%s, y" % ir.algo())
+        for t in (y_e, y_d, y):
+            t.fill_(POISON)
+        ir.dispatch(xd, y)
+        same(host(y), want_y, probe_y, "%s, y without the inner edges" % ir.algo())
+        for t, nm in ((y_e, "y_expand"), (y_d, "y_dw")):
+            assert int(host(t).min()) == POISON == int(host(t).max()), (what, ir.algo(), "NULL %s was written" % nm)
+    return codes
+
+
+def run_case(cs, min_forms=1):
+    return run_block((cs.geo, cs.variant, cs.bias), block_of(cs), cs.x, cs.e, cs.d, cs.y, cs.res, min_forms=min_forms)
+
+
+# ---- the nine geometries ----------------------------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("name", sorted(IU.GEOMETRIES))
+def test_geometries_every_form_bit_exact(name):
+    codes = run_case(IU.case(name), min_forms=2)
+    if IU.GEOMETRIES[name][4] <= 16:      # an image of at most 16 columns also has the small-image form
+        assert 3 in codes, (name, codes)
+
+
+def test_zero_padding_of_the_expanded_edge():
+    """geometry (b) with the input all zero bytes and the expand biases positive: expand(0) = relu(bias') > 0 inside the image, and the
+    depthwise conv pads that edge with ZEROS - the border ring of y differs from the interior (asserted on the oracle's result first)"""
+    cs = IU.case("b", zero_x=True)
+    assert cs.e.min() > 0, "the expanded edge of an all-zero input must be positive everywhere for this test to see the padding"
+    inner, y = cs.y[:, 1:-1, 1:-1, :], cs.y
+    assert all(np.array_equal(inner[:, i, j, :], inner[:, 0, 0, :]) for i in range(inner.shape[1]) for j in range(inner.shape[2]))
+    for ring in (y[:, 0, 1:-1, :], y[:, -1, 1:-1, :], y[:, 1:-1, 0, :], y[:, 1:-1, -1, :], y[:, 0:1, 0, :], y[:, -1:, -1, :]):
+        assert not np.array_equal(ring[:, 0, :], inner[:, 0, 0, :])
+    run_case(cs, min_forms=2)
+
+
+@pytest.mark.parametrize("name", ["a", "d", "f"])
+def test_dtype_and_epilogue_variants(name):
+    """x s8 and u8 (the latter without residual), project to s8 without relu and to u8 with relu, eltwise relu on and off; the bias
+    pattern (present or absent on each member) moves with the variant"""
+    geo = IU.GEOMETRIES[name]
+    ran = 0
+    for vi, (idt, res, p_relu, e_relu) in enumerate(IU.VARIANTS):
+        if res and not (geo[0] == geo[2] and geo[5] == 1):
+            continue
+        run_case(IU.case(name, vi))
+        ran += 1
+    assert ran >= 4
+
+
+def test_every_bias_pattern():
+    seen = {IU.case(n, vi).bias for n in ("a", "d", "f") for vi in range(len(IU.VARIANTS))
+            if not IU.VARIANTS[vi][1] or (IU.GEOMETRIES[n][0] == IU.GEOMETRIES[n][2] and IU.GEOMETRIES[n][5] == 1)}
+    assert seen == set(IU.BIASES), seen
+
+
+@pytest.mark.parametrize("vi", [1, 2, 3])
+def test_saturation(vi):
+    """every scale a quarter of MAXABS: the oracle's edges and result hold saturated and unsaturated bytes on both rails each has
+    (asserted before the GPU runs), every form equals them"""
+    cs = IU.case("a", vi, sat=True)
+    for y, dt, relu in ((cs.e, IU.U8, 1), (cs.d, IU.U8, 1), (cs.p, cs.odt, cs.p_relu), (cs.y, cs.odt, cs.p_relu or (cs.res and cs.e_relu))):
+        hi, lo, unsat = IU.saturates(y, dt, relu)
+        assert hi > 0 and unsat > 0 and (lo is None or lo > 0), (cs.variant, hi, lo, unsat)
+    run_case(cs)
+
+
+# ---- guard bands ------------------------------------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("name", ["b", "d", "h"])
+def test_guard_bands(name):
+    """x, y and both inner edges between guard bands: no byte outside any tensor is written, and the outputs do not depend on the bytes
+    outside (tests/guard_util.py), for every form, with the inner edges given and NULL"""
+    cs = IU.case(name)
+    ex, dw, pr = block_of(cs)
+    ir = S.SaberConvIR(ex, dw, pr)
+    lib = L.load()
+    for code in forms_of(ir):
+        ir.set_tile(code)
+        for edges in (True, False):
+            def launch(T, ws):
+                L.check(lib.saber_hip_conv2d_ir_run(ir.h, T["x"].data_ptr(), T["y_e"].data_ptr() if edges else None,
+                                                    T["y_d"].data_ptr() if edges else None, T["y"].data_ptr(), None))
+                torch.cuda.synchronize()
+            outs = {"y": (cs.y.shape, cs.y.dtype, None), "y_e": (cs.e.shape, cs.e.dtype, None), "y_d": (cs.d.shape, cs.d.dtype, None)}
+            got = GU.run_guarded({"x": cs.x}, outs, launch, "cuda", what="%s %s edges=%s" % (name, ir.algo(), edges))
+            assert np.array_equal(got["y"], cs.y), (name, ir.algo(), edges)
+            if edges:
+                assert np.array_equal(got["y_e"], cs.e) and np.array_equal(got["y_d"], cs.d), (name, ir.algo())
+            else:
+                assert (got["y_e"] == GU.SENTINEL).all() and (got["y_d"] == GU.SENTINEL).all(), (name, ir.algo())
+
+
+# ---- requantisation probes --------------------------------------------------------------------------------------------------------------------
+def test_pointwise_probes_as_the_project_member():
+    """the conv/pw_k64 probes (ties, rails, +-1e6, op order) through the block launch's LAST epilogue: expand and depthwise members are
+    identities on the probe's u8 image. The block's scope admits u8 -> s8 without relu and u8 -> u8 with relu."""
+    ran = 0
+    for i, o, r in P.CONV_COMBOS:
+        if i != O.U8 or (o, r) not in ((O.S8, 0), (O.U8, 1)):
+            continue
+        p = P.build("conv/pw_k64/%s%s/relu%d" % (P.DT_NAME[i], P.DT_NAME[o], r))
+        P.assert_classes(p)
+        N, H, Wd, Cc, K, k, pad, stride = p.geo
+        we, wse = IU.identity_expand(Cc, p.idt, p.in_scale)
+        wd, wsd = IU.identity_dw(Cc)
+        ops = make_block(N, Cc, Cc, K, H, Wd, 1, p.idt, p.odt, int(p.relu), we, None, wse, wd, None, wsd, p.wq, p.bias, p.w_scale,
+                         (p.in_scale, p.in_scale, p.in_scale, p.out_scale))
+        run_block(p.name, ops, p.x, p.x, p.x, P.oracle_bytes(p), False, probe_y=p)
+        ran += 1
+    assert ran == 2
+
+
+@pytest.mark.parametrize("gn", sorted(P.DW_GEOMETRIES))
+def test_depthwise_probes_as_the_depthwise_member(gn):
+    """the dw/s1 | s2 probes (u8 -> u8 with relu: the block's depthwise member) through the block launch's MIDDLE epilogue, behind an
+    identity expand conv, a random project conv behind them"""
+    rng = np.random.default_rng(30271)
+    p = P.build("dw/%s/u8u8/relu1" % gn)
+    P.assert_classes(p)
+    N, H, Wd, Cc, K, k, pad, stride = p.geo
+    mid = P.oracle_bytes(p)
+    K2 = 24
+    w2 = (rng.standard_normal((K2, Cc, 1, 1)) * 0.2).astype(np.float32)
+    b2 = (rng.standard_normal(K2) * 0.5).astype(np.float32)
+    ws2 = O.weight_scales(w2)
+    out_scale = 0.9
+    bp, sc = O.conv_i8_prepare(ws2, b2, p.out_scale, out_scale, p.odt, O.S8)
+    want = O.conv_i8(mid, O.quant_weights(w2, ws2), bp, sc, O.S8, 0)
+    we, wse = IU.identity_expand(Cc, p.idt, p.in_scale)
+    ops = make_block(N, Cc, Cc, K2, H, Wd, stride, p.idt, O.S8, 0, we, None, wse, p.wq, p.bias, p.w_scale, w2, b2, None,
+                     (p.in_scale, p.in_scale, p.out_scale, out_scale))
+    run_block(p.name, ops, p.x, p.x, mid, want, False, probe_d=p)
+
+
+# ---- refusals that need weights ----------------------------------------------------------------------------------------------------------------
+def test_set_tile_and_run_refusals():
+    cs = IU.case("a")
+    ex, dw, pr = block_of(cs)
+    ir = S.SaberConvIR(ex, dw, pr)
+    lib = L.load()
+    codes = forms_of(ir)
+    keep = ir.tile()
+    for bad in [c for c in range(0, 17) if c not in codes] + [-1, 255]:
+        assert lib.saber_hip_conv2d_ir_set_tile(ir.h, bad) == -2 and lib.saber_hip_last_error(), bad
+        assert ir.tile() == keep and lib.saber_hip_conv2d_ir_get_tile(ir.h) == keep
+    x, y = dev(cs.x), pr.new_output()
+    assert lib.saber_hip_conv2d_ir_run(ir.h, None, None, None, y.data_ptr(), None) == -2
+    assert lib.saber_hip_conv2d_ir_run(ir.h, x.data_ptr(), None, None, None, None) == -2
+    assert lib.saber_hip_conv2d_ir_run(None, x.data_ptr(), None, None, y.data_ptr(), None) == -2
+    # a residual that is not the block's input shape: Cin != Cout
+    cd = IU.case("d")
+    ex2, dw2, _ = block_of(cd)
+    h = C.c_void_p()
+    assert lib.saber_hip_conv2d_ir_create(ex2.h, dw2.h, pr.h, C.byref(h)) == -3 and not h.value
+
+
+# ---- MobileNet-v2 through the executor ------------------------------------------------------------------------------------------------------------
+@pytest.fixture(scope="module")
+def mobilenet():
+    model = W.build_model("mobilenet_v2")
+    fw = W.framework_model(model, "int8")
+    cache = {}
+
+    def at(batch, hw=224):
+        if (batch, hw) not in cache:
+            x = W.make_input(batch, hw=hw)
+            scales = W.calibrate(model, x)
+            cache[(batch, hw)] = (x, scales, DU.run_int8(fw, scales, x))
+        return cache[(batch, hw)]
+    return model, fw, at
+
+
+def compare_edges(net, ref, what, at_least):
+    torch.cuda.synchronize()
+    checked = 0
+    for name in net.tensors:
+        if name == "data" or name not in ref or net.unwritten(name):
+            continue
+        got, want = host(net.tensor(name)), ref[name]
+        if name == "prob":
+            assert np.abs(got - want.reshape(got.shape)).max() <= 1e-4 * want.max(), (what, name)
+        else:
+            assert np.array_equal(got, want.reshape(got.shape)), (what, name, int(np.count_nonzero(got != want.reshape(got.shape))))
+        checked += 1
+    assert checked >= at_least, (what, checked)
+    return checked
+
+
+def run_passes(net, x, ref, what, at_least):
+    for name in net.tensors:
+        if name != "data" and not net.unwritten(name):
+            net.tensor(name).fill_(POISON)
+    net.tensor("data").copy_(torch.from_numpy(x).cuda())
+    net.run()
+    compare_edges(net, ref, (what, "eager"), at_least)
+    net.tensor("fc10").zero_()
+    net.capture()
+    net.replay()
+    compare_edges(net, ref, (what, "replayed"), at_least)
+
+
+@pytest.mark.parametrize("batch", [1, 8])
+def test_mobilenet_v2_int8_default_path(mobilenet, batch):
+    """the framework op list one launch per operator, and with the default fusions: every written edge bit-exact against the oracle walk"""
+    model, fw, at = mobilenet
+    x, scales, ref = at(batch)
+    net = W.build_int8_net(fw, dict(scales), batch, fuse=False)
+    assert net.num_ops() == net.num_launches() == 52 + 10 + 3      # convs, eltwise sums, pool9 + fc10 + prob
+    run_passes(net, x, ref, (batch, "unfused"), 65)
+    net = W.build_int8_net(fw, dict(scales), batch)
+    assert net.removed >= 10 and net.inverted == 0      # (the ten eltwise sums are conv epilogues)
+    run_passes(net, x, ref, (batch, "default"), 40)
+
+
+@pytest.mark.parametrize("batch", [1, 8])
+def test_mobilenet_v2_fp32(mobilenet, batch):
+    model, fw, at = mobilenet
+    x = W.make_input(batch)
+    ref = DU.run_fp32(model, x)
+    net = W.build_fp32_net(model, batch)
+    net.tensor("data").copy_(torch.from_numpy(x).cuda())
+    net.run()
+    for name in ("fc10", "prob"):      # the project's two 1e-4 criteria (tests/test_gpu_dw.py: _fp32_close)
+        got = host(net.tensor(name))
+        want = ref[name].reshape(got.shape)
+        d = np.abs(got - want)
+        e_max = float(d.max() / max(np.abs(want).max(), 1e-30))
+        e_el = float((d / (np.abs(want) + np.abs(want).mean() + 1e-30)).max())
+        assert e_max <= 1e-4 and e_el <= 1e-4, (batch, name, e_max, e_el)
+
+
+def ir_sites(net):
+    """[(op index, form code now selected)] of the ops that record a block decision (bit 31 without bit 30 of their choice)"""
+    return [(i, (c >> 24) & 15) for i, c in enumerate(net.choices()) if (c >> 30) & 3 == 2]
+
+
+def force(net, code=None):
+    """every site on: with form `code` where the block has it, else (and for code None) with its first valid form"""
+    lib = L.load()
+    for i, _ in ir_sites(net):
+        base = net.choices()[i] & ~(15 << 24)
+        order = ([code] if code else []) + list(range(1, IU.IR_MAX_CODE + 1))
+        assert any(lib.saber_hip_net_set_choice(net.h, i, base | (f << 24)) == 0 for f in order), i
+    on = ir_sites(net)
+    assert all(f for _, f in on), on
+    return on
+
+
+def check_net(net, spec, x, ref, plain_launches, what):
+    sites = ir_sites(net)
+    n_on = sum(1 for _, f in sites if f)
+    assert len(sites) == 16, (what, sites)
+    assert net.num_launches() == plain_launches - 2 * n_on, (what, net.num_launches(), plain_launches, n_on)
+    names = [net.op_name(i) for i in range(net.num_ops())]
+    for i, f in sites:
+        assert ("ir_expand_dw_project_i8_" in names[i]) == bool(f), (what, i, names[i])
+        for j in (i + 1, i + 2):
+            assert (names[j] == "conv:(in the inverted-residual launch)") == bool(f), (what, j, names[j])
+    inner = [l["name"] for l in spec if l["kind"] == "conv" and (l["name"].endswith("_expand") or (l["name"].endswith("_dwise") and l["cin"] != 32))]
+    assert len(inner) == 32
+    assert sum(1 for n in inner if net.unwritten(n)) == 2 * n_on, (what, [n for n in inner if net.unwritten(n)])
+    run_passes(net, x, ref, what, 40 - 2 * n_on)
+    return n_on
+
+
+@pytest.mark.parametrize("batch,hw", [(1, 224), (8, 224), (3, 96)])
+def test_mobilenet_v2_int8_block_flag(mobilenet, batch, hw):
+    """inverted=True: 16 sites; the static selection, every site forced on per form, and the autotuned selection, eager and replayed"""
+    model, fw, at = mobilenet
+    x, scales, ref = at(batch, hw)
+    plain = W.build_int8_net(fw, dict(scales), batch, hw=hw)
+    plain_launches = plain.num_launches()
+    assert not ir_sites(plain)
+    net = W.build_int8_net(fw, dict(scales), batch, hw=hw, inverted=True)
+    assert net.inverted == 16
+    static = net.choices()
+    check_net(net, fw["spec"], x, ref, plain_launches, (batch, hw, "static"))
+    for code in (1, 2, 3):
+        force(net, code)
+        assert check_net(net, fw["spec"], x, ref, plain_launches, (batch, hw, "forced on, form %d" % code)) == 16
+    net.set_choices(static)
+    assert net.choices() == static
+    net.autotune(iters=2)
+    check_net(net, fw["spec"], x, ref, plain_launches, (batch, hw, "autotuned"))
+
+
+def test_choice_round_trip_and_compaction(mobilenet):
+    model, fw, at = mobilenet
+    x, scales, ref = at(3, 96)
+    lib = L.load()
+    net = W.build_int8_net(fw, dict(scales), 3, hw=96, inverted=True)
+    sites = ir_sites(net)
+    i0, i1 = sites[0][0], sites[1][0]      # one site on (form 2), one off, whatever the static rule said
+    L.check(lib.saber_hip_net_set_choice(net.h, i0, (net.choices()[i0] & ~(15 << 24)) | (2 << 24)))
+    L.check(lib.saber_hip_net_set_choice(net.h, i1, net.choices()[i1] & ~(15 << 24)))
+    ch = net.choices()
+    assert (ch[i0] >> 24) & 15 == 2 and (ch[i1] >> 24) & 15 == 0 and (ch[i1] >> 30) & 3 == 2
+    names = [net.op_name(i) for i in range(net.num_ops())]
+    fresh = W.build_int8_net(fw, dict(scales), 3, hw=96, inverted=True)
+    fresh.set_choices(ch)
+    assert fresh.choices() == ch
+    assert [fresh.op_name(i) for i in range(fresh.num_ops())] == names
+    # a code with no form is refused before anything changes
+    bad = (ch[i0] & ~(15 << 24)) | (15 << 24)
+    assert lib.saber_hip_net_set_choice(fresh.h, i0, bad) == -2
+    assert fresh.choices() == ch and [fresh.op_name(i) for i in range(fresh.num_ops())] == names
+    # arena compaction with every site on: the one launch reads the expand op's input while it writes the project op's output
+    force(fresh)
+    before = fresh.arena_bytes()
+    fresh.compact()
+    assert fresh.compacted() and fresh.arena_bytes() < before
+    fresh.tensor("data").copy_(torch.from_numpy(x).cuda())
+    fresh.run()
+    assert np.array_equal(host(fresh.tensor("fc10")), ref["fc10"])
+    fresh.capture()
+    fresh.tensor("fc10").zero_()
+    fresh.replay()
+    assert np.array_equal(host(fresh.tensor("fc10")), ref["fc10"])
+
+
+def test_opt_in(mobilenet):
+    """with the flag off, the op count, launch count, names and choices equal a net built without the argument"""
+    model, fw, at = mobilenet
+    x, scales, _ = at(3, 96)
+    a = W.build_int8_net(fw, dict(scales), 3, hw=96)
+    b = W.build_int8_net(fw, dict(scales), 3, hw=96, inverted=False)
+    assert a.inverted == b.inverted == 0
+    assert a.num_ops() == b.num_ops() and a.num_launches() == b.num_launches() and a.choices() == b.choices()
+    assert [a.op_name(i) for i in range(a.num_ops())] == [b.op_name(i) for i in range(b.num_ops())]
+    assert not ir_sites(a) and not any("ir_" in a.op_name(i) for i in range(a.num_ops()))
+    assert not any(a.unwritten(l["name"]) for l in fw["spec"] if l["kind"] == "conv" and "eltwise" not in l)
+
+
+@pytest.mark.parametrize("other", [16, 16384])
+def test_flag_order(mobilenet, other):
+    """flag 32768 and the chain flag (16) / the separable flag (16384) in both orders: no op is in two sites, and the bytes are unchanged.
+    Block flag first (build_int8_net's order): 16 sites, and the other flag forms nothing over their ops. Other flag first: it forms its
+    sites, and the block flag forms a site exactly over the blocks none of whose ops the other flag holds."""
+    model, fw, at = mobilenet
+    x, scales, ref = at(3, 96)
+    blocks = None
+    for order in ((32768, other), (other, 32768)):
+        got = {}
+
+        def flags(net):
+            for f in order:
+                got[f] = net.optimize(f)
+        net = W.build_int8_net(fw, dict(scales), 3, hw=96, chain=0, before_finalize=flags)
+        ch = net.choices()
+        heads = sorted(i for i, c in enumerate(ch) if (c >> 30) & 3 == 2)
+        others = sorted(i for i, c in enumerate(ch) if (c >> 28) & 3 == (1 if other == 16 else 3))
+        held = {j for i in others for j in (i, i + 1)}
+        in_block = [j for i in heads for j in (i, i + 1, i + 2)]
+        assert len(in_block) == len(set(in_block)) and not (set(in_block) & held), (order, heads, others)
+        assert len(heads) == got[32768], (order, heads, got)
+        if order[0] == 32768:
+            assert got[32768] == 16 and len(heads) == 16, (order, got)
+            blocks = heads
+            # what the other flag forms lies outside every block (MobileNet-v2's first, expand-less block is a separable pair)
+            assert got[other] == len(others) and not (held & set(in_block)), (order, got, others)
+        else:
+            free = [i for i in blocks if not ({i, i + 1, i + 2} & held)]
+            assert heads == free, (order, heads, free, others)
+        if heads:
+            force(net)
+        run_passes(net, x, ref, (order, "sites on"), 8)
