@@ -169,6 +169,23 @@ int capture_stream_op(OpKind kind, const char* name, const int* p, int np, const
     return SABER_HIP_OK;
 }
 
+// a concat: every input is read, the output is a new tensor (the arguments were checked by saber_hip_concat_nhwc)
+int capture_concat(size_t pixels, int n_inputs, const void* const* xs, const int* channels, const float* mult, int dtype, void* y) {
+    Capture& c = *g_capture;
+    int ids[CONCAT_MAX_INPUTS];
+    size_t row = 0;
+    for (int i = 0; i < n_inputs; ++i) {
+        ids[i] = c.read(xs[i], pixels * channels[i] * esz(dtype));
+        row += channels[i] * esz(dtype);
+        if (ids[i] < 0) return c.bad("bad tensor");
+    }
+    const int out = c.write(y, pixels * row);
+    if (c.failed || out < 0) return c.bad("bad tensor");
+    if (saber_hip_net_add_concat(c.net, pixels, n_inputs, ids, channels, mult, dtype, out) < 0) return c.bad("saber_hip_net_add_concat failed");
+    ++c.ops;
+    return SABER_HIP_OK;
+}
+
 }  // namespace saber_api
 
 int saber_hip_capture_begin(void) {

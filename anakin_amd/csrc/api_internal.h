@@ -292,6 +292,17 @@ struct saber_hip_ir {
     std::string name;               // "ir_expand_dw_project_i8_<form>" of the selected form
 };
 
+// a Fire module - a 1x1 squeeze conv, the 1x1 and the padded 3x3 expand convs that read it, and the concat of the two - in one launch
+// (conv_fire.hip); refers to the three ops, owns the three fragment streams and constant tables as they were when it was created
+struct saber_hip_fire {
+    saber_hip_conv* squeeze = nullptr;
+    saber_hip_conv* e1 = nullptr;
+    saber_hip_conv* e3 = nullptr;
+    int form = 0;                   // the selected row of conv_fire.hip's form table (its code)
+    DevBuf<uint8_t> d_ws, d_sprm, d_w1, d_prm1, d_w3, d_prm3;
+    std::string name;               // "fire_squeeze_expand_i8_<form>" of the selected form
+};
+
 struct saber_hip_fc {
     saber_hip_fc_desc d;
     saber_hip_conv* conv = nullptr;
@@ -394,9 +405,9 @@ struct ColdScope {
 
 // op-list executor
 namespace saber_api {
-enum OpKind { OP_CONV, OP_CONV_PAIR, OP_FC, OP_QUANT, OP_DEQUANT, OP_TRANSPOSE_IN, OP_ELT_I8, OP_ELT_F32, OP_POOL_I8, OP_POOL_F32, OP_POOL_F32_I8, OP_FC_Q, OP_SOFTMAX, OP_RELU_F32, OP_ACT_F32 };
+enum OpKind { OP_CONV, OP_CONV_PAIR, OP_FC, OP_QUANT, OP_DEQUANT, OP_TRANSPOSE_IN, OP_ELT_I8, OP_ELT_F32, OP_POOL_I8, OP_POOL_F32, OP_POOL_F32_I8, OP_FC_Q, OP_SOFTMAX, OP_RELU_F32, OP_ACT_F32, OP_CONCAT };
 // What an op launches in the current selection: DERIVED from the sites' decisions by net_resolve (api_net_optimize.hip), never set elsewhere
-enum Launch { LAUNCH_NONE, LAUNCH_OWN, LAUNCH_CHAIN, LAUNCH_CHAIN3, LAUNCH_STAGE, LAUNCH_STEM_PAIR, LAUNCH_SEP, LAUNCH_IR };
+enum Launch { LAUNCH_NONE, LAUNCH_OWN, LAUNCH_CHAIN, LAUNCH_CHAIN3, LAUNCH_STAGE, LAUNCH_STEM_PAIR, LAUNCH_SEP, LAUNCH_IR, LAUNCH_FIRE };
 // A SITE is a group of adjacent ops that can run as one launch. The op that heads a site holds the site's object and its DECISION (*_on: stored
 // as asked by the net_set_* setters and read back by saber_hip_net_get_choice; a decision is never changed to express what another site
 // does); what every op launches, which ops launch nothing and every conv / pair / fc / softmax op's name follow from the decisions in
@@ -407,6 +418,10 @@ struct NetOp {
     saber_hip_conv* conv = nullptr;
     saber_hip_fc* fc = nullptr;
     int in = -1, in2 = -1, out = -1, out2 = -1;
+    // OP_CONCAT: EVERY input id in channel order (in = ins[0], in2 stays -1), their channel counts in elements and - u8 with rescaling - the
+    // per-input multipliers (empty: a copy). Whatever asks which tensors an op reads goes through op_for_each_input / op_reads below.
+    std::vector<int> ins, cat_c;
+    std::vector<float> cat_m;
     // derived (net_resolve): this op's launch; LAUNCH_NONE = `skip`: ops[absorbed_by]'s launch covers it
     Launch launch = LAUNCH_OWN;
     int absorbed_by = -1;
@@ -456,12 +471,34 @@ struct NetOp {
     saber_hip_ir* ir = nullptr;
     int ir_out = -1;
     bool ir_on = false;
+    // a Fire module (flag 65536, SABER_HIP_NET_FIRE): THIS op is the 1x1 squeeze conv, the next three are the two expand convs and the concat;
+    // while fire_on is set its launch covers all three, this op's and both expand ops' output edges are not written and fire_out is the
+    // concat's output
+    saber_hip_fire* fire = nullptr;
+    int fire_out = -1;
+    bool fire_on = false;
     int lane = 0;            // 0: caller's stream, 1: the net's side stream (graph::Lane, operator_func.h:103-114)
     bool record = false;     // an op on the other lane consumes this op's output: record an event after it
     int p[16] = {0};
     float f[6] = {0};
     size_t count = 0;
 };
+// the tensors an op READS as operands (a concat: its whole input list; every other kind: in and in2)
+template <typename F>
+inline void op_for_each_input(const NetOp& o, F&& f) {
+    if (o.kind == OP_CONCAT) {
+        for (int t : o.ins) f(t);
+        return;
+    }
+    if (o.in >= 0) f(o.in);
+    if (o.in2 >= 0) f(o.in2);
+}
+inline int op_reads(const NetOp& o, int t) {      // how many of its operands are tensor t
+    int n = 0;
+    op_for_each_input(o, [&](int u) { n += u == t; });
+    return n;
+}
+inline bool op_touches(const NetOp& o, int t) { return op_reads(o, t) || o.out == t || o.out2 == t; }
 }  // namespace saber_api
 
 struct saber_hip_net {
@@ -504,6 +541,7 @@ struct saber_hip_net {
     std::vector<saber_hip_stem_pair*> owned_stem_pairs;
     std::vector<saber_hip_sep*> owned_seps;
     std::vector<saber_hip_ir*> owned_irs;
+    std::vector<saber_hip_fire*> owned_fires;
 };
 
 // Op-list capture (api_capture.hip; saber_hip_capture_begin / _end): while g_capture is set on the calling thread every
@@ -514,6 +552,7 @@ extern thread_local Capture* g_capture;
 int capture_conv(saber_hip_conv* op, const void* x, void* y, const void* res);
 int capture_fc(saber_hip_fc* fc, const void* x, float* y, bool quantised_input);
 int capture_unsupported(const char* what);
+int capture_concat(size_t pixels, int n_inputs, const void* const* xs, const int* channels, const float* mult, int dtype, void* y);
 // streaming ops: kind + the argument block of the matching saber_hip_net_add_* call; in2 / out2 may be null
 int capture_stream_op(OpKind kind, const char* name, const int* p, int np, const float* f, int nf, size_t count, const void* in,
                       size_t in_bytes, const void* in2, size_t in2_bytes, void* out, size_t out_bytes, void* out2, size_t out2_bytes);
@@ -551,6 +590,7 @@ int net_launch(saber_hip_net* net, const NetOp& o, hipStream_t s);      // api_n
 bool fc_softmax_ok(const saber_hip_fc* fc, bool quantised_input = false);      // api_ops.hip: the INT8 small-batch fc kernel can normalise its own logits (fc_small.hip)
 int fc_run_softmax(saber_hip_fc* fc, const void* x, float* y, float* prob, void* workspace, hipStream_t s, bool quantised_input);
 int fc_softmax_prepare(saber_hip_fc* fc);        // ... allocates the arrival counter (not under stream capture)
+int concat_check(int n_inputs, const int* channels, const float* mult, int dtype, int* row_bytes);      // api_ops.hip: a status; row_bytes (may be null) = bytes per pixel of each input
 // sites (api_net_optimize.hip): each setter stores decisions and calls net_resolve, the one place that derives launch / absorbed_by / skip and the names
 void net_resolve(saber_hip_net* net);
 void net_drop_graph(saber_hip_net* net);      // api_net.hip: a captured hipGraph holds the old selection / addresses
@@ -580,6 +620,12 @@ bool ir_form_valid(const saber_hip_ir* ir, int code);      // the form exists fo
 void for_each_ir_form(const saber_hip_ir* ir, const std::function<void(int code)>& fn);      // its forms, in the autotuner's candidate order
 int ir_static_form(const saber_hip_ir* ir);      // the executor's static choice: a form code, or 0 = three launches
 void net_set_ir(saber_hip_net* net, int i, int code);      // api_net_optimize.hip: the site headed by ops[i] on (a valid form code) / off (0)
+// Fire modules (api_fire.hip)
+bool conv_fire_ok(const saber_hip_conv* squeeze, const saber_hip_conv* e1, const saber_hip_conv* e3, std::string* why);      // a module conv_fire.hip can run
+bool fire_form_valid(const saber_hip_fire* fr, int code);
+void for_each_fire_form(const saber_hip_fire* fr, const std::function<void(int code)>& fn);
+int fire_static_form(const saber_hip_fire* fr);      // the executor's static choice: a form code, or 0 = four launches
+void net_set_fire(saber_hip_net* net, int i, int code);      // api_net_optimize.hip: the site headed by ops[i] on (a valid form code) / off (0)
 // api_chain.hip; y_tail: the tail's output - the tail then runs inside the launch (a stage created with one), null: the blocks only
 // y_head: the second output of the stage's head - the pair then runs inside the launch (a stage created with one), x is the PAIR's input and res is not read
 int stage_run(saber_hip_chain_stage* st, const void* x, const void* res, void* const* y1, void* const* y2, hipStream_t s, void* y_tail = nullptr,

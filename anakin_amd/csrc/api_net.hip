@@ -49,6 +49,7 @@ int net_launch(saber_hip_net* net, const NetOp& o, hipStream_t s) {
         case LAUNCH_CHAIN: return saber_hip_conv2d_chain_run(o.chain, T(o.in), T(o.in2), T(o.out), T(o.chain_out), s);
         case LAUNCH_SEP: return saber_hip_conv2d_sep_run(o.sep, T(o.in), nullptr, T(o.sep_out), s);      // the depthwise edge stays in LDS
         case LAUNCH_IR: return saber_hip_conv2d_ir_run(o.ir, T(o.in), nullptr, nullptr, T(o.ir_out), s);      // both inner edges stay in LDS
+        case LAUNCH_FIRE: return saber_hip_conv2d_fire_run(o.fire, T(o.in), nullptr, T(o.fire_out), s);      // the three inner edges stay in LDS
         case LAUNCH_OWN: break;
         }
         if (o.conv->gpool) return saber_hip_conv2d_run_gpool(o.conv, T(o.in), T(o.out), T(o.in2), T(o.out2), s);
@@ -92,6 +93,12 @@ int net_launch(saber_hip_net* net, const NetOp& o, hipStream_t s) {
         return saber_hip_softmax_f32(o.p[0], o.p[1], (const float*)T(o.in), (float*)T(o.out), s);
     case OP_RELU_F32: return saber_hip_relu_f32(o.count, (const float*)T(o.in), (float*)T(o.out), s);
     case OP_ACT_F32: return saber_hip_activation_f32(o.p[0], o.count, o.f[0], o.f[1], (const float*)T(o.in), (float*)T(o.out), s);
+    case OP_CONCAT: {
+        if (o.skip) return SABER_HIP_OK;      // written by the Fire launch in front of it (flag 65536)
+        const void* xs[CONCAT_MAX_INPUTS];
+        for (size_t k = 0; k < o.ins.size(); ++k) xs[k] = T(o.ins[k]);
+        return saber_hip_concat_nhwc(o.count, (int)o.ins.size(), xs, o.cat_c.data(), o.cat_m.empty() ? nullptr : o.cat_m.data(), o.p[0], T(o.out), s);
+    }
     }
     return SABER_HIP_UNIMPL;
 }
@@ -244,6 +251,29 @@ int saber_hip_net_add_activation_f32(saber_hip_net_t* net, int active, size_t co
     o.p[0] = active; o.f[0] = negative_slope; o.f[1] = coef;
     return push(net, std::move(o));
 }
+int saber_hip_net_add_concat(saber_hip_net_t* net, size_t pixels, int n_inputs, const int* in_ids, const int* channels, const float* mult, int dtype,
+                             int out_id) {
+    int row_bytes[CONCAT_MAX_INPUTS];
+    const int rc = concat_check(n_inputs, channels, mult, dtype, row_bytes);
+    if (rc) return rc;
+    if (!net || !in_ids) return fail(SABER_HIP_INVALID_VALUE, "concat: null argument");
+    const int nt = (int)net->tensor_bytes.size();
+    if (out_id < 0 || out_id >= nt) return fail(SABER_HIP_INVALID_VALUE, "bad tensor id");
+    size_t out_row = 0;
+    for (int i = 0; i < n_inputs; ++i) {
+        if (in_ids[i] < 0 || in_ids[i] >= nt || in_ids[i] == out_id) return fail(SABER_HIP_INVALID_VALUE, "bad tensor id");
+        if (net->tensor_bytes[in_ids[i]] < pixels * (size_t)row_bytes[i]) return fail(SABER_HIP_INVALID_VALUE, "concat: an input tensor is smaller than pixels x channels");
+        out_row += (size_t)row_bytes[i];
+    }
+    if (net->tensor_bytes[out_id] < pixels * out_row) return fail(SABER_HIP_INVALID_VALUE, "concat: the output tensor is smaller than pixels x the sum of the channels");
+    NetOp o;
+    o.kind = OP_CONCAT; o.in = in_ids[0]; o.out = out_id; o.count = pixels; o.name = "concat" + std::to_string(n_inputs);
+    o.ins.assign(in_ids, in_ids + n_inputs);
+    o.cat_c.assign(channels, channels + n_inputs);
+    if (mult) o.cat_m.assign(mult, mult + n_inputs);
+    o.p[0] = dtype;
+    return push(net, std::move(o));
+}
 int saber_hip_net_add_softmax(saber_hip_net_t* net, int rows, int cols, int in_id, int out_id) {
     NetOp o;
     o.kind = OP_SOFTMAX; o.in = in_id; o.out = out_id; o.name = "softmax_f32";
@@ -313,19 +343,21 @@ int saber_hip_net_compact_arena(saber_hip_net_t* net, const int* keep, int n_kee
         if (o.chain) span(i, 2);
         if (o.stem_pair) span(i, 2);
         if (o.sep) span(i, 2);      // (the one launch reads the depthwise conv's input while it writes the pointwise conv's output)
+        if (o.fire) span(i, 4);     // (the one launch reads the squeeze conv's input while it writes the concat's output)
         if (o.ir) span(i, 3);       // (the one launch reads the expand conv's input - the residual too - while it writes the project conv's output)
         if ((o.kind == OP_FC || o.kind == OP_FC_Q) && o.out2 >= 0) span(i, 2);
     }
     for (int i = 0; i < nops; ++i) {
         const NetOp& o = net->ops[i];
         const int rd[] = {o.in, o.in2, o.chain3_res};
-        const int wr[] = {o.out, o.out2, o.chain_out, o.chain3_y1, o.chain3_y2, o.chain3_y3, o.stem_y1, o.stem_y2, o.sep_out, o.ir_out};
+        const int wr[] = {o.out, o.out2, o.chain_out, o.chain3_y1, o.chain3_y2, o.chain3_y3, o.stem_y1, o.stem_y2, o.sep_out, o.ir_out, o.fire_out};
         auto touch = [&](int t) {
             if (t < 0 || t >= nt) return;
             first[t] = std::min(first[t], g_lo[i]);
             last[t] = std::max(last[t], g_hi[i]);
         };
         for (int t : rd) { touch(t); if (t >= 0 && t < nt) ++reads[t]; }
+        for (size_t k = 1; k < o.ins.size(); ++k) { touch(o.ins[k]); if (o.ins[k] >= 0 && o.ins[k] < nt) ++reads[o.ins[k]]; }      // (a concat's inputs behind the first)
         for (int t : wr) { touch(t); if (t >= 0 && t < nt) ++writes[t]; }
     }
     for (int t = 0; t < nt; ++t)
@@ -398,9 +430,12 @@ static int net_prepare_lanes(saber_hip_net* net) {
     for (int i = 0; i < nops; ++i) {
         NetOp& o = net->ops[i];
         if (o.lane) net->has_side = true;
-        const int ins[3] = {o.in, o.in2, o.out};   // `out` counts as an input: in-place epilogues read it
-        for (int t : ins)
+        int ins[1 + CONCAT_MAX_INPUTS] = {o.out}, n_ins = 1;   // `out` counts as an input: in-place epilogues read it
+        op_for_each_input(o, [&](int t) { ins[n_ins++] = t; });
+        for (int k = 0; k < n_ins; ++k) {
+            const int t = ins[k];
             if (t >= 0 && w[t] >= 0 && net->ops[w[t]].lane != o.lane) net->ops[w[t]].record = true;   // RAW / WAW
+        }
         const int outs[2] = {o.out, o.out2};
         for (int t : outs) {
             if (t < 0) continue;
@@ -409,8 +444,7 @@ static int net_prepare_lanes(saber_hip_net* net) {
             rd[t].clear();
             w[t] = i;
         }
-        if (o.in >= 0) rd[o.in].push_back(i);
-        if (o.in2 >= 0) rd[o.in2].push_back(i);
+        op_for_each_input(o, [&](int t) { rd[t].push_back(i); });
     }
     if (net->has_side) {
         HIP_TRY(hipStreamCreateWithFlags(&net->side, hipStreamNonBlocking));
@@ -444,8 +478,10 @@ int saber_hip_net_run(saber_hip_net_t* net, saber_hip_stream_t stream) {
     for (size_t i = 0; i < net->ops.size(); ++i) {
         const NetOp& o = net->ops[i];
         hipStream_t s = o.lane ? net->side : main_s;
-        const int ins[3] = {o.in, o.in2, o.out};
-        for (int t : ins) {
+        int ins[1 + CONCAT_MAX_INPUTS] = {o.out}, n_ins = 1;
+        op_for_each_input(o, [&](int t) { ins[n_ins++] = t; });
+        for (int k = 0; k < n_ins; ++k) {
+            const int t = ins[k];
             if (t < 0) continue;
             const int wi = net->writer[t];
             if (wi >= 0 && net->ops[wi].lane != o.lane) HIP_TRY(hipStreamWaitEvent(s, net->ev_op[wi], 0));
@@ -463,8 +499,7 @@ int saber_hip_net_run(saber_hip_net_t* net, saber_hip_stream_t stream) {
         if (o.lane) side_dirty = true;
         net->writer[o.out] = (int)i;
         if (o.out2 >= 0) net->writer[o.out2] = (int)i;
-        if (o.in >= 0) readers[o.in].push_back((int)i);
-        if (o.in2 >= 0) readers[o.in2].push_back((int)i);
+        op_for_each_input(o, [&](int t) { readers[t].push_back((int)i); });
     }
     if (side_dirty) {   // join: required before a capture ends, and so that the caller sees one ordered stream
         HIP_TRY(hipEventRecord(net->ev_join, net->side));
@@ -476,7 +511,7 @@ int saber_hip_net_set_lane(saber_hip_net_t* net, int index, int lane) {
     if (index < 0 || index >= (int)net->ops.size() || lane < 0 || lane > 1) return fail(SABER_HIP_INVALID_VALUE, "bad op index / lane");
     if (net->lanes_ready) return fail(SABER_HIP_INVALID_VALUE, "lanes are fixed after the first run");
     for (const NetOp& o : net->ops)
-        if (lane && (o.chain || o.chain3 || o.stem_pair || o.sep || o.ir))
+        if (lane && (o.chain || o.chain3 || o.stem_pair || o.sep || o.ir || o.fire))
             return fail(SABER_HIP_INVALID_VALUE, "the net has launches that span several ops' tensors (conv1x1 chains, the stem pair, separable sites): lanes must be assigned before saber_hip_net_optimize");
     if (lane) {   // both lanes share the arena's single workspace: an op that uses it stays on the main lane
         const NetOp& o = net->ops[index];
@@ -548,7 +583,7 @@ int saber_hip_net_op_work(const saber_hip_net_t* net, int index, double* bytes, 
         if (o.skip) return SABER_HIP_OK;
         conv_work(o.conv, *bytes, *flops);      // + the work of the ops behind it that its launch covers (the algorithmic bytes of the separate ops)
         for (int j = index + 1; j < (int)net->ops.size(); ++j)
-            if (net->ops[j].absorbed_by == index) conv_work(net->ops[j].conv, *bytes, *flops);
+            if (net->ops[j].absorbed_by == index && net->ops[j].conv) conv_work(net->ops[j].conv, *bytes, *flops);
         return SABER_HIP_OK;
     case OP_CONV_PAIR:
         if (!o.skip) conv_work(o.conv, *bytes, *flops);
@@ -564,7 +599,8 @@ int saber_hip_net_op_work(const saber_hip_net_t* net, int index, double* bytes, 
     }
     default:
         if (o.skip) return SABER_HIP_OK;
-        *bytes = tb(o.in) + tb(o.in2) + tb(o.out) + tb(o.out2);
+        *bytes = tb(o.out) + tb(o.out2);
+        op_for_each_input(o, [&](int t) { *bytes += tb(t); });
         return SABER_HIP_OK;
     }
 }
@@ -666,6 +702,8 @@ int saber_hip_net_tensor_unwritten(const saber_hip_net_t* net, int id) {
         if (o.out == id && (o.launch == LAUNCH_CHAIN3 || o.launch == LAUNCH_STEM_PAIR || o.launch == LAUNCH_SEP || (o.chain3 && by == LAUNCH_STAGE))) return 1;
         // both inner edges of an inverted-residual block while its one launch is selected: the expand op's and the depthwise op's outputs
         if (o.out == id && (o.launch == LAUNCH_IR || (o.skip && by == LAUNCH_IR && (int)(&o - net->ops.data()) == o.absorbed_by + 1))) return 1;
+        // the three inner edges of a Fire module while its one launch is selected: the squeeze op's and both expand ops' outputs
+        if (o.out == id && o.kind == OP_CONV && (o.launch == LAUNCH_FIRE || (o.skip && by == LAUNCH_FIRE))) return 1;
         // the first block's shortcut while the pair that makes it runs as the stage launch's head: it stays in LDS
         if (o.launch == LAUNCH_STAGE && o.head_on && o.chain3_res == id) return 1;
     }
@@ -730,6 +768,7 @@ void saber_hip_net_destroy(saber_hip_net_t* net) {
     for (saber_hip_chain* c : net->owned_chains) saber_hip_conv2d_chain_destroy(c);
     for (saber_hip_sep* sp : net->owned_seps) saber_hip_conv2d_sep_destroy(sp);
     for (saber_hip_ir* ir : net->owned_irs) saber_hip_conv2d_ir_destroy(ir);
+    for (saber_hip_fire* fr : net->owned_fires) saber_hip_conv2d_fire_destroy(fr);
     for (saber_hip_conv* c : net->owned) saber_hip_conv2d_destroy(c);
     for (hipEvent_t e : net->ev_op)
         if (e) (void)hipEventDestroy(e);

@@ -27,6 +27,7 @@ int saber_hip_net_get_choice(saber_hip_net_t* net, int index) {
     if (o.chain3) choice |= (1 << 29) | ((o.led_on ? o.chain3->form.code : 0) << 24);      // (a strided head reports its own decision while it runs as a tail)
     if (o.sep) choice |= (3 << 28) | ((o.sep_on ? o.sep->form : 0) << 24);
     if (o.ir) choice |= (int)0x80000000u | ((o.ir_on ? o.ir->form : 0) << 24);
+    if (o.fire) choice |= (int)0x80000000u | ((o.fire_on ? o.fire->form : 0) << 24);      // (the squeeze op of a Fire site, flag 65536: the same pattern; no op heads both)
     if (o.stage && o.stage_on) choice |= 1 << 30;      // this op launches its whole stage
     if (o.stage && o.stage_on && o.tail_on) choice |= (int)0x80000000u;      // ... and the strided head behind it as the launch's tail
     // bit 29 on a sibling-pair op (which never leads a chain: bits 24..29 mean nothing else there): the pair runs as the HEAD of the stage launch behind it
@@ -48,6 +49,13 @@ int saber_hip_net_set_choice(saber_hip_net_t* net, int index, int choice) {
     const bool ir_bits = c && net->ops[index].ir && ((unsigned)choice >> 30) == 2u;
     const int ir_tn = (choice >> 24) & 15;
     if (ir_bits && ir_tn && !ir_form_valid(net->ops[index].ir, ir_tn)) return saber_hip_conv2d_ir_set_tile(net->ops[index].ir, ir_tn);      // (its status and message)
+    const bool fire_bits = c && net->ops[index].fire && ((unsigned)choice >> 30) == 2u;
+    if (fire_bits && ir_tn && !fire_form_valid(net->ops[index].fire, ir_tn)) return saber_hip_conv2d_fire_set_tile(net->ops[index].fire, ir_tn);
+    if (fire_bits && !(choice & 0xffffff)) {
+        net_set_fire(net, index, ir_tn);
+        net_drop_graph(net);
+        return SABER_HIP_OK;
+    }
     if (ir_bits && !(choice & 0xffffff)) {
         net_set_ir(net, index, ir_tn);
         net_drop_graph(net);
@@ -91,6 +99,7 @@ int saber_hip_net_set_choice(saber_hip_net_t* net, int index, int choice) {
     if (o.head_of >= 0) net_set_head(net, o.head_of, (chain_bits & 32) && !net->shared_device);
     if (sep_bits) net_set_sep(net, index, tn);      // (a choice without the bits leaves the site as it is)
     if (ir_bits) net_set_ir(net, index, ir_tn);
+    if (fire_bits) net_set_fire(net, index, ir_tn);
     net_resolve(net);      // (the names follow the kernel selection)
     net_drop_graph(net);
     return SABER_HIP_OK;
@@ -364,6 +373,34 @@ int saber_hip_net_autotune(saber_hip_net_t* net, saber_hip_stream_t stream, int 
             if (rt == SABER_HIP_OK && us < best) { best = us; best_code = code; }
         });
         net_set_ir(net, (int)i, best_code);
+        rc = run_all();   // every written output holds the selected form's result
+        if (rc) return rc;
+    }
+    // Fire sites (flag 65536): the three tuned convs + the concat against every form of the one launch, cold L2, on the real tensors
+    for (size_t i = 0; i + 3 < net->ops.size(); ++i) {
+        NetOp& Q = net->ops[i];
+        if (!Q.fire) continue;
+        hipStream_t s = (hipStream_t)stream;
+        auto run_all = [&]() -> int {
+            int r = 0;
+            for (size_t j = i; j <= i + 3; ++j) r |= net_launch(net, net->ops[j], s);
+            return r;
+        };
+        auto timed = [&](float* t) { return time_enqueued(s, run_all, 20, t); };
+        float best = 0.f;
+        int best_code = 0;
+        net_set_fire(net, (int)i, 0);
+        int rc = timed(&best);
+        if (rc) return rc;
+        log_cand(Q.conv, "separate", best);
+        for_each_fire_form(Q.fire, [&](int code) {
+            float us = -1.f;
+            net_set_fire(net, (int)i, code);
+            const int rt = timed(&us);
+            log_cand(Q.conv, Q.name.substr(5), us);
+            if (rt == SABER_HIP_OK && us < best) { best = us; best_code = code; }
+        });
+        net_set_fire(net, (int)i, best_code);
         rc = run_all();   // every written output holds the selected form's result
         if (rc) return rc;
     }

@@ -24,9 +24,9 @@
 void net_resolve(saber_hip_net* net) {
     std::vector<NetOp>& ops = net->ops;
     const int n = (int)ops.size();
-    enum { IN_CHAIN, IN_STAGE, IN_STEM, IN_SEP, IN_IR };
+    enum { IN_CHAIN, IN_STAGE, IN_STEM, IN_SEP, IN_IR, IN_FIRE };
     static const char* const covered[] = {"conv:(in the chain launch)", "conv:(in the stage launch)", "conv:(in the stem launch)", "conv:(in the separable launch)",
-                                          "conv:(in the inverted-residual launch)"};
+                                          "conv:(in the inverted-residual launch)", "conv:(in the fire launch)"};
     std::vector<int> in(n, IN_CHAIN);
     for (NetOp& o : ops) {
         o.launch = LAUNCH_OWN;
@@ -72,12 +72,17 @@ void net_resolve(saber_hip_net* net) {
             o.launch = LAUNCH_IR;
             absorb(i + 1, i, IN_IR);
             absorb(i + 2, i, IN_IR);
+        } else if (o.fire && o.fire_on && i + 3 < n) {      // (no op of a Fire site belongs to another site: formed that way)
+            o.launch = LAUNCH_FIRE;
+            for (int j = i + 1; j <= i + 3; ++j) absorb(j, i, IN_FIRE);
         }
     }
     for (int i = 0; i < n; ++i) {
         NetOp& o = ops[i];
         o.skip = o.launch == LAUNCH_NONE;
-        if (o.kind == OP_SOFTMAX) {
+        if (o.kind == OP_CONCAT) {
+            o.name = "concat" + std::to_string(o.ins.size()) + (o.skip ? " (in the fire launch)" : "");
+        } else if (o.kind == OP_SOFTMAX) {
             o.name = o.skip ? "softmax_f32 (in the fc launch)" : "softmax_f32";
         } else if (o.kind == OP_FC || o.kind == OP_FC_Q) {
             o.name = std::string("fc:") + o.fc->conv->algo_name;
@@ -92,6 +97,7 @@ void net_resolve(saber_hip_net* net) {
             case LAUNCH_CHAIN3: o.name = "conv:" + chain_form_name(o.chain3); break;
             case LAUNCH_SEP: o.name = std::string("conv:") + saber_hip_conv2d_sep_algo(o.sep); break;
             case LAUNCH_IR: o.name = std::string("conv:") + saber_hip_conv2d_ir_algo(o.ir); break;
+            case LAUNCH_FIRE: o.name = std::string("conv:") + saber_hip_conv2d_fire_algo(o.fire); break;
             case LAUNCH_STEM_PAIR: o.name = "conv:" + own + "+pair1x1_" + std::to_string(o.stem_pair->a->d.k) + "+" + std::to_string(o.stem_pair->b->d.k); break;
             case LAUNCH_STAGE:
                 o.name = std::string(o.head_on && !kept ? "conv:[pair1x1]+stage_c" : "conv:stage_c") + std::to_string(o.stage->c1) + "_" + std::to_string(o.stage_n) + "x[conv3x3+chain1x1]_2x16" +
@@ -161,6 +167,15 @@ void net_set_ir(saber_hip_net* net, int i, int code) {
     E.ir_on = code != 0;
     net_resolve(net);
 }
+// The Fire site headed by ops[i] (NetOp::fire): code = a valid form of the module -> the one launch with that form; 0 -> the four ops launch on
+// their own again.
+void net_set_fire(saber_hip_net* net, int i, int code) {
+    NetOp& Q = net->ops[i];
+    if (!Q.fire || i + 3 >= (int)net->ops.size()) return;
+    if (code && saber_hip_conv2d_fire_set_tile(Q.fire, code) != SABER_HIP_OK) code = 0;
+    Q.fire_on = code != 0;
+    net_resolve(net);
+}
 static int clone_conv_i8(const saber_hip_conv* src, const saber_hip_conv_desc& d, saber_hip_conv** out) {
     int rc = saber_hip_conv2d_create(&d, out);
     if (rc) return rc;
@@ -189,12 +204,12 @@ int saber_hip_net_optimize(saber_hip_net_t* net, int flags) {
     auto consumers = [&](int t) {
         int c = 0;
         for (size_t i = 0; i < ops.size(); ++i)
-            if (!dead[i]) c += (ops[i].in == t) + (ops[i].in2 == t);
+            if (!dead[i]) c += op_reads(ops[i], t);
         return c;
     };
     auto readers = [&](int t) {      // ... over the list as it stands (after the compaction below: every op)
         int r = 0;
-        for (const NetOp& o : ops) r += (o.in == t) + (o.in2 == t);
+        for (const NetOp& o : ops) r += op_reads(o, t);
         return r;
     };
     auto producer = [&](int t, int before) {   // last live op before `before` that writes tensor t
@@ -205,6 +220,8 @@ int saber_hip_net_optimize(saber_hip_net_t* net, int flags) {
     // an op of an inverted-residual site (flag 32768 in this or an earlier call): the expand op or one of the two behind it
     auto in_ir = [&](const NetOp& o) {
         const size_t i = (size_t)(&o - ops.data());
+        for (size_t b = 0; b <= 3 && b <= i && i < ops.size(); ++b)      // (... or of a Fire site, flag 65536: the squeeze op or one of the three behind it)
+            if (ops[i - b].fire != nullptr) return true;
         return o.ir != nullptr || (i > 0 && i < ops.size() && ops[i - 1].ir != nullptr) || (i > 1 && i < ops.size() && ops[i - 2].ir != nullptr);
     };
     // an op of a separable site (flag 16384 in an earlier call) or of an inverted-residual site keeps its conv: the site's object was made from it
@@ -235,7 +252,7 @@ int saber_hip_net_optimize(saber_hip_net_t* net, int flags) {
                 // and it must not alias the residual (in-place eltwise)
                 bool clash = e.out == tr;
                 for (int j = p + 1; j < (int)i && !clash; ++j)
-                    if (!dead[j]) clash = ops[j].in == e.out || ops[j].in2 == e.out || ops[j].out == e.out || ops[j].out2 == e.out;
+                    if (!dead[j]) clash = op_touches(ops[j], e.out);
                 if (clash) continue;
                 saber_hip_conv_desc d = src->d;
                 d.res_mode = SABER_HIP_RES_ELTWISE;
@@ -273,7 +290,7 @@ int saber_hip_net_optimize(saber_hip_net_t* net, int flags) {
                 if (ops[j].in2 == q.out && ops[j].kind == OP_CONV && ops[j].conv && !ops[j].chain && !ops[j].chain3 &&
                     ops[j].conv->d.res_mode == SABER_HIP_RES_ELTWISE && ops[j].conv->d.res_stride <= 1 && ops[j].lane == q.lane && !in_ir(ops[j]))
                     c = (int)j;
-                else if (ops[j].in == q.out || ops[j].in2 == q.out) break;       // some other reader
+                else if (op_reads(ops[j], q.out)) break;       // some other reader
             }
             if (c < 0) continue;
             const saber_hip_conv* src = ops[c].conv;
@@ -331,7 +348,7 @@ int saber_hip_net_optimize(saber_hip_net_t* net, int flags) {
                 {   // op j's output is written at position i instead: nothing in [i, j) may touch that tensor
                     bool clash = false;
                     for (size_t m = i; m < j && !clash; ++m)
-                        if (!dead[m]) clash = ops[m].in == ops[j].out || ops[m].in2 == ops[j].out || ops[m].out == ops[j].out || ops[m].out2 == ops[j].out;
+                        if (!dead[m]) clash = op_touches(ops[m], ops[j].out);
                     if (clash) continue;
                 }
                 saber_hip_conv* pair = nullptr;
@@ -389,7 +406,7 @@ int saber_hip_net_optimize(saber_hip_net_t* net, int flags) {
             {   // the pooled tensor is written at the CONV's position instead: nothing in (p, i) may read or write it
                 bool clash = false;
                 for (int j = p + 1; j < (int)i && !clash; ++j)
-                    if (!dead[j]) clash = ops[j].in == q.out || ops[j].in2 == q.out || ops[j].out == q.out || ops[j].out2 == q.out;
+                    if (!dead[j]) clash = op_touches(ops[j], q.out);
                 if (clash) continue;
             }
             saber_hip_conv* fused = nullptr;
@@ -438,6 +455,42 @@ int saber_hip_net_optimize(saber_hip_net_t* net, int flags) {
     bool two_lanes = false;
     for (const NetOp& o : ops) two_lanes |= o.lane != 0;
     if (two_lanes) flags &= ~(16 | 32);
+    // ---- 65536 (SABER_HIP_NET_FIRE): four consecutive lane-0 ops - a 1x1 squeeze conv, the two convs that alone read it (1x1, then 3x3), the u8
+    // concat that alone reads exactly those two, in that order, with all multipliers 1 (SqueezeNet's Fire module) - that
+    // saber_hip_conv2d_fire_create accepts -> a site of the one-launch form (conv_fire.hip). All four ops stay; which sites are on is
+    // fire_static_form's choice until the autotuner has timed every form against the four launches. No workgroup of that kernel depends on
+    // another: allowed on a shared device. Applied BEFORE the block, separable and chain flags, which skip the ops a Fire site holds (in_ir);
+    // ops another site already holds are skipped here. Counted: the sites formed (each removes three launches while a form is selected).
+    if ((flags & SABER_HIP_NET_FIRE) && !two_lanes) {
+        auto free_op = [&](size_t j) {
+            const NetOp& o = ops[j];
+            if (o.chain || o.chain3 || o.stem_pair || o.sep || o.stage || o.skip || o.lane || in_ir(o)) return false;
+            if (j > 0 && (ops[j - 1].chain || ops[j - 1].chain3 || ops[j - 1].stem_pair || ops[j - 1].sep)) return false;
+            return !(j > 1 && ops[j - 2].chain3 != nullptr);
+        };
+        for (size_t i = 0; i + 3 < ops.size(); ++i) {
+            NetOp& Q = ops[i];
+            NetOp& A = ops[i + 1];
+            NetOp& B = ops[i + 2];
+            NetOp& K = ops[i + 3];
+            if (Q.kind != OP_CONV || A.kind != OP_CONV || B.kind != OP_CONV || K.kind != OP_CONCAT || !Q.conv || !A.conv || !B.conv) continue;
+            if (!free_op(i) || !free_op(i + 1) || !free_op(i + 2) || !free_op(i + 3)) continue;
+            if (Q.in2 >= 0 || A.in2 >= 0 || B.in2 >= 0 || Q.out2 >= 0 || A.out2 >= 0 || B.out2 >= 0 || A.in != Q.out || B.in != Q.out) continue;
+            if (K.ins.size() != 2 || K.ins[0] != A.out || K.ins[1] != B.out || K.p[0] != SABER_HIP_U8) continue;
+            bool copy = true;
+            for (float m : K.cat_m) copy = copy && m == 1.0f;
+            if (!copy || readers(Q.out) != 2 || readers(A.out) != 1 || readers(B.out) != 1) continue;
+            if (K.cat_c[0] != A.conv->d.k || K.cat_c[1] != B.conv->d.k || K.count != (size_t)Q.conv->d.n * Q.conv->oh * Q.conv->ow) continue;
+            saber_hip_fire* fr = nullptr;
+            if (saber_hip_conv2d_fire_create(Q.conv, A.conv, B.conv, &fr) != SABER_HIP_OK) continue;      // not a module the kernel takes
+            net->owned_fires.push_back(fr);
+            Q.fire = fr;
+            Q.fire_out = K.out;
+            net_set_fire(net, (int)i, fire_static_form(fr));
+            ++removed;
+            i += 3;
+        }
+    }
     // ---- 32768 (SABER_HIP_NET_INVERTED_RESIDUAL): three consecutive lane-0 ops - a 1x1 expand conv, the depthwise 3x3 conv that alone reads it,
     // the 1x1 project conv that alone reads that (MobileNet-v2's blocks) - that saber_hip_conv2d_ir_create accepts -> a site of the one-launch
     // form (conv_ir.hip). Where the project conv carries the fused eltwise (flag 1 ran first) its residual must be the expand conv's input.

@@ -313,6 +313,35 @@ int saber_hip_relu_f32(size_t count, const float* x, float* y, saber_hip_stream_
     HIP_TRY(launch_relu_f32(count, x, y, (hipStream_t)s));
     return SABER_HIP_OK;
 }
+// the argument checks saber_hip_concat_nhwc and saber_hip_net_add_concat share (no device needed); *row_bytes = the inputs' bytes per pixel
+int concat_check(int n_inputs, const int* channels, const float* mult, int dtype, int* row_bytes) {
+    if (n_inputs < 1 || n_inputs > CONCAT_MAX_INPUTS) return fail(SABER_HIP_INVALID_VALUE, "concat: 1 .. 8 inputs");
+    if (dtype != SABER_HIP_F32 && dtype != SABER_HIP_S8 && dtype != SABER_HIP_U8) return fail(SABER_HIP_INVALID_VALUE, "concat: dtype is F32, S8 or U8");
+    if (!channels) return fail(SABER_HIP_INVALID_VALUE, "concat: null argument");
+    if (mult && dtype != SABER_HIP_U8) return fail(SABER_HIP_INVALID_VALUE, "concat: only u8 inputs are rescaled (f32 and s8 are copied: pass mult = NULL)");
+    long long total = 0;
+    for (int i = 0; i < n_inputs; ++i) {
+        if (channels[i] <= 0) return fail(SABER_HIP_INVALID_VALUE, "concat: a channel count is not positive");
+        if (mult && !(mult[i] > 0.f && std::isfinite(mult[i]))) return fail(SABER_HIP_INVALID_VALUE, "concat: a multiplier is not a positive finite number");
+        total += (long long)channels[i] * (dtype == SABER_HIP_F32 ? 4 : 1);
+        if (total > 0x7fffffffLL) return fail(SABER_HIP_INVALID_VALUE, "concat: the output row exceeds 2^31 bytes");
+        if (row_bytes) row_bytes[i] = channels[i] * (dtype == SABER_HIP_F32 ? 4 : 1);
+    }
+    return SABER_HIP_OK;
+}
+int saber_hip_concat_nhwc(size_t pixels, int n_inputs, const void* const* xs, const int* channels, const float* mult, int dtype, void* y,
+                          saber_hip_stream_t s) {
+    int row_bytes[CONCAT_MAX_INPUTS];
+    const int rc = concat_check(n_inputs, channels, mult, dtype, row_bytes);
+    if (rc) return rc;
+    if (!pixels) return SABER_HIP_OK;
+    if (!xs || !y) return fail(SABER_HIP_INVALID_VALUE, "concat: null argument");
+    for (int i = 0; i < n_inputs; ++i)
+        if (!xs[i]) return fail(SABER_HIP_INVALID_VALUE, "concat: null argument");
+    if (g_capture) return capture_concat(pixels, n_inputs, xs, channels, mult, dtype, y);
+    HIP_TRY(launch_concat_nhwc(pixels, n_inputs, xs, row_bytes, mult, y, (hipStream_t)s));
+    return SABER_HIP_OK;
+}
 static bool activation_kind_ok(int active) { return active == 1 || active == 3 || active == 4 || active == 5 || active == 9 || active == 11 || active == 12; }
 int saber_hip_activation_f32(int active, size_t count, float negative_slope, float coef, const float* x, float* y, saber_hip_stream_t s) {
     if (active == 2) {      // Active_relu: the standalone operator ignores negative_slope (saber_activation.cpp:136-154)

@@ -303,6 +303,59 @@ hipError_t launch_relu_f32(size_t count, const float* x, float* y, hipStream_t s
     return hipGetLastError();
 }
 
+// ---- concat along the channel axis of NHWC tensors (SaberConcat<X86>: impl/x86/saber_concat.cpp) ----------------------------
+// Input i holds [pixels][cb_i] bytes and lands at byte offset off_i of every [ctot]-byte output pixel. f32 / s8 and u8 with
+// m_i == 1: a byte copy. u8 with m_i != 1: y = sat_u8(rne(float(x) * m_i)), the sequence of kernel/jit_avx512_core_8bit_concat_kernel.cpp
+// (vpmovzxbd, vcvtdq2ps, vmulps, vcvtps2dq, vpmovusdb). blockIdx.y = the input; its lanes move `unit` bytes each - 16 where the row
+// length, the offset, the output row length and both pointers are multiples of 16, else 4, else 1 - so no access crosses the end of an
+// input row or leaves the input's slice of the output row.
+__device__ __forceinline__ unsigned concat_scale4(unsigned w, float m) {
+    unsigned o = 0;
+#pragma unroll
+    for (int t = 0; t < 4; ++t) o |= (unsigned)q_sat_u8(rintf(__fmul_rn((float)((w >> (8 * t)) & 0xffu), m))) << (8 * t);
+    return o;
+}
+__global__ __launch_bounds__(256) void concat_nhwc_kernel(size_t pixels, ConcatKArgs a, uint8_t* __restrict__ y) {
+    const int i = blockIdx.y;
+    const uint8_t* __restrict__ x = (const uint8_t*)a.x[i];
+    const int cb = a.cb[i], off = a.off[i], unit = a.unit[i];
+    const float m = a.m[i];
+    const bool copy = m == 1.0f;
+    const size_t per = (size_t)(cb / unit), total = pixels * per;
+    for (size_t gid = (size_t)blockIdx.x * 256 + threadIdx.x; gid < total; gid += (size_t)gridDim.x * 256) {
+        const size_t p = gid / per, u = gid - p * per;
+        const uint8_t* src = x + p * (size_t)cb + u * (size_t)unit;
+        uint8_t* dst = y + p * (size_t)a.ctot + (size_t)off + u * (size_t)unit;
+        if (unit == 16) {
+            uint4 v = *(const uint4*)src;
+            if (!copy) v = make_uint4(concat_scale4(v.x, m), concat_scale4(v.y, m), concat_scale4(v.z, m), concat_scale4(v.w, m));
+            *(uint4*)dst = v;
+        } else if (unit == 4) {
+            const unsigned v = *(const unsigned*)src;
+            *(unsigned*)dst = copy ? v : concat_scale4(v, m);
+        } else {
+            const unsigned v = *src;
+            *dst = copy ? (uint8_t)v : (uint8_t)q_sat_u8(rintf(__fmul_rn((float)v, m)));
+        }
+    }
+}
+hipError_t launch_concat_nhwc(size_t pixels, int n_inputs, const void* const* xs, const int* row_bytes, const float* mult, void* y, hipStream_t s) {
+    ConcatKArgs a = {};
+    size_t most = 0;
+    for (int i = 0; i < n_inputs; ++i) a.ctot += row_bytes[i];
+    for (int i = 0, off = 0; i < n_inputs; off += row_bytes[i], ++i) {
+        a.x[i] = xs[i];
+        a.cb[i] = row_bytes[i];
+        a.off[i] = off;
+        a.m[i] = mult ? mult[i] : 1.0f;
+        const uintptr_t bits = (uintptr_t)xs[i] | (uintptr_t)y | (uintptr_t)row_bytes[i] | (uintptr_t)off | (uintptr_t)a.ctot;
+        a.unit[i] = (bits & 15) == 0 ? 16 : ((bits & 3) == 0 ? 4 : 1);
+        most = std::max(most, pixels * (size_t)(row_bytes[i] / a.unit[i]));
+    }
+    hipLaunchKernelGGL(concat_nhwc_kernel, dim3(grid_for(most), n_inputs), dim3(256), 0, s, pixels, a, (uint8_t*)y);
+    return hipGetLastError();
+}
+
 // ---- the other activation types of SaberActivation<X86, AK_FLOAT> (saber_activation.cpp:156-262; the scalar formulas of
 // test/saber/test_saber_activation.cpp:17-115): elementwise, HBM-bound, in place allowed. `active` = the reference's ActiveType value.
 template <int ACTIVE>

@@ -417,6 +417,36 @@ void ir_pack(const int8_t* w_kc, int k, int c, std::vector<uint8_t>& out);      
 hipError_t conv_ir_prepare();      // per device, once: the kernels may use more than 64 KB of LDS
 hipError_t launch_conv_ir(int code, bool in_u8, const IrKArgs& a, hipStream_t s);      // sets the tile fields of `a` from the form
 
+// SqueezeNet's Fire module - a 1x1 squeeze conv (C -> S), the 1x1 (S -> E1) and the padded 3x3 (S -> E3) expand convs that both read it, and the
+// channel concat of the two - INT8, in one launch (conv_fire.hip). A workgroup owns a tile of pixels of one image and ALL of E1 + E3: it squeezes
+// the tile and a one-pixel halo on the i8 matrix cores into LDS (S padded to one 64-deep k-step), runs both expand convs from there and stores
+// each into its channel slice of the one output tensor. ACCEPTED: S in {16, 32, 48, 64}; C, E1, E3 multiples of 16, 16 <= C <= 512,
+// 16 <= E1, E3 <= 512; x s8 | u8; the three convs relu -> u8; stride 1, dilation 1, group 1, the 3x3 with pad 1.
+struct FireKArgs {
+    const void* x;        // [N][H][W][C] s8 | u8
+    const void* ws;       // the squeeze conv's weights in fragment order (ir_pack of [S][C])
+    const void* sprm;     // its {scale[4], bias'[4], comp[4]} per 4 channels, padded to 64 channels
+    const void* w1;       // the 1x1 expand conv's weights (ir_pack of [E1][S]: one k-step)
+    const void* prm1;
+    const void* w3;       // the 3x3 expand conv's weights: per tap (ir_pack of [E3][S]) - nine k-steps, [tap][group of 64][4][64 lanes][16]
+    const void* prm3;
+    void* y_s;            // [N][H][W][S] u8, or null: the squeeze edge is not written
+    void* y;              // [N][H][W][E1 + E3] u8: expand1x1 at channel 0, expand3x3 at channel E1
+    int N, H, W, C, S, E1, E3;
+    int th, tw, nf;       // the tile: th x tw pixels in nf fragments of 16
+    int hh, hw, hpf;      // its halo: (th + 2) x (tw + 2) pixels in hpf fragments of 16
+    int tiles_x, tiles_per_img;
+};
+// the launch forms: code 1 .. FIRE_MAX_CODE -> the tile; false: no such form for this shape, the shape is outside the accepted range, or the
+// LDS footprint is above FIRE_LDS_LIMIT
+constexpr int FIRE_MAX_CODE = 2;
+constexpr size_t FIRE_LDS_LIMIT = 80 * 1024 - 64;
+struct FireGeom { int th, tw, nf, hh, hw, hpf, tiles_x, tiles_y; size_t lds; };
+const char* conv_fire_form_name(int code);      // "" where the table has no such code
+bool conv_fire_geom(int code, int c, int s, int e1, int e3, int h, int w, FireGeom* g);
+hipError_t conv_fire_prepare();
+hipError_t launch_conv_fire(int code, bool in_u8, const FireKArgs& a, hipStream_t s);      // sets the tile fields of `a` from the form
+
 // reads `bytes` of device memory through every XCD (autotuning: the timed launch then finds none of its operands in
 // an L2, which is how it runs inside the op list)
 hipError_t launch_l2_flush(const void* buf, size_t bytes, unsigned* sink, hipStream_t s);
@@ -439,6 +469,16 @@ hipError_t launch_eltwise_sum_i8(size_t count, const int8_t* a, const int8_t* b,
 hipError_t launch_eltwise_sum_f32(size_t count, const float* a, const float* b, float c0, float c1, int relu,
                                   float* y, hipStream_t s);
 hipError_t launch_relu_f32(size_t count, const float* x, float* y, hipStream_t s);
+// concat along the channel axis of up to CONCAT_MAX_INPUTS NHWC tensors: rows of row_bytes[i] bytes per pixel, copied (mult NULL or 1) or - u8 -
+// rescaled by mult[i]
+constexpr int CONCAT_MAX_INPUTS = 8;
+struct ConcatKArgs {
+    const void* x[CONCAT_MAX_INPUTS];
+    int cb[CONCAT_MAX_INPUTS], off[CONCAT_MAX_INPUTS], unit[CONCAT_MAX_INPUTS];      // row bytes, byte offset in the output row, bytes per lane (16 | 4 | 1)
+    float m[CONCAT_MAX_INPUTS];
+    int ctot;                                                                         // output row bytes
+};
+hipError_t launch_concat_nhwc(size_t pixels, int n_inputs, const void* const* xs, const int* row_bytes, const float* mult, void* y, hipStream_t s);
 hipError_t launch_activation_f32(int active, size_t count, float slope, float coef, const float* x, float* y, hipStream_t s);
 hipError_t launch_prelu_f32(size_t count, int channels, int inner, int shared, const float* slope, const float* x, float* y, hipStream_t s);
 hipError_t launch_pool2d_i8_nhwc(int n, int h, int w, int c, int oh, int ow, int kh, int kw, int sh, int sw,

@@ -56,6 +56,9 @@ SYMBOLS = [
     "saber_hip_net_add_relu_f32", "saber_hip_net_add_activation_f32", "saber_hip_net_bind_tensor", "saber_hip_net_num_tensors", "saber_hip_net_tensor_bytes",
     "saber_hip_capture_begin", "saber_hip_capture_end", "saber_hip_capture_active", "saber_hip_net_tensor_of_ptr",
     "saber_hip_net_compact_arena", "saber_hip_net_arena_compacted", "saber_hip_serving_streams",
+    "saber_hip_concat_nhwc", "saber_hip_net_add_concat",
+    "saber_hip_conv2d_fire_create", "saber_hip_conv2d_fire_run", "saber_hip_conv2d_fire_set_tile", "saber_hip_conv2d_fire_get_tile",
+    "saber_hip_conv2d_fire_algo", "saber_hip_conv2d_fire_destroy",
 ]
 
 
@@ -264,6 +267,16 @@ def load():
     lib.saber_hip_capture_active.argtypes = []
     lib.saber_hip_net_tensor_of_ptr.argtypes = [P, P]
     lib.saber_hip_serving_streams.argtypes = [I, C.POINTER(P), C.POINTER(I)]
+    lib.saber_hip_conv2d_fire_create.argtypes = [P, P, P, C.POINTER(P)]
+    lib.saber_hip_conv2d_fire_run.argtypes = [P, P, P, P, P]
+    lib.saber_hip_conv2d_fire_set_tile.argtypes = [P, I]
+    lib.saber_hip_conv2d_fire_get_tile.argtypes = [P]
+    lib.saber_hip_conv2d_fire_algo.argtypes = [P]
+    lib.saber_hip_conv2d_fire_algo.restype = C.c_char_p
+    lib.saber_hip_conv2d_fire_destroy.argtypes = [P]
+    lib.saber_hip_conv2d_fire_destroy.restype = None
+    lib.saber_hip_concat_nhwc.argtypes = [Z, I, C.POINTER(P), C.POINTER(I), C.POINTER(F), I, P, P]
+    lib.saber_hip_net_add_concat.argtypes = [P, Z, I, C.POINTER(I), C.POINTER(I), C.POINTER(F), I, I]
     _lib = lib
     return lib
 

@@ -466,6 +466,37 @@ class SaberConvIR:
             pass
 
 
+class SaberConvFire:
+    """SqueezeNet's Fire module in ONE launch (saber_hip_conv2d_fire_create): a 1x1 squeeze conv, the 1x1 and the padded 3x3 expand convs that
+    read it, and the concat of the two. dispatch(x, y, y_squeeze=None): y is [n, h, w, E1 + E3], the squeeze edge only when it is wanted. The
+    output holds the bits of dispatching the three convs and the concat one after the other. The object keeps the weights the ops had."""
+
+    def __init__(self, squeeze, e1, e3):
+        self.ops = (squeeze, e1, e3)             # keep them alive: the object refers to them
+        self.h = C.c_void_p()
+        L.check(L.load().saber_hip_conv2d_fire_create(squeeze.h, e1.h, e3.h, C.byref(self.h)))
+
+    def dispatch(self, x, y, y_squeeze=None):
+        L.check(L.load().saber_hip_conv2d_fire_run(self.h, _p(x), _p(y_squeeze), _p(y), _stream()))
+        return y
+
+    def set_tile(self, code):
+        L.check(L.load().saber_hip_conv2d_fire_set_tile(self.h, code))
+
+    def tile(self):
+        return L.load().saber_hip_conv2d_fire_get_tile(self.h)
+
+    def algo(self):
+        return L.load().saber_hip_conv2d_fire_algo(self.h).decode()
+
+    def __del__(self):
+        try:
+            if self.h:
+                L.load().saber_hip_conv2d_fire_destroy(self.h)
+        except Exception:
+            pass
+
+
 class SaberStage:
     """XCD-resident stage (saber_hip_stage_create): `phases` = [(conv, in_slot, out_slot, res_slot | -1), ...] run as ONE
     persistent launch, image i on XCD i % 8; dispatch(tensors) takes the device tensors by slot. Every output slot holds
@@ -657,6 +688,48 @@ def eltwise_sum(a, b, coeff=(1.0, 1.0), relu=True, scale_a=1.0, scale_b=1.0, out
     return y
 
 
+class SaberConcat:
+    """Concat<MI355X, AK_FLOAT | AK_INT8> along the channel axis of NHWC tensors (saber/funcs/concat.h; saber_hip_concat_nhwc).
+
+    f32 and s8 inputs are copied whatever their scales (the reference's non-u8 branch is a memcpy). u8 inputs follow
+    SaberConcat<X86, AK_INT8>::create (saber/funcs/impl/x86/saber_concat.cpp:163-201): the output scale is the LARGEST input scale
+    and input i is multiplied by m_i = scale_max / scale_i - the direction is the reference's, written here exactly as it is there
+    (float32 division) - then rounded to nearest even and saturated to u8; an input whose m_i is 1 is copied."""
+
+    def __init__(self):
+        self.mult = None
+        self.out_scale = 1.0
+
+    def init(self, channels, dtype, scales=None):
+        """channels: per input; dtype: L.F32 | L.S8 | L.U8; scales: per-input activation scales (u8 only; None: all equal)."""
+        self.channels = [int(c) for c in channels]
+        self.dtype = int(dtype)
+        self.mult, self.out_scale = None, (float(scales[0]) if scales is not None else 1.0)
+        if scales is not None:
+            sc = np.asarray(scales, np.float32)
+            self.out_scale = float(sc.max())
+            if self.dtype == L.U8:
+                self.mult = (sc.max() / sc).astype(np.float32)      # scale_[i] = jpp_.scale_max / inputs[i]->get_scale()[0]
+                if np.all(self.mult == np.float32(1.0)):
+                    self.mult = None
+        return self
+
+    def _args(self):
+        n = len(self.channels)
+        ch = (C.c_int * n)(*self.channels)
+        m = None if self.mult is None else (C.c_float * n)(*[float(v) for v in self.mult])
+        return n, ch, m
+
+    def dispatch(self, xs, out=None):
+        """xs: NHWC (or [pixels, c]) tensors of one dtype and one pixel count; returns [..., sum(channels)]."""
+        n, ch, m = self._args()
+        lead = tuple(xs[0].shape[:-1])
+        y = _out(out, lead + (sum(self.channels),), xs[0].dtype)
+        ptrs = (C.c_void_p * n)(*[_p(x) for x in xs])
+        L.check(L.load().saber_hip_concat_nhwc(int(np.prod(lead)), n, ptrs, ch, m, self.dtype, _p(y), _stream()))
+        return y
+
+
 def pool_out_dim(inp, pad, win, stride, floor_mode=False, any_pad=None):
     """Pooling output size along one dimension. any_pad: pad_h > 0 or pad_w > 0 - the reference clips the last window of BOTH
     dimensions back inside the input whenever EITHER pad is non-zero (saber/funcs/pooling.h:113-120); None = this pad only."""
@@ -816,6 +889,20 @@ class Net:
         """INT8 fc reading an input already quantised with its in_scale (see add_pool_f32_from_i8_q)."""
         self.keep.append(fc)
         return self._chk(L.load().saber_hip_net_add_fc_q(self.h, fc.h, self.tid(xq), self.tid(y)))
+
+    def add_concat(self, names, out, concat=None):
+        """The channel concat of the named NHWC edges, in that order, into `out` (saber_hip_net_add_concat). Channel counts and dtype come
+        from the tensors' shapes; `concat` (a SaberConcat initialised with the inputs' scales) supplies u8 multipliers."""
+        tids = [self.tid(nm) for nm in names]
+        chans = [self.tensors[nm][1][-1] for nm in names]
+        dt = self.tensors[out][2]
+        code = L.F32 if dt == torch.float32 else (L.S8 if dt == torch.int8 else L.U8)
+        pixels = int(np.prod(self.tensors[out][1][:-1]))
+        n = len(names)
+        m = None
+        if concat is not None and concat.mult is not None:
+            m = (C.c_float * n)(*[float(v) for v in concat.mult])
+        return self._chk(L.load().saber_hip_net_add_concat(self.h, pixels, n, (C.c_int * n)(*tids), (C.c_int * n)(*chans), m, code, self.tid(out)))
 
     def add_softmax(self, rows, cols, x, y):
         return self._chk(L.load().saber_hip_net_add_softmax(self.h, rows, cols, self.tid(x), self.tid(y)))

@@ -137,6 +137,31 @@ def mobilenet_v2_spec():
     return L
 
 
+def squeezenet_v1_1_spec():
+    """SqueezeNet v1.1 (224 x 224): conv1 3x3 / 2 without padding, eight Fire modules with max pooling 3 / 2 (ceil mode) in front of
+    fire2, fire4 and fire6, conv10 1x1 -> 1000 classes, global average pooling, softmax. A Fire module (S, E1 + E3) is four entries: the
+    1x1 `squeeze1x1` conv to S channels, the 1x1 `expand1x1` (E1) and the padded 3x3 `expand3x3` (E3) convs that both read it, and a
+    `concat` entry (kind "concat", `srcs` in channel order) of the two. Every conv has relu and a plain bias, no BatchNorm. The
+    spatial sizes 111 -> 55 -> 27 -> 13 are all odd."""
+    L = [dict(kind="conv", name="conv1", src="data", cin=3, cout=64, k=3, stride=2, pad=0, relu=True),
+         dict(kind="pool", name="pool1", src="conv1", win=3, stride=2, pad=0, type=0)]
+    prev, cin = "pool1", 64
+    for i, (s, e) in zip(range(2, 10), [(16, 64), (16, 64), (32, 128), (32, 128), (48, 192), (48, 192), (64, 256), (64, 256)]):
+        f = "fire%d" % i
+        L.append(dict(kind="conv", name=f + "_squeeze1x1", src=prev, cin=cin, cout=s, k=1, stride=1, pad=0, relu=True))
+        L.append(dict(kind="conv", name=f + "_expand1x1", src=f + "_squeeze1x1", cin=s, cout=e, k=1, stride=1, pad=0, relu=True))
+        L.append(dict(kind="conv", name=f + "_expand3x3", src=f + "_squeeze1x1", cin=s, cout=e, k=3, stride=1, pad=1, relu=True))
+        L.append(dict(kind="concat", name=f + "_concat", srcs=[f + "_expand1x1", f + "_expand3x3"]))
+        prev, cin = f + "_concat", 2 * e
+        if i in (3, 5):
+            L.append(dict(kind="pool", name="pool%d" % i, src=prev, win=3, stride=2, pad=0, type=0))
+            prev = "pool%d" % i
+    L.append(dict(kind="conv", name="conv10", src=prev, cin=cin, cout=1000, k=1, stride=1, pad=0, relu=True))
+    L.append(dict(kind="gpool", name="pool10", src="conv10"))
+    L.append(dict(kind="softmax", name="prob", src="pool10"))
+    return L
+
+
 def conv_macs(spec, hw=224):
     """Algorithmic MACs per image of the conv + fc layers."""
     sizes, total = {"data": hw}, 0
@@ -151,6 +176,8 @@ def conv_macs(spec, hw=224):
             sizes[l["name"]] = int(rnd((s + 2 * l["pad"] - l["win"]) / l["stride"])) + 1
         elif l["kind"] == "eltwise":
             sizes[l["name"]] = sizes[l["a"]]
+        elif l["kind"] == "concat":
+            sizes[l["name"]] = sizes[l["srcs"][0]]
         elif l["kind"] == "fc":
             total += l["cin"] * l["cout"]
     return total
@@ -171,14 +198,15 @@ def framework_spec(spec, precision="int8"):
     * The tail runs 8-bit: an int8 -> fp32 edge would be f32, which SaberEltwise<AK_INT8> cannot write
       (saber_eltwise.cpp:85-95), so pool5 is an INT8 average pooling (s8 -> s8, scale inherited,
       saber_pooling.cpp:571-582) and the fc reads s8 (vender_fc.cpp:254-262 -> PackedMKLInt8Gemm).
+      A global pooling that no fc reads (SqueezeNet: it feeds the softmax) stays the FP32 pooling fed an 8-bit edge.
+    * A concat (SaberConcat<X86, AK_INT8>) has the dtype of its inputs: u8 behind relu convs.
     FP32: only the stride-up applies (conv + eltwise stay separate entries here; the FP32 executor fuses them)."""
     out = [dict(l) for l in spec]
     by = {l["name"]: l for l in out}
     readers = {}
     for l in out:
-        for key in ("src", "a", "b"):
-            if key in l:
-                readers.setdefault(l[key], []).append(l)
+        for src in [l[key] for key in ("src", "a", "b") if key in l] + list(l.get("srcs", ())):
+            readers.setdefault(src, []).append(l)
 
     def conv1x1(l, stride=None):
         return l["kind"] == "conv" and l["k"] == 1 and (stride is None or l["stride"] == stride)
@@ -224,7 +252,7 @@ def framework_spec(spec, precision="int8"):
                     nxt = readers.get(l["name"], [])
                     relu_conv = bool(nxt) and all(r["kind"] == "conv" and r["relu"] for r in nxt)
                     l["odt"] = U8 if relu_conv else S8
-            elif l["kind"] == "gpool":
+            elif l["kind"] == "gpool" and any(r["kind"] == "fc" for r in readers.get(l["name"], [])):
                 l["int8"] = True
     return out
 
@@ -256,14 +284,15 @@ def fold_bn(w, bias, bn_scale, eps, mean, var, scale_w, scale_b):
 def build_model(name="resnet50", seed=42):
     """Seeded weights: conv ~ N(0, sqrt(2/(C*k*k))), BN gamma U(.5,1.5), beta/mean U(-.1,.1), var U(.5,1.5)."""
     spec = {"resnet50": lambda: resnet_spec(50), "resnet101": lambda: resnet_spec(101), "vgg16": vgg16_spec,
-            "mobilenet_v1": mobilenet_v1_spec, "mobilenet_v2": mobilenet_v2_spec, "resnext50_32x4d": resnext_spec}[name]()
+            "mobilenet_v1": mobilenet_v1_spec, "mobilenet_v2": mobilenet_v2_spec, "resnext50_32x4d": resnext_spec,
+            "squeezenet_v1_1": squeezenet_v1_1_spec}[name]()
     params, raw = {}, {}          # raw: the BatchNorm / Scale blobs before folding (what a model file holds)
     for idx, l in enumerate(spec):
         rng = np.random.default_rng(seed + idx)
         if l["kind"] == "conv":
             c, k, ks = l["cin"] // l.get("group", 1), l["cout"], l["k"]      # (a depthwise weight is [C, 1, 3, 3], std sqrt(2 / 9))
             w = (rng.standard_normal((k, c, ks, ks)) * np.sqrt(2.0 / (c * ks * ks))).astype(np.float32)
-            if name == "vgg16":
+            if name in ("vgg16", "squeezenet_v1_1"):      # plain biases, no BatchNorm
                 b = (rng.uniform(-0.1, 0.1, k)).astype(np.float32)
                 params[l["name"]] = (w, b)
             else:
@@ -287,7 +316,9 @@ def make_input(batch, seed=1234, hw=224):
 
 # --------------------------------------------------------------------------------------------- calibration
 def calibrate(model, x):
-    """MAXABS per-edge scales from one FP32 pass (torch CPU conv: model preparation, not the hot path)."""
+    """MAXABS per-edge scales from one FP32 pass (torch CPU conv: model preparation, not the hot path). A concat's scale is the largest
+    of its inputs' scales (SaberConcat<X86, AK_INT8>::create) and is handed back to those input edges: the convs in front then
+    requantise straight to the common scale and the INT8 concat is a copy."""
     import torch
     import torch.nn.functional as Fn
     t = {"data": torch.from_numpy(x)}
@@ -315,6 +346,12 @@ def calibrate(model, x):
                     y = torch.relu(y)
             elif kd == "softmax":
                 y = torch.softmax(t[l["src"]], 1)
+            elif kd == "concat":
+                t[l["name"]] = torch.cat([t[s] for s in l["srcs"]], 1)
+                scales[l["name"]] = max(scales[s] for s in l["srcs"])
+                for s in l["srcs"]:
+                    scales[s] = scales[l["name"]]
+                continue
             t[l["name"]] = y
             scales[l["name"]] = max(float(y.abs().max()), 1e-6) / 127.0
     return scales
@@ -326,7 +363,7 @@ def _out_hw(h, k, s, p):
 
 
 def build_int8_net(model, scales, batch, hw=224, fuse=True, chain=2, stage=True, stem_pair=True, head_pair=False, shared_device=False,
-                   fc_softmax=True, absorb_pool=True, separable=False, inverted=False, before_finalize=None, **legacy):
+                   fc_softmax=True, absorb_pool=True, separable=False, inverted=False, fire=False, before_finalize=None, **legacy):
     """ResNet INT8 op list on the device (see the module docstring for the dtype rules): ONE op per reference operator, exactly the list
     `model["spec"]` holds (workloads.framework_spec: what the reference's own optimiser emits) - and, with `fuse`, handed to the C++ host
     side (saber_hip_net_optimize, the product's only executor-level fuser) which finds conv + eltwise, sibling pairs, conv + pooling,
@@ -350,6 +387,10 @@ def build_int8_net(model, scales, batch, hw=224, fuse=True, chain=2, stage=True,
     with the block's fused eltwise sum) become sites of the one-launch form (flag SABER_HIP_NET_INVERTED_RESIDUAL = 32768, after the flag-15
     pass and BEFORE the separable and chain flags, which skip the ops a block site holds): net.inverted counts them. Which sites run fused is
     the static rule's choice, then the autotuner's (profiles/ir/README.md); the default builds exactly the list it built before.
+    fire (opt-in): a 1x1 squeeze conv, the 1x1 and 3x3 expand convs that alone read it and the u8 concat of exactly those two (SqueezeNet's Fire
+    module) become sites of the one-launch form (flag SABER_HIP_NET_FIRE = 65536, after the flag-15 pass and before every other site flag):
+    net.fired counts them. Which sites run fused is the static rule's choice (none without a measured row), then the autotuner's
+    (profiles/fire/README.md); the default builds exactly the list it built before.
     before_finalize (optional): called with the net once the op list has its final form, just before finalize() - the place to bind
     tensors to caller-owned memory (Net.bind; net.tensors maps every edge name to its id).
     (The Python fuser of rounds 1 - 5 lives in tests/py_fuser.py: test infrastructure.)"""
@@ -392,6 +433,14 @@ def build_int8_net(model, scales, batch, hw=224, fuse=True, chain=2, stage=True,
             net.add_tensor(nm, (B, ho, ho, c), S8)
             coeff = 1.0 / scales[nm]
             net.add_eltwise_i8(B * ho * ho * c, scales[l["a"]], scales[l["b"]], coeff, coeff, l["relu"], l["a"], l["b"], nm)
+        elif kd == "concat":
+            # SaberConcat<AK_INT8>: the inputs' dtype, the largest input scale; with calibrate()'s scales every multiplier is 1 (a copy)
+            ho, dt = shape[l["srcs"][0]][0], dtype[l["srcs"][0]]
+            chans = [shape[s][1] for s in l["srcs"]]
+            cat = S.SaberConcat().init(chans, dt, [scales[s] for s in l["srcs"]])
+            shape[nm], dtype[nm], scales[nm] = (ho, sum(chans)), dt, cat.out_scale
+            net.add_tensor(nm, (B, ho, ho, sum(chans)), dt)
+            net.add_concat(l["srcs"], nm, cat)
         elif kd == "gpool" and l.get("int8"):
             # INT8 global average pooling (framework_spec): s8 NHWC -> s8 [B,1,1,c], scale inherited
             hin, c = shape[l["src"]]
@@ -412,16 +461,19 @@ def build_int8_net(model, scales, batch, hw=224, fuse=True, chain=2, stage=True,
             net.add_tensor(nm, (B, l["cout"]), F32)
             net.add_fc(fc, l["src"], nm)
         elif kd == "softmax":
-            classes = next(e["cout"] for e in model["spec"] if e["name"] == l["src"])      # (the fc in front of it: 1000 for the BASELINE models)
+            # (the fc in front of it: 1000 for the BASELINE models; SqueezeNet: the channels of the global pooling)
+            classes = next(e.get("cout", shape.get(l["src"], (0, 0))[1]) for e in model["spec"] if e["name"] == l["src"])
             net.add_tensor(nm, (B, classes), F32)
             net.add_softmax(B, classes, l["src"], nm)
     net.unfused_ops = net.num_ops()
     if shared_device:
         net.optimize(2048)           # (sticks to the net: every later optimize / autotune / set_choices call honours it)
         stage = False
-    net.removed = net.absorbed = net.gpooled = net.stem_paired = net.chained = net.fc_softmaxed = net.separated = net.inverted = 0
+    net.removed = net.absorbed = net.gpooled = net.stem_paired = net.chained = net.fc_softmaxed = net.separated = net.inverted = net.fired = 0
     if fuse:
         net.removed = net.optimize(15)      # conv + eltwise, sibling pairs, conv + pooling, pool -> fc quantisation
+    if fire:
+        net.fired = net.optimize(65536)          # the sites formed (each removes three launches while one of its forms is selected)
     if inverted:
         net.inverted = net.optimize(32768)       # the sites formed (each removes two launches while one of its forms is selected)
     if separable:
@@ -490,9 +542,8 @@ def build_fp32_net(model, batch, hw=224, pair_siblings=True, fuse_pool=True, sha
     sib = {}
     consumers = {}
     for e in spec:
-        for key in ("src", "a", "b"):
-            if key in e:
-                consumers[e[key]] = consumers.get(e[key], 0) + 1
+        for src in [e[key] for key in ("src", "a", "b") if key in e] + list(e.get("srcs", ())):
+            consumers[src] = consumers.get(src, 0) + 1
     def mark(*names):
         for n_ in names:
             produced.append((net.num_ops() - 1, n_))
@@ -561,6 +612,12 @@ def build_fp32_net(model, batch, hw=224, pair_siblings=True, fuse_pool=True, sha
             net.add_pool_f32(B, hin, hin, c, ho, ho, (l["win"],) * 2, (l["stride"],) * 2, (l["pad"],) * 2, l["type"],
                              L.NHWC, T(l["src"]), nm)
             mark(nm)
+        elif kd == "concat":
+            ho, chans = shape[T(l["srcs"][0])][0], [shape[T(s)][1] for s in l["srcs"]]
+            net.add_tensor(nm, (B, ho, ho, sum(chans)), F32)
+            shape[nm] = (ho, sum(chans))
+            net.add_concat([T(s) for s in l["srcs"]], nm)
+            mark(nm)
         elif kd == "eltwise":
             pass  # fused into branch2c above
         elif kd == "gpool":
@@ -582,7 +639,7 @@ def build_fp32_net(model, batch, hw=224, pair_siblings=True, fuse_pool=True, sha
                 net.add_eltwise_f32(B * l["cout"], 0.5, 0.5, True, nm, nm, nm)
             mark(nm)
         elif kd == "softmax":
-            classes = next(e["cout"] for e in spec if e["name"] == l["src"])
+            classes = next(e.get("cout", shape.get(l["src"], (0, 0))[1]) for e in spec if e["name"] == l["src"])
             net.add_tensor(nm, (B, classes), F32)
             net.add_softmax(B, classes, T(l["src"]), nm)
             mark(nm)
@@ -619,6 +676,8 @@ def algorithmic_bytes_int8(model, batch, hw=224):
             sizes[l["name"]] = (int(rnd((hin + 2 * l["pad"] - l["win"]) / l["stride"])) + 1, c)
         elif l["kind"] == "eltwise":
             sizes[l["name"]] = sizes[l["a"]]
+        elif l["kind"] == "concat":      # (no conv / fc kernel: the copy itself is not compulsory traffic)
+            sizes[l["name"]] = (sizes[l["srcs"][0]][0], sum(sizes[s][1] for s in l["srcs"]))
         elif l["kind"] == "fc":
             wts += l["cin"] * l["cout"]
     return act * batch + wts

@@ -323,6 +323,24 @@ int saber_hip_conv2d_ir_get_tile(const saber_hip_ir_t* ir);
 const char* saber_hip_conv2d_ir_algo(const saber_hip_ir_t* ir);
 void saber_hip_conv2d_ir_destroy(saber_hip_ir_t* ir);
 
+/* SqueezeNet's Fire module as ONE launch (anakin_amd/csrc/conv_fire.hip: fire_squeeze_expand_i8): `squeeze` = a plain 1x1 / stride-1 INT8
+ * conv C -> S with relu (x s8 | u8 NHWC, u8 out), `e1` = the plain 1x1 conv S -> E1 and `e3` = the 3x3 / pad-1 conv S -> E3 that both read
+ * it (relu, u8 out; their output scales may differ), and the channel concat of the two with all multipliers 1. S in {16, 32, 48, 64}; C,
+ * E1, E3 multiples of 16 up to 512; stride 1, no dilation, group 1. A workgroup squeezes a pixel tile and its one-pixel halo into LDS (halo
+ * pixels outside the image are zero bytes, not squeeze(0)) and runs both expand convs from there. y [n, h, w, E1 + E3] holds e1's bytes at
+ * channel 0 and e3's at channel E1 - the bytes of running the three ops and saber_hip_concat_nhwc one after the other; y_squeeze
+ * [n, h, w, S] is written unless it is NULL. The object refers to the three ops (they must outlive it) and KEEPS THE WEIGHTS ITS MEMBERS HAD
+ * WHEN IT WAS CREATED. Null operands: SABER_HIP_INVALID_VALUE; operands outside that range, or without weights: SABER_HIP_UNIMPL. set_tile
+ * takes a form code (1 = 4 x 16 pixel tiles, 2 = 2 x 16); a code without a form returns SABER_HIP_INVALID_VALUE and changes nothing.
+ * algo: "fire_squeeze_expand_i8_<form>". */
+typedef struct saber_hip_fire saber_hip_fire_t;
+int saber_hip_conv2d_fire_create(saber_hip_conv_t* squeeze, saber_hip_conv_t* e1, saber_hip_conv_t* e3, saber_hip_fire_t** out);
+int saber_hip_conv2d_fire_run(saber_hip_fire_t* fire, const void* x, void* y_squeeze /* may be NULL */, void* y, saber_hip_stream_t stream);
+int saber_hip_conv2d_fire_set_tile(saber_hip_fire_t* fire, int code);
+int saber_hip_conv2d_fire_get_tile(const saber_hip_fire_t* fire);
+const char* saber_hip_conv2d_fire_algo(const saber_hip_fire_t* fire);
+void saber_hip_conv2d_fire_destroy(saber_hip_fire_t* fire);
+
 /* XCD-resident stage: a run of INT8 convolutions over SMALL feature maps (h * w <= 64 pixels per image: ResNet's res5) as
  * ONE persistent launch. Image i is computed entirely on XCD i % 8 (32 CUs, one workgroup each); the convolutions
  * ("phases") follow each other inside the kernel, separated by an XCD-local barrier where one reads what an earlier one
@@ -454,6 +472,15 @@ int saber_hip_activation_f32(int active, size_t count, float negative_slope, flo
                              saber_hip_stream_t stream);
 int saber_hip_prelu_f32(size_t count, int channels, int inner, int channel_shared, const float* slope, const float* x, float* y,
                         saber_hip_stream_t stream);
+/* Concat<T,D> along the channel axis of NHWC tensors (saber/funcs/concat.h; x86: saber/funcs/impl/x86/saber_concat.cpp): input i
+ * is [pixels][channels[i]], y is [pixels][sum of channels], pixels = N * H * W, 1 .. 8 inputs. dtype F32 / S8: a copy, whatever the
+ * tensors' scales (the reference's non-u8 branch is a memcpy). dtype U8: `mult` (host memory, n_inputs values > 0, or NULL = all 1)
+ * rescales input i - y = saturate_u8(round_to_nearest_even(float(x) * mult[i])), the arithmetic of
+ * kernel/jit_avx512_core_8bit_concat_kernel.cpp; an input with mult[i] == 1 is copied. Which multipliers belong to which scales is
+ * the caller's business (SaberConcat::create, saber_concat.cpp:163-201). SABER_HIP_INVALID_VALUE: n_inputs outside 1 .. 8, a
+ * channel count <= 0, a multiplier that is not a positive finite number, multipliers with a dtype other than U8. */
+int saber_hip_concat_nhwc(size_t pixels, int n_inputs, const void* const* xs, const int* channels, const float* mult, int dtype,
+                          void* y, saber_hip_stream_t stream);
 /* Pooling<>::compute_output_shape (pooling.h:69-130) */
 int saber_hip_pool_out_dim(int in, int pad, int window, int stride, int floor_mode);
 /* The same for one dimension of a pooling whose OTHER dimension may be padded: the reference clips the last window of
@@ -580,6 +607,14 @@ int saber_hip_net_add_fc_q(saber_hip_net_t* net, saber_hip_fc_t* op, int in_q_id
 #define SABER_HIP_NET_REPRODUCIBLE_FP32 8192
 #define SABER_HIP_NET_SEPARABLE 16384
 #define SABER_HIP_NET_INVERTED_RESIDUAL 32768
+/* 65536 (SABER_HIP_NET_FIRE; NOT in 255, never implied): four consecutive lane-0 ops - a 1x1 squeeze conv, the 1x1 and the 3x3 conv that alone
+ * read it, and the u8 concat that alone reads exactly those two, in that order, with all multipliers 1 (SqueezeNet's Fire module) - that
+ * saber_hip_conv2d_fire_create accepts become a SITE of the one-launch form. All four ops stay in the list; while a form is selected the
+ * squeeze op's launch covers the other three and the three inner edges report saber_hip_net_tensor_unwritten. Which sites are on is the
+ * static rule's choice (none without a measured row) until saber_hip_net_autotune has timed every form against the four launches; the
+ * decision travels in the squeeze op's choice word like a block decision (bit 31 without bit 30, form code in bits 24..27). Apply it before
+ * the chain and separable flags: no op belongs to two sites. Returns the number of sites formed. */
+#define SABER_HIP_NET_FIRE 65536
 int saber_hip_net_optimize(saber_hip_net_t* net, int flags);
 /* How many cooperative launches of this net have reported a failed pass since it was created (each made saber_hip_net_status /
  * the site's next launch return SABER_HIP_RUNTIME_ERROR once and its site fall back to single-workgroup launches): 0 on a net that
@@ -657,6 +692,11 @@ void saber_hip_net_destroy(saber_hip_net_t* net);
 int saber_hip_net_add_relu_f32(saber_hip_net_t* net, size_t count, int in_id, int out_id);
 int saber_hip_net_add_activation_f32(saber_hip_net_t* net, int active, size_t count, float negative_slope, float coef, int in_id,
                                      int out_id);
+/* saber_hip_concat_nhwc inside an op list: in_ids[0 .. n_inputs) in channel order (the same tensor may appear twice), the rest as
+ * there. The op is named concat<n_inputs>; the arena planner, the lanes and saber_hip_net_op_work (bytes read + written, no flops)
+ * see every input. */
+int saber_hip_net_add_concat(saber_hip_net_t* net, size_t pixels, int n_inputs, const int* in_ids, const int* channels,
+                             const float* mult, int dtype, int out_id);
 /* Caller-owned storage for tensor `id` instead of a slot of the net's arena (the net's inputs and outputs when the caller
  * has buffers of its own: the reference's Net owns its edge tensors). Before finalize any tensor can be bound (ptr != NULL)
  * or returned to the arena (NULL); after finalize only the address of an already external tensor can change. A captured

@@ -274,6 +274,12 @@ struct SoftmaxParam {   // saber_funcs_param.h: axis only
     int axis;
 };
 
+template <typename TargetType>
+struct ConcatParam {   // saber_funcs_param.h:450-467: axis only
+    explicit ConcatParam(int axis_in = 1) : axis(axis_in) {}
+    int axis;
+};
+
 }  // namespace saber
 }  // namespace anakin
 
@@ -328,6 +334,8 @@ template <typename TargetType, DataType OpDtype>
 using SaberEltwise = SaberEltwiseMI355X<TargetType, OpDtype>;
 template <typename TargetType, DataType OpDtype>
 using SaberSoftmax = SaberSoftmaxMI355X<TargetType, OpDtype>;
+template <typename TargetType, DataType OpDtype>
+using SaberConcat = SaberConcatMI355X<TargetType, OpDtype>;
 template <typename TargetType, DataType OpDtype>
 using SaberActivation = SaberActivationMI355X<TargetType, OpDtype>;
 template <typename TargetType>

@@ -15,6 +15,7 @@
 
 #include "saber_hip.h"
 
+#include <algorithm>
 #include <cstring>
 #include <vector>
 
@@ -460,6 +461,69 @@ public:
                                                        param.coeff[0], param.coeff[1], relu,
                                                        (float*)outputs[0]->mutable_data(), stream));
     }
+};
+
+// Concat<MI355X, OpDtype> (saber/funcs/concat.h; x86: saber_concat.cpp) along the channel axis of 1 .. 8 tensors of one dtype:
+// NHWC (axis 3: the 8-bit edges and the target's FP32 edges) or any layout whose pixels collapse to one (NCHW [n, c, 1, 1], axis 1).
+// f32 and s8: a copy. u8: the x86 create's loops as they are written (saber_concat.cpp:163-201) - scale_max starts at the first
+// input's scale (1 without one), every scaled input raises it, an unscaled input RESETS it to 1 (a later, larger scale raises it
+// again); multiplier scale_max / scale_i per scaled input, scale_max for an unscaled one - handed to saber_hip_concat_nhwc, which
+// copies where the multiplier is 1. (The x86 kernel chooses between its copy and its float path with |scale_max - scale_i| >
+// FLT_MIN; here the multiplier itself decides: where it rounds to 1.0f the float path would return the byte unchanged.)
+template <typename TargetType, DataType OpDtype>
+class SaberConcatMI355X : public ImplBase<TargetType, OpDtype, ConcatParam<TargetType> > {
+public:
+    virtual SaberStatus init(const std::vector<Tensor<TargetType>*>& inputs, std::vector<Tensor<TargetType>*>& outputs,
+                             ConcatParam<TargetType>& param, Context<TargetType>& ctx) {
+        this->_ctx = &ctx;
+        return create(inputs, outputs, param, ctx);
+    }
+    virtual SaberStatus create(const std::vector<Tensor<TargetType>*>& inputs, std::vector<Tensor<TargetType>*>& outputs,
+                               ConcatParam<TargetType>& param, Context<TargetType>& ctx) {
+        this->_ctx = &ctx;
+        if (inputs.empty() || inputs.size() > 8 || outputs.empty()) return SaberUnImplError;
+        const DataType dt = inputs[0]->get_dtype();
+        if (dt != AK_FLOAT && dt != AK_INT8 && dt != AK_UINT8) return SaberUnImplError;
+        // the concat axis must be the innermost one that is not 1: every input is then [pixels][channels]
+        if (inputs[0]->count_valid(param.axis + 1, inputs[0]->dims()) != 1) return SaberUnImplError;
+        _pixels = (size_t)inputs[0]->count_valid(0, param.axis);
+        _channels.clear();
+        _mult.clear();
+        float scale_max = inputs[0]->get_scale().size() ? inputs[0]->get_scale()[0] : 1.f;
+        for (size_t i = 0; i < inputs.size(); ++i) {
+            if (inputs[i]->get_dtype() != dt || inputs[i]->get_layout() != inputs[0]->get_layout()) return SaberUnImplError;
+            if ((size_t)inputs[i]->count_valid(0, param.axis) != _pixels || inputs[i]->count_valid(param.axis + 1, inputs[i]->dims()) != 1)
+                return SaberUnImplError;
+            _channels.push_back(inputs[i]->valid_shape()[param.axis]);
+            if (inputs[i]->get_scale().size()) scale_max = std::max(scale_max, inputs[i]->get_scale()[0]);      // :169-178
+            else scale_max = 1.f;
+        }
+        if (outputs[0]->get_dtype() != dt) return SaberUnImplError;
+        if (dt == AK_UINT8) {
+            bool copy = true;
+            for (size_t i = 0; i < inputs.size(); ++i) {
+                _mult.push_back(inputs[i]->get_scale().size() ? scale_max / inputs[i]->get_scale()[0] : scale_max);
+                copy = copy && _mult.back() == 1.f;
+            }
+            if (copy) _mult.clear();
+        }
+        _dtype = mi355x_dtype(dt);
+        return SaberSuccess;
+    }
+    virtual SaberStatus dispatch(const std::vector<Tensor<TargetType>*>& inputs, std::vector<Tensor<TargetType>*>& outputs,
+                                 ConcatParam<TargetType>& param) {
+        if (inputs.size() != _channels.size()) return SaberInvalidValue;      // (create refused more than 8; the list must be the one it saw)
+        const void* xs[8];
+        for (size_t i = 0; i < inputs.size(); ++i) xs[i] = inputs[i]->data();
+        return mi355x_status(saber_hip_concat_nhwc(_pixels, (int)_channels.size(), xs, _channels.data(), _mult.empty() ? nullptr : _mult.data(),
+                                                   _dtype, outputs[0]->mutable_data(), (saber_hip_stream_t)this->_ctx->get_compute_stream()));
+    }
+
+private:
+    size_t _pixels = 0;
+    int _dtype = 0;
+    std::vector<int> _channels;
+    std::vector<float> _mult;
 };
 
 // Softmax<MI355X, AK_FLOAT> (saber/funcs/softmax.h; x86: saber_softmax.cpp) over `axis` when everything after it is 1

@@ -12,3 +12,5 @@ template class anakin::saber::SaberConv2DPoolingMI355X<X86, AK_INT8>;
 template class anakin::saber::SaberFcMI355X<X86, AK_INT8>;
 template class anakin::saber::SaberFcMI355X<X86, AK_FLOAT>;
 template class anakin::saber::SaberGemmMI355X<X86>;
+template class anakin::saber::SaberConcatMI355X<X86, AK_INT8>;
+template class anakin::saber::SaberConcatMI355X<X86, AK_FLOAT>;
