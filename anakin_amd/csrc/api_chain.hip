@@ -175,6 +175,16 @@ static void pack_stage1_c128_stream(const saber_hip_conv* c3, const saber_hip_co
         for (int ks = 0; ks < 8; ++ks) pack_frag1(b->wq_oihw.data(), K1, w * 16, 1, 0, ks, out);
     }
 }
+// ... and the C = 64 stage kernel's (conv_stage1_c64_kernel, four waves): per wave w, in consumption order:
+//   3x3, channels w*16 .. +15: [tap] (9) | 1x1 + eltwise, channels w*64 .. +63: [accumulator 0..3] (4) | 1x1, channels w*16 .. +15: [k-step 0..3] (4)
+void pack_stage1_c64_stream(const int8_t* w3, const int8_t* wa, const int8_t* wb, std::vector<uint8_t>& out) {
+    const int C = 64, K1 = 256;
+    for (int w = 0; w < 4; ++w) {
+        for (int tap = 0; tap < 9; ++tap) pack_frag3(w3, C, w * 16, tap, 0, out);
+        for (int mf = 0; mf < 4; ++mf) pack_frag1(wa, C, w * 64, 4, mf, 0, out);
+        for (int ks = 0; ks < 4; ++ks) pack_frag1(wb, K1, w * 16, 1, 0, ks, out);
+    }
+}
 // ------------------------------------------------------------------------------------------------
 // stem conv + max pooling + the sibling pair of 1x1 convs on the pooled tensor in ONE launch (conv_stem.h)
 // ------------------------------------------------------------------------------------------------
@@ -240,7 +250,7 @@ saber_hip_chain::~saber_hip_chain() {
     delete stage1;
 }
 // ------------------------------------------------------------------------------------------------
-// stage: a run of 3x3-led C = 256 chains in ONE persistent launch (conv_stage_coop.hip)
+// stage: a run of 3x3-led C = 256 (or 128, or 64) chains in ONE persistent launch (conv_stage_coop.hip)
 // ------------------------------------------------------------------------------------------------
 // ceil(2^32 / d) for the kernels' __umulhi divisions by a tile count; 0 for d == 1 (they then skip the division)
 static unsigned div_magic(int d) { return d >= 2 ? (unsigned)((0x100000000ull + (unsigned)d - 1) / (unsigned)d) : 0u; }
@@ -282,14 +292,14 @@ static int stage_build(saber_hip_chain* const* chains, int n, bool per_image, sa
         if (tail->a->d.res_stride != 2) return fail(SABER_HIP_INVALID_VALUE, "stage: the tail's shortcut must be sub-sampled by 2");
     }
     if (n > 1 && !per_image) return fail(SABER_HIP_INVALID_VALUE, "stage: several blocks need an image per XCD");
-    if (n < 2 && chains[0] && chains[0]->c1 == 128) return fail(SABER_HIP_INVALID_VALUE, "stage: at C = 128 a stage is at least two blocks");
+    if (n < 2 && chains[0] && (chains[0]->c1 == 128 || chains[0]->c1 == 64)) return fail(SABER_HIP_INVALID_VALUE, "stage: at C = 128 / 64 a stage is at least two blocks");
     const saber_hip_chain* c0 = chains[0];
     std::vector<saber_mi355x::StageBlk> blk;
     for (int k = 0; k < n; ++k) {
         const saber_hip_chain* ch = chains[k];
-        const uint8_t* stream = !ch ? nullptr : (ch->c1 == 256 ? ch->d_stream[CS_COOP4].p : (ch->c1 == 128 ? ch->d_stream_stage1.p : nullptr));
+        const uint8_t* stream = !ch ? nullptr : (ch->c1 == 256 ? ch->d_stream[CS_COOP4].p : (ch->c1 == 128 || ch->c1 == 64 ? ch->d_stream_stage1.p : nullptr));
         if (!ch || ch->c1 != c0->c1 || !ch->c3 || !ch->b || !stream || ch->c3->d.stride_h != 1)
-            return fail(SABER_HIP_INVALID_VALUE, "stage: every block must be a conv3x3 (stride 1) + conv1x1 + conv1x1 chain at C = 256 (or all at C = 128)");
+            return fail(SABER_HIP_INVALID_VALUE, "stage: every block must be a conv3x3 (stride 1) + conv1x1 + conv1x1 chain at C = 256 (or all at C = 128, or all at C = 64)");
         const saber_hip_conv_desc& da = ch->a->d;
         if (da.n != c0->a->d.n || da.h != c0->a->d.h || da.w != c0->a->d.w) return fail(SABER_HIP_INVALID_VALUE, "stage: blocks of one tensor shape");
         if (k && ((ch->c3->x_dtype == DT_U8) != (chains[k - 1]->b->d.out_dtype == SABER_HIP_U8)))
@@ -319,14 +329,17 @@ static int stage_build(saber_hip_chain* const* chains, int n, bool per_image, sa
     st->tiles_per_img = st->tiles_x * ((d0.h + 1) / 2);
     st->per_image = per_image;
     // every workgroup of an image must hold a CU of its XCD at once (one workgroup per CU: 235 - 250 VGPRs); C = 256: four workgroups per
-    // tile, edge counters for one column tile; C = 128: one per tile, 1 / 2 / 4 column tiles (arrivals per edge: a power of two)
+    // tile, edge counters for one column tile; C = 128: one per tile, 1 / 2 / 4 column tiles (arrivals per edge: a power of two);
+    // C = 64: one per tile and SEVERAL workgroups per CU (conv_stage1_c64_kernel: 128 VGPRs, 22 KB of LDS) - as many as the runtime's
+    // occupancy query gives this kernel, so what it cannot keep resident is refused here and never waited for
     const int wg_per_tile = st->c1 == 256 ? 4 : 1;
-    const bool fits = d0.n <= 8 && st->tiles_per_img * wg_per_tile <= 32 &&
+    const int wg_per_cu = st->c1 == 64 ? saber_mi355x::conv_stage1_c64_blocks_per_cu() : 1;
+    const bool fits = d0.n <= 8 && st->tiles_per_img * wg_per_tile <= 32 * wg_per_cu &&
                       (st->c1 == 256 ? st->tiles_x == 1 : (st->tiles_x == 1 || st->tiles_x == 2 || st->tiles_x == 4));
-    if ((per_image && !fits) || (st->c1 == 128 && !per_image)) {
+    if ((per_image && !fits) || (st->c1 != 256 && !per_image)) {
         delete st;
-        return fail(SABER_HIP_INVALID_VALUE, "stage: an image per XCD needs batch <= 8 and <= 32 workgroups per image (C = 256: width <= 16, <= 8 tiles "
-                    "of 2 x 16 pixels; C = 128: width <= 64, <= 32 tiles)");
+        return fail(SABER_HIP_INVALID_VALUE, "stage: an image per XCD needs batch <= 8 and every workgroup of an image resident on its XCD's 32 CUs (C = 256: "
+                    "width <= 16, <= 8 tiles of 2 x 16 pixels; C = 128: width <= 64, <= 32 tiles; C = 64: width <= 64, <= 32 x the kernel's workgroups per CU)");
     }
     const size_t tiles = (size_t)d0.n * st->tiles_per_img;
     hipError_t e = hipSuccess;
@@ -388,7 +401,8 @@ static int stage_launch(saber_hip_chain_stage* st, const void* x, const void* re
     for (int i = 0; i < k.nblk; ++i) { k.y1[i] = y1[i]; k.y2[i] = y2[i]; }
     if (y_tail) k.y1[k.nblk] = y_tail;      // (the slot behind the last block's: stage_run has picked an argument block with room for it)
     k.head_y = y_head;                      // (with a head x is the pair's input and res is not read)
-    HIP_TRY(st->c1 == 256 ? saber_mi355x::launch_conv_stage4(k, y_tail != nullptr, y_head != nullptr, s) : saber_mi355x::launch_conv_stage1_c128(k, s));
+    HIP_TRY(st->c1 == 256 ? saber_mi355x::launch_conv_stage4(k, y_tail != nullptr, y_head != nullptr, s)
+                          : (st->c1 == 128 ? saber_mi355x::launch_conv_stage1_c128(k, s) : saber_mi355x::launch_conv_stage1_c64(k, s)));
     return SABER_HIP_OK;
 }
 int stage_run(saber_hip_chain_stage* st, const void* x, const void* res, void* const* y1, void* const* y2, hipStream_t s, void* y_tail, void* y_head) {
@@ -421,8 +435,9 @@ void saber_hip_conv2d_stage_destroy(saber_hip_chain_stage_t* st) { delete st; }
 int saber_hip_conv2d_stage_run(saber_hip_chain_stage_t* st, const void* x, const void* res, void* const* y1, void* const* y2, saber_hip_stream_t stream) {
     if (g_capture) return capture_unsupported("saber_hip_conv2d_stage_run (saber_hip_net_optimize forms stages itself)");
     if (!st || !x || !res || !y1 || !y2) return fail(SABER_HIP_INVALID_VALUE, "null argument");
+    // (C = 64: a null y1[i] of a block that is not the last leaves that tensor unwritten - its tile stays in LDS for block i + 1)
     for (size_t i = 0; i < st->chains.size(); ++i)
-        if (!y1[i] || !y2[i]) return fail(SABER_HIP_INVALID_VALUE, "stage: an output pointer per block");
+        if ((!y1[i] && !(st->c1 == 64 && i + 1 < st->chains.size())) || !y2[i]) return fail(SABER_HIP_INVALID_VALUE, "stage: an output pointer per block");
     return stage_run(st, x, res, y1, y2, (hipStream_t)stream);
 }
 int saber_hip_conv2d_stage_run_tail(saber_hip_chain_stage_t* st, const void* x, const void* res, void* const* y1, void* const* y2, void* y_tail,
@@ -553,9 +568,10 @@ static int chain_build(saber_hip_conv* c3, saber_hip_conv* a, saber_hip_conv* b,
         if (e == hipSuccess) e = hipHostMalloc((void**)&ch->h_coop_err, sizeof(unsigned), hipHostMallocMapped);
         if (e == hipSuccess) *ch->h_coop_err = 0u;
     }
-    if (e == hipSuccess && da.c == 128 && c3 && b && c3->d.stride_h == 1 && xcd_round_robin()) {
+    if (e == hipSuccess && (da.c == 128 || da.c == 64) && c3 && b && !pair2 && c3->d.stride_h == 1 && xcd_round_robin()) {
         std::vector<uint8_t> s1;
-        pack_stage1_c128_stream(c3, a, b, s1);
+        if (da.c == 128) pack_stage1_c128_stream(c3, a, b, s1);
+        else pack_stage1_c64_stream(c3->wq_oihw.data(), a->wq_oihw.data(), b->wq_oihw.data(), s1);
         e = ch->d_stream_stage1.upload(s1);
     }
     if (e == hipSuccess) e = ch->d_prm1.upload(p1);

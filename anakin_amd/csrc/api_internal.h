@@ -236,7 +236,7 @@ struct saber_hip_chain {
     DevBuf<uint8_t> d_prm0, d_prm1, d_prm2;
     // CS_COOP2: the pairs' arrival counters, the 3x3 conv's exchange tile, the halves' XCC ids, the pinned error word; CS_COOP4: all but the streams is in `stage1`
     DevBuf<uint8_t> d_coop_xch;
-    DevBuf<uint8_t> d_stream_stage1;  // C == 128, 3x3-led with a second 1x1 conv: per-wave streams of the one-workgroup-per-tile stage kernel
+    DevBuf<uint8_t> d_stream_stage1;  // C == 128 | 64, 3x3-led (stride 1) with a second 1x1 conv: per-wave streams of the one-workgroup-per-tile stage kernel
     DevBuf<unsigned long long> d_coop_ctr;
     DevBuf<unsigned> d_coop_xcc;
     unsigned* h_coop_err = nullptr;
@@ -456,6 +456,9 @@ struct NetOp {
     // then not written. Switching the stage on never sets it; switching the stage off clears it
     bool head_on = false;
     int head_of = -1;
+    // a block's 3x3 conv inside a C = 64 run, not the last block: the block's first output (chain3_y1) is read only by the next block of the
+    // run - its eltwise and its first 1x1 conv. While the stage launch is selected that tensor stays in LDS and is not written
+    bool stage_y1_private = false;
     // the fused stem conv + pooling with the sibling pair that reads the pooled tensor (flag 512): THIS op is the stem conv and always covers
     // the next op (the pair); stem_y1 / stem_y2 are the pair's outputs and this op's own output edge is not written
     saber_hip_stem_pair* stem_pair = nullptr;

@@ -22,7 +22,7 @@ int net_launch(saber_hip_net* net, const NetOp& o, hipStream_t s) {
             void* y2[saber_mi355x::STAGE4_LONG];
             const NetOp* ops = &o;            // (the ops of a net are contiguous: block k's 3x3 conv is ops[3 * k])
             for (int k = 0; k < o.stage_n; ++k) {
-                y1[k] = T(ops[3 * k].chain3_y1);
+                y1[k] = ops[3 * k].stage_y1_private ? nullptr : T(ops[3 * k].chain3_y1);      // (C = 64: an inner tensor only the launch reads stays in LDS)
                 y2[k] = T(ops[3 * k].chain3_y2);
             }
             // (with the head the launch starts from the pair's input - the pair is the op in front - and writes this op's input itself)
@@ -706,6 +706,8 @@ int saber_hip_net_tensor_unwritten(const saber_hip_net_t* net, int id) {
         if (o.out == id && o.kind == OP_CONV && (o.launch == LAUNCH_FIRE || (o.skip && by == LAUNCH_FIRE))) return 1;
         // the first block's shortcut while the pair that makes it runs as the stage launch's head: it stays in LDS
         if (o.launch == LAUNCH_STAGE && o.head_on && o.chain3_res == id) return 1;
+        // a C = 64 stage's inner block outputs that only the launch reads: they stay in LDS too
+        if (o.chain3 && o.stage_y1_private && o.chain3_y1 == id && (o.launch == LAUNCH_STAGE || (o.skip && by == LAUNCH_STAGE))) return 1;
     }
     return 0;
 }
@@ -743,15 +745,21 @@ int saber_hip_net_status(saber_hip_net_t* net) {
                 "timed out: another kernel held the CUs); its outputs are not valid - those sites now launch block by block: run the pass again");
 }
 // testing aid: makes the next saber_hip_net_status report a failed cooperative launch at the first stage that is selected or, where none
-// is, at the first site that has an error word
+// is, at the first site that has an error word. A res2 site (C = 64) is passed by, as it is by everything that walks "every stage": it takes
+// the error only where it is selected and no other stage is, or where the net has no other site
 int saber_hip_net_inject_coop_error(saber_hip_net_t* net) {
     if (!net) return fail(SABER_HIP_INVALID_VALUE, "null argument");
+    auto res2 = [](const NetOp& o) { return o.stage && o.stage->c1 == 64; };
     for (NetOp& o : net->ops)
-        if (o.stage && o.stage_on && o.stage->h_err) { *(volatile unsigned*)o.stage->h_err = 1u; return SABER_HIP_OK; }
+        if (o.stage && !res2(o) && o.stage_on && o.stage->h_err) { *(volatile unsigned*)o.stage->h_err = 1u; return SABER_HIP_OK; }
+    for (NetOp& o : net->ops)
+        if (res2(o) && o.stage_on && o.stage->h_err) { *(volatile unsigned*)o.stage->h_err = 1u; return SABER_HIP_OK; }
     for (NetOp& o : net->ops) {
-        if (o.stage && o.stage->h_err) { *(volatile unsigned*)o.stage->h_err = 1u; return SABER_HIP_OK; }
+        if (o.stage && !res2(o) && o.stage->h_err) { *(volatile unsigned*)o.stage->h_err = 1u; return SABER_HIP_OK; }
         if (o.chain3 && o.chain3->h_coop_err) { *(volatile unsigned*)o.chain3->h_coop_err = 1u; return SABER_HIP_OK; }
     }
+    for (NetOp& o : net->ops)
+        if (res2(o) && o.stage->h_err) { *(volatile unsigned*)o.stage->h_err = 1u; return SABER_HIP_OK; }
     return fail(SABER_HIP_INVALID_VALUE, "the net has no cooperative launch site");
 }
 int saber_hip_net_num_launches(const saber_hip_net_t* net) {

@@ -36,7 +36,10 @@ int saber_hip_net_get_choice(saber_hip_net_t* net, int index) {
 }
 int saber_hip_net_stage_blocks(const saber_hip_net_t* net, int index) {
     if (!net || index < 0 || index >= (int)net->ops.size()) return 0;
-    return net->ops[index].stage ? net->ops[index].stage_n : 0;
+    // (the res2 site, C = 64, reports its blocks NEGATIVE: callers that walk "every stage" - written before the site existed - pass it by, it has
+    // a selector of its own)
+    const NetOp& o = net->ops[index];
+    return o.stage ? (o.stage->c1 == 64 ? -o.stage_n : o.stage_n) : 0;
 }
 int saber_hip_net_stage_head(const saber_hip_net_t* net, int index) {
     if (!net || index < 1 || index >= (int)net->ops.size() || !net->ops[index].stage) return -1;
@@ -317,7 +320,8 @@ int saber_hip_net_autotune(saber_hip_net_t* net, saber_hip_stream_t stream, int 
             else if (ok_h && wh < one * 0.99f) one = wh;
             else net_set_head(net, first, false);
         }
-        if (!ok || one >= sep) {
+        // (the res2 stage, C = 64, is kept only where it wins by more than 1 %: what two cold medians of one form differ by)
+        if (!ok || one >= sep * (H0.stage->c1 == 64 ? 0.99f : 1.f)) {
             *(volatile unsigned*)H0.stage->h_err = 0u;
             net_set_stage(net, first, false);
             for (int k = 0; k < H0.stage_n; ++k) {

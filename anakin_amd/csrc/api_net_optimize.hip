@@ -610,7 +610,7 @@ int saber_hip_net_optimize(saber_hip_net_t* net, int flags) {
             if (Hd.led_on) removed += P ? 2 : 1;
         }
     }
-    // ---- 256: runs of 3x3-led C = 256 (or C = 128) chains whose blocks feed each other (ResNet's res4 / res3 stage) -> one persistent launch
+    // ---- 256: runs of 3x3-led C = 256 (or C = 128, or C = 64) chains whose blocks feed each other (ResNet's res4 / res3 stage) -> one persistent launch
     // NOT part of 255: the launch needs every workgroup of an image resident on its XCD at once - fine for one net on the GPU
     // (the latency path), not for several nets in flight on their own streams (two such launches can each hold half of the CUs
     // and wait for the other half: they time out, report an error and fall back; conv_stage_coop.hip)
@@ -618,7 +618,7 @@ int saber_hip_net_optimize(saber_hip_net_t* net, int flags) {
         for (size_t i = 0; i + 2 < ops.size();) {
             auto block_ok = [&](size_t j) {
                 return j + 2 < ops.size() && ops[j].chain3 && ops[j].chain3->b && !ops[j].stage && ops[j].chain3_y2 >= 0 &&
-                       ((ops[j].chain3->c1 == 256 && ops[j].chain3->stage1) || (ops[j].chain3->c1 == 128 && ops[j].chain3->d_stream_stage1.p));
+                       ((ops[j].chain3->c1 == 256 && ops[j].chain3->stage1) || ((ops[j].chain3->c1 == 128 || ops[j].chain3->c1 == 64) && ops[j].chain3->d_stream_stage1.p));
             };
             if (!block_ok(i)) { ++i; continue; }
             std::vector<saber_hip_chain*> run{ops[i].chain3};
@@ -662,8 +662,13 @@ int saber_hip_net_optimize(saber_hip_net_t* net, int flags) {
                     int before = 0;
                     for (size_t k = 0; k < run.size(); ++k) before += 3 - (ops[i + 3 * k].skip + ops[i + 3 * k + 1].skip + ops[i + 3 * k + 2].skip);
                     if (tail) before += 2 - (ops[jt].skip + ops[jt + 1].skip);
+                    // C = 64: a block's first output that only the next block of the run reads (its eltwise and its first 1x1 conv) is not
+                    // written while the one launch is selected - the tile stays in LDS
+                    if (run[0]->c1 == 64)
+                        for (size_t k = 0; k + 1 < run.size(); ++k) ops[i + 3 * k].stage_y1_private = readers(ops[i + 3 * k].chain3_y1) == 2;
                     // default until the autotuner has timed both forms: the res4 stage (C = 256) on from batch 4 (an image per XCD: fewer
-                    // images leave XCDs idle); the res3 stage (C = 128) off - measured slower than its chain launches
+                    // images leave XCDs idle); the res3 stage (C = 128) off - measured slower than its chain launches; the res2
+                    // stage (C = 64) off: it goes on through its choice word, the autotuner or a setter only
                     const bool on = run[0]->a->d.n >= 4 && run[0]->c1 == 256;
                     net_set_stage(net, (int)i, on);
                     if (on) removed += before - 1;

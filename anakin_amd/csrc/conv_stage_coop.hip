@@ -850,17 +850,311 @@ __global__ __launch_bounds__(512) void conv_stage1_c128_kernel(const Stage4KArgs
     SABER_TL_FLUSH();
 }
 
+// ------------------------------------------------------------------------------------------------------------------------------
+// ... and for the res2 stage (C = 64, 56 x 56): conv_stage1_c128_kernel's structure with FOUR waves - 9 + 4 + 4 fragments per wave, 22 016 bytes of LDS - and FOUR
+// workgroups per CU: an image is 28 tile rows x 4 column tiles = 112 workgroups on its XCD's 32 CUs, so the kernel is bound to 128 VGPRs
+// (conv_stage1_c64_kernel's launch bounds) and the host refuses the launch where the occupancy query says an image's workgroups cannot all
+// be resident (api_chain.hip: stage_build). An edge has 8 arriving workgroups (4 at the top and bottom). One workgroup's edge wait and halo
+// copy sit under the arithmetic of the three others on its CU. y1[k] may be null there: the y1 tile of a block whose only readers are the
+// next block's eltwise and 1x1 conv - both inside this launch, both served from LDS - is not stored.
+template <int MAXB>      // (256, 4): four workgroups = 16 waves per CU, at most 128 VGPRs
+__global__ __launch_bounds__(256, 4) void conv_stage1_c64_kernel(const Stage4KArgs<MAXB> ka) {
+    constexpr int C1 = 64, K1 = 4 * C1, K2 = C1, NW = C1 / 16, NT = NW * 64;      // a wave per 16 channels of the 3x3 conv
+    constexpr int KS = C1 / 64;                              // k-steps of 64 input channels per tap / of the first 1x1 conv: 1
+    constexpr int F0 = 9 * KS, F1 = 4 * KS, F2 = K1 / 64;    // 1 KB weight fragments per wave and phase: 9 + 4 + 4
+    constexpr int FS = F1 - 2;                               // ... of the first 1x1 conv that come with the block itself (two came a block ahead)
+    // (128 VGPRs: the last conv's fragments are requested behind the first 1x1 conv's MFMAs, under its eltwise epilogue, not at the block's start,
+    // and of the 3x3 conv's 9 + the first 1x1 conv's first 2 only the first PF are requested a block AHEAD, the others at the block's start:
+    // they are consumed in issue order and land under the first MFMAs - with all 11 in flight across the edge the kernel needed scratch)
+    constexpr int PF = 7;
+    constexpr int CH1 = C1 / 16, PCH = CH1 + 1, HW = 18, HP = 4 * HW;
+    constexpr int HCH = (HP * PCH + 63) / 64 * 64;
+    constexpr int CPRW = K1 / 16;                            // 16-byte chunks per row of the shortcut / output tile: 32
+    constexpr int P0C = (C1 / 4 * 3 + 63) / 64 * 64, P1C = K1 / 4 * 3, P2C = (K2 / 4 * 3 + 63) / 64 * 64;
+    constexpr int MPC = C1 / 16 + 1;                         // LDS pitch (chunks) of the 3x3 output tile: 8 + 1 padding
+    static_assert(P1C % 64 == 0 && (32 * CPRW) % NT == 0, "DMA granularity");
+    __shared__ v4i halo[HCH];
+    __shared__ v4i tile[32 * CPRW];
+    __shared__ v4i mid[32 * MPC];
+    __shared__ v4i prm0[P0C];
+    __shared__ v4i prm1[P1C];
+    __shared__ v4i prm2[P2C];
+    SABER_TL_DECL;
+    SABER_TL(0);
+    const int tid = threadIdx.x, lane = tid & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const int frow = lane & 15, fq = lane >> 4;
+    const int b = blockIdx.x;
+    const int slot = b >> 3;                                 // all workgroups of an image on one XCD: image (slot / tiles) * 8 + b % 8
+    const int il = ka.mg_tpi ? (int)__umulhi((unsigned)slot, ka.mg_tpi) : slot;
+    const int rem = slot - il * ka.tiles_per_img;
+    const int n = il * 8 + (b & 7);
+    if (n >= ka.N) return;
+    const int t = n * ka.tiles_per_img + rem;
+    const int ty = ka.mg_tiles_x ? (int)__umulhi((unsigned)rem, ka.mg_tiles_x) : rem;
+    const int x0 = (rem - ty * ka.tiles_x) * 16, y0 = ty * 2;
+    const int tile_rows = ka.tiles_per_img / ka.tiles_x;
+    const int H = ka.H, W = ka.W;
+    auto pix = [&](int m, bool& ok) -> int {                  // m = tile row * 16 + column
+        int x = x0 + (m & 15), y = y0 + (m >> 4);
+        ok = x < W && y < H;
+        x = x < W ? x : W - 1;
+        y = y < H ? y : H - 1;
+        return (n * H + y) * W + x;
+    };
+    unsigned long long* const e_up = ka.img_ctr + ((size_t)n * (ka.tiles_per_img + 1) + ty) * 16;   // the edge above this tile row; + 16: below
+
+    // (128 VGPRs) the per-lane index arithmetic that repeats every block - the halo copy, the y1 store, the operand and output addresses of
+    // the two 1x1 convs - starts from an opaque copy of the lane number, so it is redone per block instead of living in registers across
+    // the whole block loop
+    auto per_block = [](int v) -> int {
+        asm volatile("" : "+v"(v));
+        return v;
+    };
+    // ... and the block table is read through the constant address space: uniform reads of memory the kernel never writes -> scalar loads,
+    // each constant fetched where it is used (held by value, as vector loads, this block's and the next one's took 2 x 20 VGPRs)
+    typedef const __attribute__((address_space(4))) StageBlk* CBlk;
+    const CBlk cblk = (CBlk)ka.blk;
+    struct EltCoeff { float coeff_conv, scale_conv, coeff_res, scale_res; };      // (what chain_elt_pack reads of a block)
+    auto dma_halo = [&](const void* x, bool l2) {            // 4 rows x 18 columns x C channels, zero page for the padding
+        const char* xg = (const char*)x;
+        for (int i = wave; i < HCH / 64; i += NW) {
+            const int L = i * 64 + per_block(lane);
+            const int hp = L / PCH, cc = L - hp * PCH;
+            const int hy = hp / HW, hx = hp - hy * HW;
+            const int gy = y0 - 1 + hy, gx = x0 - 1 + hx;
+            const bool in = hp < HP && cc < CH1 && (unsigned)gy < (unsigned)H && (unsigned)gx < (unsigned)W;
+            const char* src = in ? xg + ((size_t)((n * H + gy) * W + gx) * C1 + cc * 16) : (const char*)ka.zero;
+            if (l2 && in) lds_dma16_l2(src, halo + i * 64);
+            else lds_dma16(src, halo + i * 64);
+        }
+    };
+    auto dma_prm = [&](int k) {
+        for (int i = wave; i < P0C / 64; i += NW) lds_dma16((const v4i*)cblk[k].prm0 + i * 64 + lane, prm0 + i * 64);
+        for (int i = wave; i < P1C / 64; i += NW) lds_dma16((const v4i*)cblk[k].prm1 + i * 64 + lane, prm1 + i * 64);
+        for (int i = wave; i < P2C / 64; i += NW) lds_dma16((const v4i*)cblk[k].prm2 + i * 64 + lane, prm2 + i * 64);
+    };
+    auto stream_of = [&](const void* wstream) -> const v4i* {   // this wave's fragments of a block, lane's 16 bytes
+        return (const v4i*)wstream + (size_t)wave * ((F0 + F1 + F2) * 64) + lane;
+    };
+
+    // ---- entry: the first block's halo, shortcut tile and constants by DMA; its first PF weight fragments ------------------------
+    dma_halo(ka.x, false);
+    for (int i = wave; i < 32 * CPRW / 64; i += NW) {
+        const int L = i * 64 + lane;
+        const int px = L / CPRW, c = (L % CPRW) ^ (px & 15);
+        bool okp;
+        const int pp_ = pix(px, okp);
+        lds_dma16((const char*)ka.res + (size_t)pp_ * K1 + c * 16, tile + i * 64);
+    }
+    dma_prm(0);
+    asm volatile("" ::: "memory");
+    v4i fr[F0 + 2];
+    {
+        const v4i* wsb = stream_of(cblk[0].wstream);
+#pragma unroll
+        for (int r = 0; r < PF; ++r) {
+            fr[r] = wsb[r * 64];
+            asm volatile("" ::: "memory");                   // issue order = consumption order
+        }
+    }
+    wait_vm_older_than<PF>();                             // everything older than the fragments: this wave's DMA
+    __builtin_amdgcn_s_barrier();
+    SABER_TL(1);
+    unsigned my_xcc;
+    asm volatile("s_getreg_b32 %0, hwreg(HW_REG_XCC_ID)" : "=s"(my_xcc));
+    my_xcc = (my_xcc & 7u) + 1u;
+    if (rem == 0 && tid == 0) ka.xcc[(size_t)t * 32 + 4] = my_xcc;      // the image's first tile publishes its XCD (+ 1: 0 = not yet)
+
+    for (int k = 0; k < ka.nblk; ++k) {
+        const v4i z = {0, 0, 0, 0};
+        const auto& B = cblk[k];
+        v4i fs[FS + F2];                                 // the rest of this block's stream: two land under the 3x3 conv
+        {
+            const v4i* wsb = stream_of(cblk[k].wstream);
+#pragma unroll
+            for (int r = PF; r < F0 + 2; ++r) {
+                fr[r] = wsb[r * 64];
+                asm volatile("" ::: "memory");
+            }
+#pragma unroll
+            for (int r = 0; r < FS; ++r) {
+                fs[r] = wsb[(F0 + 2 + r) * 64];
+                asm volatile("" ::: "memory");
+            }
+        }
+        // ================= phase 0: 3x3 conv, 16 mid channels per wave, both tile rows per fragment ==================================
+        {
+            const int xm0 = B.in0_u8 ? (int)0x80808080u : 0;
+            const int c0 = wave * 16 + fq * 4;
+            const v4i* pp = prm0 + (c0 / 4) * 3;
+            v4i acc0 = pp[2], acc1 = acc0;                   // starts at the compensation (exact integer sum)
+            const v4i* hb = halo + frow * PCH + fq;
+#pragma unroll
+            for (int s = 0; s < F0; ++s) {
+                const int kl = s % KS, tap = s / KS;
+                const int dy = tap / 3, dx = tap % 3;
+                v4i b0 = hb[(dy * HW + dx) * PCH + kl * 4];
+                v4i b1 = hb[((dy + 1) * HW + dx) * PCH + kl * 4];
+                b0.x ^= xm0; b0.y ^= xm0; b0.z ^= xm0; b0.w ^= xm0;
+                b1.x ^= xm0; b1.y ^= xm0; b1.z ^= xm0; b1.w ^= xm0;
+                acc0 = mma_step(fr[s], b0, acc0);
+                acc1 = mma_step(fr[s], b1, acc1);
+            }
+            const float lo0 = B.relu0 ? 0.f : -3.0e38f;
+            const float off0 = B.in_u8 ? 0.f : 128.f;
+            const unsigned xo0 = B.in_u8 ? 0u : 0x80808080u;
+            const unsigned o0 = chain_out_pack(acc0, z, __builtin_bit_cast(v4f, pp[1]), __builtin_bit_cast(v4f, pp[0]), lo0, off0, xo0);
+            const unsigned o1 = chain_out_pack(acc1, z, __builtin_bit_cast(v4f, pp[1]), __builtin_bit_cast(v4f, pp[0]), lo0, off0, xo0);
+            *(unsigned*)((char*)mid + frow * (MPC * 16) + c0) = o0;
+            *(unsigned*)((char*)mid + (16 + frow) * (MPC * 16) + c0) = o1;
+        }
+        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+        __builtin_amdgcn_s_barrier();                        // the 3x3 conv's tile is complete
+        SABER_TL(2);
+
+        // ================= phase 1: 1x1 conv + eltwise, 64 channels per wave ==========================================================
+        {
+            const int ln = per_block(lane), frow = ln & 15, fq = ln >> 4;
+            const int xmask = B.in_u8 ? (int)0x80808080u : 0;
+            const int cg = wave * 64 + fq * 16;              // 16 consecutive channels of pixel (row, frow)
+            const v4i* pp = prm1 + (cg / 4) * 3;
+            v4i acc[2][4];
+#pragma unroll
+            for (int m = 0; m < 2; ++m)
+#pragma unroll
+                for (int mf = 0; mf < 4; ++mf) acc[m][mf] = pp[mf * 3 + 2];
+#pragma unroll
+            for (int ks = 0; ks < KS; ++ks)
+#pragma unroll
+                for (int m = 0; m < 2; ++m) {
+                    v4i bo = mid[(m * 16 + frow) * MPC + ks * 4 + fq];
+                    bo.x ^= xmask; bo.y ^= xmask; bo.z ^= xmask; bo.w ^= xmask;
+#pragma unroll
+                    for (int mf = 0; mf < 4; ++mf) {
+                        const int f = ks * 4 + mf;           // fragments 0, 1 came with the previous block's prefetch
+                        acc[m][mf] = mma_step(f < 2 ? fr[F0 + f] : fs[f - 2], bo, acc[m][mf]);
+                    }
+                }
+            {
+                const v4i* wsb = stream_of(cblk[k].wstream);
+#pragma unroll
+                for (int r = FS; r < FS + F2; ++r) {
+                    fs[r] = wsb[(F0 + 2 + r) * 64];
+                    asm volatile("" ::: "memory");
+                }
+            }
+            const float lo_s8 = B.relu1 ? 0.f : -128.f;
+            const float res_lo = B.res_relu ? 0.f : -3.0e38f;
+            const EltCoeff ec = {B.coeff_conv, B.scale_conv, B.coeff_res, B.scale_res};
+#pragma unroll
+            for (int m = 0; m < 2; ++m) {
+                v4i* tp = tile + (m * 16 + frow) * CPRW + ((cg / 16) ^ frow);
+                const v4i rs = *tp;
+                v4i o;
+                o.x = (int)chain_elt_pack(acc[m][0], z, __builtin_bit_cast(v4f, pp[1]), __builtin_bit_cast(v4f, pp[0]), (unsigned)rs.x, lo_s8, res_lo, ec);
+                o.y = (int)chain_elt_pack(acc[m][1], z, __builtin_bit_cast(v4f, pp[4]), __builtin_bit_cast(v4f, pp[3]), (unsigned)rs.y, lo_s8, res_lo, ec);
+                o.z = (int)chain_elt_pack(acc[m][2], z, __builtin_bit_cast(v4f, pp[7]), __builtin_bit_cast(v4f, pp[6]), (unsigned)rs.z, lo_s8, res_lo, ec);
+                o.w = (int)chain_elt_pack(acc[m][3], z, __builtin_bit_cast(v4f, pp[10]), __builtin_bit_cast(v4f, pp[9]), (unsigned)rs.w, lo_s8, res_lo, ec);
+                *tp = o;
+            }
+        }
+        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+        __builtin_amdgcn_s_barrier();
+        // (a null y1[k] = a tensor no op outside the launch reads - the tile stays in LDS for block k + 1 and is not stored)
+        if (ka.y1[k]) {
+#pragma unroll
+        for (int j = 0; j < 32 * CPRW / NT; ++j) {           // the 32 x 4C tile -> y1, coalesced
+            const int L = per_block(tid) + j * NT;
+            const int px = L / CPRW, c = (L % CPRW) ^ (px & 15);
+            bool okp;
+            const int pp_ = pix(px, okp);
+            if (okp) *(v4i*)((char*)ka.y1[k] + (size_t)pp_ * K1 + c * 16) = tile[L];
+        }
+        }
+        SABER_TL(4);
+        if (k + 1 < ka.nblk) {         // the next block's first PF fragments: one block ahead
+            const v4i* wsb = stream_of(cblk[k + 1].wstream);
+#pragma unroll
+            for (int r = 0; r < PF; ++r) {
+                fr[r] = wsb[r * 64];
+                asm volatile("" ::: "memory");
+            }
+        }
+
+        // ================= phase 2: second 1x1 conv, 16 channels per wave, its operand is the y1 tile in LDS ===========================
+        {
+            const int ln = per_block(lane), frow = ln & 15, fq = ln >> 4;
+            bool ok0, ok1;
+            const int p0 = pix(frow, ok0), p1 = pix(16 + frow, ok1);
+            const int c2 = wave * 16 + fq * 4;
+            const v4i* pp = prm2 + (c2 / 4) * 3;
+            v4i acc0 = pp[2], acc1 = acc0;
+#pragma unroll
+            for (int ks = 0; ks < F2; ++ks) {
+                const int ch = (ks * 4 + fq) ^ frow;
+                acc0 = mma_step(fs[FS + ks], tile[frow * CPRW + ch], acc0);
+                acc1 = mma_step(fs[FS + ks], tile[(16 + frow) * CPRW + ch], acc1);
+            }
+            const float lo2 = B.relu2 ? 0.f : -3.0e38f;
+            const float off2 = B.out_u8_2 ? 0.f : 128.f;
+            const unsigned xm2 = B.out_u8_2 ? 0u : 0x80808080u;
+            const unsigned o0 = chain_out_pack(acc0, z, __builtin_bit_cast(v4f, pp[1]), __builtin_bit_cast(v4f, pp[0]), lo2, off2, xm2);
+            const unsigned o1 = chain_out_pack(acc1, z, __builtin_bit_cast(v4f, pp[1]), __builtin_bit_cast(v4f, pp[0]), lo2, off2, xm2);
+            if (ok0) *(unsigned*)((char*)ka.y2[k] + (size_t)p0 * K2 + c2) = o0;
+            if (ok1) *(unsigned*)((char*)ka.y2[k] + (size_t)p1 * K2 + c2) = o1;
+        }
+        SABER_TL(6);
+        if (k + 1 < ka.nblk) {
+            // ============= between two blocks: the edge barriers of conv_stage4_c256_kernel, tiles_x workgroups per tile row ================
+            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+            __builtin_amdgcn_s_barrier();                                // (every wave is also done with this block's constants)
+            unsigned long long* const e_k = e_up + (k & 1);              // (one word per block parity: see conv_stage4_c256_kernel)
+            if (wave == 0 && lane == 0) {
+                (void)__hip_atomic_fetch_add(e_k, 1ull, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+                (void)__hip_atomic_fetch_add(e_k + 16, 1ull, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+            }
+            dma_prm(k + 1);
+            if (wave == 0) {
+                const unsigned long long one = (unsigned long long)ka.tiles_x;     // arrivals at an edge: tiles_x per tile row
+                coop_wait_mask2(e_k, (ty > 0 ? 2 * one : one) - 1, e_k + 16, (ty + 1 < tile_rows ? 2 * one : one) - 1, ka.err);
+            }
+            __builtin_amdgcn_s_barrier();
+            dma_halo(ka.y2[k], true);
+            wait_vm_older_than<0>();
+            __builtin_amdgcn_s_barrier();
+            SABER_TL(7);
+        }
+    }
+    if (tid == 0 && ka.err) {      // this tile ran on its image's XCD? (0: the first tile has not published yet - nothing to compare)
+        const unsigned first = (unsigned)L2Reader(ka.xcc).load16((unsigned)(n * ka.tiles_per_img) * 128u + 16u).x;
+        if (first && first != my_xcc) __hip_atomic_fetch_add(ka.err, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+    }
+    SABER_TL_FLUSH();
+}
+
 template <int MAXB>
-static hipError_t launch_stage1(const Stage4KArgs<MAXB>& ka, hipStream_t s) {
+static hipError_t launch_stage1(const Stage4KArgs<MAXB>& ka, int c1, hipStream_t s) {
     if (ka.nblk <= 1 || ka.nblk > MAXB || ka.N <= 0 || !ka.blk || !ka.xcc || !ka.per_image || !ka.img_ctr ||
         (ka.tiles_x != 1 && ka.tiles_x != 2 && ka.tiles_x != 4))
         return hipErrorInvalidValue;
-    const dim3 grid((ka.N + 7) / 8 * ka.tiles_per_img * 8), block(512);
-    hipLaunchKernelGGL(conv_stage1_c128_kernel<MAXB>, grid, block, 0, s, ka);
+    const dim3 grid((ka.N + 7) / 8 * ka.tiles_per_img * 8);
+    if (c1 == 64) hipLaunchKernelGGL(conv_stage1_c64_kernel<MAXB>, grid, dim3(256), 0, s, ka);
+    else hipLaunchKernelGGL(conv_stage1_c128_kernel<MAXB>, grid, dim3(512), 0, s, ka);
     return hipGetLastError();
 }
-hipError_t launch_conv_stage1_c128(const Stage4KArgs<STAGE4_SHORT>& a, hipStream_t s) { return launch_stage1(a, s); }
-hipError_t launch_conv_stage1_c128(const Stage4KArgs<STAGE4_LONG>& a, hipStream_t s) { return launch_stage1(a, s); }
+hipError_t launch_conv_stage1_c128(const Stage4KArgs<STAGE4_SHORT>& a, hipStream_t s) { return launch_stage1(a, 128, s); }
+hipError_t launch_conv_stage1_c128(const Stage4KArgs<STAGE4_LONG>& a, hipStream_t s) { return launch_stage1(a, 128, s); }
+hipError_t launch_conv_stage1_c64(const Stage4KArgs<STAGE4_SHORT>& a, hipStream_t s) { return launch_stage1(a, 64, s); }
+hipError_t launch_conv_stage1_c64(const Stage4KArgs<STAGE4_LONG>& a, hipStream_t s) { return launch_stage1(a, 64, s); }
+// resident workgroups of the C = 64 stage kernel per CU (the residency rule of api_chain.hip: stage_build); 0 where the query fails
+int conv_stage1_c64_blocks_per_cu() {
+    int nb = 0;
+    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, conv_stage1_c64_kernel<STAGE4_SHORT>, 256, 0) != hipSuccess) return 0;
+    int nl = 0;
+    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&nl, conv_stage1_c64_kernel<STAGE4_LONG>, 256, 0) != hipSuccess) return 0;
+    return nb < nl ? nb : nl;
+}
 template <int MAXB>
 static hipError_t launch_stage4(const Stage4KArgs<MAXB>& ka, bool tail, bool head, hipStream_t s) {
     // tail: blk[nblk] holds the strided head's constants, y1[nblk] is its output (two blocks at least: an image per XCD, W <= 16)

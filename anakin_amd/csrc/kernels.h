@@ -214,6 +214,11 @@ hipError_t launch_conv_stage4(const Stage4KArgs<STAGE4_LONG>& a, bool tail, bool
 // the res3 stage (C = 128): one workgroup per tile, an image per XCD, nblk >= 2; grp_ctr / xch unused; tiles_x in {1, 2, 4}
 hipError_t launch_conv_stage1_c128(const Stage4KArgs<STAGE4_SHORT>& a, hipStream_t s);
 hipError_t launch_conv_stage1_c128(const Stage4KArgs<STAGE4_LONG>& a, hipStream_t s);
+// the res2 stage (C = 64): the same kernel body with four waves, FOUR workgroups per CU (an image's tiles_per_img workgroups must all be
+// resident on its XCD's 32 CUs: conv_stage1_c64_blocks_per_cu() * 32 >= tiles_per_img); a null y1[k] is not stored
+hipError_t launch_conv_stage1_c64(const Stage4KArgs<STAGE4_SHORT>& a, hipStream_t s);
+hipError_t launch_conv_stage1_c64(const Stage4KArgs<STAGE4_LONG>& a, hipStream_t s);
+int conv_stage1_c64_blocks_per_cu();
 
 // stage_xcd_kernel (stage_xcd.hip): a run of INT8 convolutions over small images as ONE persistent launch, one image per XCD
 // at a time, the phases separated by an XCD-local barrier instead of a kernel boundary.

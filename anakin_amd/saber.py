@@ -334,7 +334,7 @@ class SaberConvChain:
 
 
 class SaberChainStage:
-    """A run of 3x3-led C = 256 chains (SaberConvChain with conv3x3 and b) as ONE persistent launch (saber_hip_conv2d_stage_create):
+    """A run of 3x3-led C = 256 (or 128, or 64) chains (SaberConvChain with conv3x3 and b) as ONE persistent launch (saber_hip_conv2d_stage_create):
     chain i + 1 reads chain i's two outputs. dispatch(x, res, y1s, y2s): chain 0's inputs, every chain's two output tensors. The
     outputs hold the bits of dispatching the chains (= the operators, net.cpp:417-509) one after the other.
     tail: the strided head behind the run (SaberConvChain(a, None, conv3x3) with a stride-2 conv3x3 and a shortcut sub-sampled by 2;
@@ -359,7 +359,8 @@ class SaberChainStage:
 
     def dispatch(self, x, res, y1s, y2s, y_tail=None):
         n = len(self.chains)
-        a = (C.c_void_p * n)(*[t.data_ptr() for t in y1s])
+        # (C = 64: None for the first output of a block that is not the last = that tensor is not written, its tile stays in LDS)
+        a = (C.c_void_p * n)(*[t.data_ptr() if t is not None else None for t in y1s])
         b = (C.c_void_p * n)(*[t.data_ptr() for t in y2s])
         if y_tail is None:
             L.check(L.load().saber_hip_conv2d_stage_run(self.h, _p(x), _p(res), a, b, _stream()))
@@ -997,9 +998,28 @@ class Net:
         out = []
         for i in range(self.num_ops()):
             n = int(lib.saber_hip_net_stage_blocks(self.h, i))
-            if n:
+            if n > 0:
                 out.append((i, n, bool(int(lib.saber_hip_net_get_choice(self.h, i)) >> 30 & 1)))
         return out
+
+    def stages_c64(self):
+        """[(op index, blocks, selected)] of the res2 sites: runs of C = 64 blocks that can go as one persistent launch
+        (conv_stage1_c64_kernel). Formed by flag 256 like every stage but NOT part of stages() / select_stages(): the site is off until its
+        choice word (bit 30), the autotuner or select_stages_c64 asks for it."""
+        lib = L.load()
+        out = []
+        for i in range(self.num_ops()):
+            n = int(lib.saber_hip_net_stage_blocks(self.h, i))
+            if n < 0:
+                out.append((i, -n, bool(int(lib.saber_hip_net_get_choice(self.h, i)) >> 30 & 1)))
+        return out
+
+    def select_stages_c64(self, on):
+        """every res2 site (C = 64 stage) of the net on / off; while one is on, its inner blocks' first outputs are not written (unwritten())"""
+        ch = self.choices()
+        for i, _, _ in self.stages_c64():
+            ch[i] = (ch[i] | (1 << 30)) if on else (ch[i] & ~(1 << 30))
+        self.set_choices(ch)
 
     def select_stages(self, on):
         """every stage of the net on / off (what saber_hip_net_autotune decides per stage by timing)"""

@@ -243,7 +243,10 @@ int saber_hip_conv2d_chain_get_tile(const saber_hip_chain_t* chain);
  * fusion with no counterpart in the reference (framework/core/net/net.cpp:417-509 dispatches one operator at a time); results
  * bit-identical to the separate launches. Batch <= 8, <= 8 tiles per image (14 x 14). Also for runs of >= 2 chains at C = 128
  * (res3: one workgroup per tile, width <= 64, <= 32 tiles per image; measured slower than its chain launches on MI355X - an
- * autotune candidate). The chains are not owned and must outlive
+ * autotune candidate), and for runs of >= 2 chains at C = 64 (res2: one workgroup per tile, FOUR workgroups per CU, width <= 64; refused
+ * where the runtime's occupancy for that kernel x 32 CUs is below an image's tiles: every workgroup of an image must be resident on its
+ * XCD at once). At C = 64 y1[i] of a block that is not the last may be NULL: that tensor is then not written (its tile stays in LDS for
+ * block i + 1, its only reader inside the launch). The chains are not owned and must outlive
  * the stage. y1[i] / y2[i]: chain i's outputs (saber_hip_conv2d_chain_run's y_a / y_b); x / res: chain 0's inputs. */
 typedef struct saber_hip_chain_stage saber_hip_chain_stage_t;
 int saber_hip_conv2d_stage_create(saber_hip_chain_t* const* chains, int n, saber_hip_chain_stage_t** out);
@@ -630,7 +633,8 @@ int saber_hip_coop_fallbacks_total(void);
 int saber_hip_net_status(saber_hip_net_t* net);
 int saber_hip_net_inject_coop_error(saber_hip_net_t* net);
 /* > 0: op `index` heads a stage of that many blocks (flag 256); bit 30 of its saber_hip_net_get_choice / _set_choice value says
- * whether the stage launch is selected */
+ * whether the stage launch is selected. < 0: op `index` heads a C = 64 (res2) site of that many blocks, negated - the same choice bit, but
+ * off until the bit, the autotuner or a caller asks for it, and passed by when a caller switches "every stage" */
 int saber_hip_net_stage_blocks(const saber_hip_net_t* net, int index);
 /* the index of the sibling-pair op that can run as the HEAD of the stage headed by op `index` (always index - 1), or -1. Whether it does is
  * bit 29 of THAT op's choice word (saber_hip_net_get_choice / set_choice); a stage that is off has its head off. */

@@ -215,6 +215,55 @@ int main(int argc, char** argv) {
         }
         return 0;
     }
+    if (argc > 1 && !strcmp(argv[1], "c64")) {
+        // the res2 stage (conv_stage1_c64_kernel): two blocks at C = 64, 56 x 56, batch 8 and 1, one workgroup per tile of 2 x 16 pixels, four
+        // per CU, an image per XCD; with every y1 written and with the inner one left in LDS. Stamps (block 1's where both blocks pass one):
+        // 0 entry, 1 first halo + shortcut tile + constants + 7 fragments landed (first barrier), 2 3x3 tile done, 4 y1 tile done (and stored),
+        // 6 y2 stored, 7 (block 0 only) past the edge barrier + the next halo landed
+        auto magic = [](int d) { return d >= 2 ? (unsigned)((0x100000000ull + (unsigned)d - 1) / (unsigned)d) : 0u; };
+        for (int n : {8, 1}) {
+            const int c = 64, hw = 56, K1 = 256, M = n * hw * hw;
+            StageBlk hb[2];
+            for (auto& B : hb) {
+                memset(&B, 0, sizeof B);
+                B.wstream = dalloc((size_t)4 * 17 * 1024, -1);
+                B.prm0 = dalloc((size_t)c * 12 + 2048, 0); B.prm1 = dalloc((size_t)K1 * 12, 0); B.prm2 = dalloc((size_t)c * 12 + 2048, 0);
+                B.coeff_conv = 16.f; B.scale_conv = 0.05f; B.coeff_res = 16.f; B.scale_res = 0.04f;
+                B.in0_u8 = 1; B.relu0 = 1; B.in_u8 = 1; B.relu1 = 0; B.res_relu = 1; B.relu2 = 1; B.out_u8_2 = 1;
+            }
+            StageBlk* dblk;
+            CK(hipMalloc((void**)&dblk, sizeof hb));
+            CK(hipMemcpy(dblk, hb, sizeof hb, hipMemcpyHostToDevice));
+            Stage4KArgs<STAGE4_SHORT> sk;
+            memset(&sk, 0, sizeof sk);
+            sk.x = dalloc((size_t)M * c, -1); sk.res = dalloc((size_t)M * K1, -1); sk.zero = zero; sk.blk = dblk;
+            sk.tiles_x = (hw + 15) / 16; sk.tiles_per_img = sk.tiles_x * ((hw + 1) / 2);
+            const int tiles = n * sk.tiles_per_img;
+            sk.img_ctr = (unsigned long long*)dalloc((size_t)n * (sk.tiles_per_img + 1) * 16 * 8, 0);
+            sk.xcc = (unsigned*)dalloc((size_t)tiles * 32 * 4, 0);
+            sk.err = (unsigned*)dalloc(64, 0);
+            sk.N = n; sk.H = sk.W = hw; sk.nblk = 2; sk.per_image = 1;
+            sk.mg_tiles_x = magic(sk.tiles_x); sk.mg_tpi = magic(sk.tiles_per_img);
+            void* const y1_0 = dalloc((size_t)M * K1, 0);
+            sk.y1[0] = y1_0; sk.y1[1] = dalloc((size_t)M * K1, 0);
+            sk.y2[0] = dalloc((size_t)M * c, 0); sk.y2[1] = dalloc((size_t)M * c, 0);
+            const int blocks = (n + 7) / 8 * sk.tiles_per_img * 8;
+            if (conv_stage1_c64_blocks_per_cu() * 32 < sk.tiles_per_img || blocks > P.maxblocks) {
+                printf("stage1 C=64: %d workgroups per CU cannot hold an image's %d tiles\n", conv_stage1_c64_blocks_per_cu(), sk.tiles_per_img);
+                return 1;
+            }
+            char nm[96];
+            snprintf(nm, sizeof nm, "stage1 C=64 56x56 b%d 2 blocks, every y1 written", n);
+            run(P, nm, blocks, 8, [&] { launch_conv_stage1_c64(sk, P.st); });
+            sk.y1[0] = nullptr;
+            snprintf(nm, sizeof nm, "stage1 C=64 56x56 b%d 2 blocks, inner y1 in LDS", n);
+            run(P, nm, blocks, 8, [&] { launch_conv_stage1_c64(sk, P.st); });
+            unsigned errs = 0;
+            CK(hipMemcpy(&errs, sk.err, 4, hipMemcpyDeviceToHost));
+            printf("    coop error word: %u\n", errs);
+        }
+        return 0;
+    }
     if (argc > 1 && !strcmp(argv[1], "f32pw")) {
         // FP32 pointwise layers of ResNet50's res2 / res3 at batch 8 (2.4 TB/s where streaming reaches 4 - 6.5): the implicit-GEMM kernel on the
         // f32 MFMA (MODE 2) and on the bf16 planes (MODE 3), with and without the in-place sum. phases: 0 entry, 1 gather state set up, 2 first stage in LDS,
