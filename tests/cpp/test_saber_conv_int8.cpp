@@ -36,6 +36,9 @@ static int g_fail = 0, g_run = 0;
 
 static DataType ak(int code) { return code == 0 ? AK_FLOAT : (code == 1 ? AK_INT8 : AK_UINT8); }
 
+// the fused eltwise's coefficients as multiples of 1 / elt_scale: coeff[0] belongs to the conv's output, coeff[1] to the residual
+static float g_coeff_mult[2] = {1.f, 1.f};
+
 // one case: conv (+ optional fused eltwise with a residual tensor); every geometry parameter per axis (h, w)
 static void test_conv_int8_axes(int N, int C, int H, int W, int K, int kh, int kw, int pad_h, int pad_w, int stride_h, int stride_w,
                                 int dil_h, int dil_w, bool bias_term, bool relu, int in_dt /*1 s8, 2 u8*/,
@@ -49,6 +52,8 @@ static void test_conv_int8_axes(int N, int C, int H, int W, int K, int kh, int k
     for (auto& v : w) v = nd(rng);
     for (auto& v : b) v = nd(rng);
     const float in_scale = 0.021f, out_scale = 0.37f, res_scale = 0.043f, elt_scale = 0.06f;
+    const float coeff0 = g_coeff_mult[0] == 1.f ? 1.f / elt_scale : g_coeff_mult[0] * (1.f / elt_scale);
+    const float coeff1 = g_coeff_mult[1] == 1.f ? 1.f / elt_scale : g_coeff_mult[1] * (1.f / elt_scale);
 
     // ---- oracle ------------------------------------------------------------------------------
     std::vector<float> ws(K), bp(K), sc(K);
@@ -64,7 +69,25 @@ static void test_conv_int8_axes(int N, int C, int H, int W, int K, int kh, int k
         std::vector<int8_t> mid(on);
         orc_conv_i8(N, H, W, C, K, kh, kw, pad_h, pad_w, stride_h, stride_w, dil_h, dil_w, 1, in_dt, 1, relu, x.data(), wq.data(),
                     bias_term ? bp.data() : nullptr, sc.data(), nullptr, nullptr, mid.data());
-        orc_eltwise_i8(on, mid.data(), res.data(), out_scale, res_scale, 1.f / elt_scale, 1.f / elt_scale, 1, (int8_t*)want.data());
+        orc_eltwise_i8(on, mid.data(), res.data(), out_scale, res_scale, coeff0, coeff1, 1, (int8_t*)want.data());
+        if (coeff0 != coeff1) {   // the case tells the pair apart: swapped, or the conv's for both, changes at least a quarter of the bytes
+            std::vector<int8_t> other(on);
+            size_t inside = 0;
+            for (size_t i = 0; i < on; ++i) inside += (int8_t)want[i] > -128 && (int8_t)want[i] < 127;
+            if (10 * inside < on) {
+                ++g_fail;
+                printf("FAIL the unequal-coefficient case leaves %zu/%zu bytes between the rails\n", inside, on);
+            }
+            for (int v = 0; v < 2; ++v) {
+                orc_eltwise_i8(on, mid.data(), res.data(), out_scale, res_scale, v ? coeff0 : coeff1, coeff0, 1, other.data());
+                size_t d = 0;
+                for (size_t i = 0; i < on; ++i) d += other[i] != (int8_t)want[i];
+                if (4 * d < on) {
+                    ++g_fail;
+                    printf("FAIL the unequal-coefficient case does not separate %s: %zu/%zu bytes\n", v ? "the conv's coefficient for both" : "a swapped pair", d, on);
+                }
+            }
+        }
     } else {
         orc_conv_i8(N, H, W, C, K, kh, kw, pad_h, pad_w, stride_h, stride_w, dil_h, dil_w, 1, in_dt, out_dt, relu, x.data(), wq.data(),
                     bias_term ? bp.data() : nullptr, sc.data(), nullptr, nullptr, want.data());
@@ -87,7 +110,7 @@ static void test_conv_int8_axes(int N, int C, int H, int W, int K, int kh, int k
     SaberStatus st;
     const char* algo = "";
     if (fuse_eltwise) {
-        EltwiseParam<MI355X> ep(Eltwise_sum, {1.f / elt_scale, 1.f / elt_scale}, ActivationParam<MI355X>(Active_relu));
+        EltwiseParam<MI355X> ep(Eltwise_sum, {coeff0, coeff1}, ActivationParam<MI355X>(Active_relu));
         ConvEltwiseParam<MI355X> cep(cp, ep);
         ins.push_back(&tres);
         SaberConvEltwise<MI355X, AK_INT8> op;
@@ -211,6 +234,12 @@ int main() {
     test_conv_int8_axes(1, 64, 13, 9, 32, 7, 1, 3, 0, 1, 1, 1, 1, true, false, 1, 1, false, 4002, ctx);
     test_conv_int8_axes(2, 64, 12, 15, 48, 3, 3, 1, 1, 2, 1, 1, 1, true, true, 2, 0, false, 4003, ctx);
     test_conv_int8_axes(1, 16, 12, 15, 16, 3, 3, 2, 1, 1, 1, 2, 1, false, false, 1, 1, true, 4004, ctx);      // dilation (2, 1) + fused eltwise
+    // unequal coefficients through the adaptor (coeff[0] -> the conv, coeff[1] -> the residual): (c, -c / 2) and (c / 2, c)
+    g_coeff_mult[1] = -0.5f;
+    test_conv_int8_axes(1, 64, 9, 13, 64, 1, 1, 0, 0, 1, 1, 1, 1, true, false, 2, 1, true, 4005, ctx);
+    g_coeff_mult[0] = 0.5f, g_coeff_mult[1] = 1.f;
+    test_conv_int8_axes(1, 16, 12, 15, 16, 3, 3, 1, 1, 1, 1, 1, 1, true, false, 1, 1, true, 4006, ctx);
+    g_coeff_mult[0] = g_coeff_mult[1] = 1.f;
     test_conv_pooling(true, ctx);     // SaberConv2DPooling: fused stem + max pooling
     test_conv_pooling(false, ctx);    // SaberConv2DPooling: two launches behind the same interface
     printf("%d/%d cases bit-exact\n", g_run - g_fail, g_run);

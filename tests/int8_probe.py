@@ -22,6 +22,10 @@ reassociated bias, half-away rounding or a clamp at -127 pass the parity tests. 
                            the clean model and the oracle agree byte for byte and that every defect changes a byte of every probe family
                            it applies to. tests/test_gpu_int8_probe.py runs the kernels against the oracle on the same probes.
 
+  coefficient pairs        the fused eltwise takes two coefficients, t = c0*q*s0 + c1*r*s1. Beside the four sets with c0 == c1 three modes have
+                           c0 != c1 (uneq, neg, zero_res: COEFF_MODES) with products exact in float32; the defects coeff_swap,
+                           coeff_conv_for_both and coeff_sign_dropped each change bytes of every such probe they apply to.
+
 On one monotone chain relu, round and saturate commute (round(+-0) = 0, both roundings are monotone), so "relu after the round" and
 "saturate before the relu" are identities on a plain convolution and no test can or should separate them there. They are defects where
 the chain is not monotone - across the sum of the fused forms - and that is how they are modelled: `relu_across_sum` moves the
@@ -109,8 +113,9 @@ ORDER_DEFECTS = ("fma_bias_scaled", "mul_add", "fma_sum")               # fma(ac
 SAT_DEFECTS = ("wrap", "clamp_m127", "u8_no_lower_clamp")
 ELT_DEFECTS = ("elt_assoc", "elt_fma", "elt_premul", "elt_rne", "half_identity_05", "relu_across_sum")
 SUM_DEFECTS = ("sum_separate", "sat_before_sum")
+COEFF_DEFECTS = ("coeff_swap", "coeff_conv_for_both", "coeff_sign_dropped")   # (c1, c0) | (c0, c0) | (|c0|, |c1|) in the fused eltwise
 ACC24_DEFECTS = ("acc_cvt_trunc", "acc_cvt_half_up")                    # (float)acc truncating / rounding a tie away from zero
-DEFECTS = ROUND_DEFECTS + ORDER_DEFECTS + SAT_DEFECTS + ELT_DEFECTS + SUM_DEFECTS + ACC24_DEFECTS
+DEFECTS = ROUND_DEFECTS + ORDER_DEFECTS + SAT_DEFECTS + ELT_DEFECTS + SUM_DEFECTS + ACC24_DEFECTS + COEFF_DEFECTS
 
 
 def _conv_d(acc, bp, sc, defect=None):
@@ -145,6 +150,12 @@ def _round_conv(d, defect=None):
 
 def _elt_t(q, r, c0, c1, s0, s1, defect=None):
     q, r, c0, c1, s0, s1 = F(q) if np.isscalar(q) else q.astype(F), r.astype(F), F(c0), F(c1), F(s0), F(s1)
+    if defect == "coeff_swap":
+        c0, c1 = c1, c0
+    if defect == "coeff_conv_for_both":
+        c1 = c0
+    if defect == "coeff_sign_dropped":
+        c0, c1 = np.abs(c0), np.abs(c1)
     if defect == "elt_assoc":
         return c0 * (q * s0) + c1 * (r * s1)
     if defect == "elt_fma":
@@ -233,6 +244,10 @@ class Probe:
             return em == "below_half"
         if defect in ELT_DEFECTS:
             return em == "order"
+        if defect == "coeff_sign_dropped":
+            return em == "neg"
+        if defect in COEFF_DEFECTS:
+            return em in COEFF_MODES
         if defect == "sum_separate":
             return self.mode == "sum" and F(self.sum[1]) not in (F(1.0), F(2.0))
         if defect == "sat_before_sum":
@@ -267,6 +282,11 @@ class Probe:
             c["elt_rail_hi"], c["elt_rail_lo"] = t >= 127.5, t <= -128.5
             c["elt_q_saturates"] = (d >= 127.5) | (d <= -128.5)
             c["elt_below_half"] = np.abs(t) == float(HALF_LO)
+            c["elt_tie_even"], c["elt_tie_odd"] = (tf == 0.5) & (np.floor(np.abs(t)) % 2 == 0), (tf == 0.5) & (np.floor(np.abs(t)) % 2 == 1)
+            if self.meta.get("elt_mode") in COEFF_MODES:
+                for dn in COEFF_DEFECTS:
+                    c[dn] = self.designated(dn)
+                c["res_at_rail"] = (self.elt[0] == 127) | (self.elt[0] == -128)
             for dn in ("elt_assoc", "elt_fma", "elt_premul"):
                 c["order_" + dn] = self.designated(dn)
         if self.mode == "sum" and F(self.sum[1]) not in (F(1.0), F(2.0)):
@@ -309,7 +329,13 @@ def required_classes(p):
                         ["order_" + dn for dn in ORDER_DEFECTS],
                 "sum": ["elt_rail_hi", "elt_q_saturates"] + ([] if p.relu else ["elt_rail_lo"]),
                 "order": ["order_elt_assoc", "order_elt_fma", "order_elt_premul"],
-                "below_half": ["elt_below_half"]}[p.meta["elt_mode"]]
+                "below_half": ["elt_below_half"],
+                "uneq": ["elt_tie_pos", "elt_tie_neg", "elt_plus_half", "elt_minus_half", "elt_tie_even", "elt_tie_odd", "elt_rail_hi", "elt_rail_lo",
+                         "coeff_swap", "coeff_conv_for_both"],
+                "neg": ["elt_tie_pos", "elt_tie_neg", "elt_plus_half", "elt_minus_half", "elt_tie_even", "elt_tie_odd"] + list(COEFF_DEFECTS),
+                "zero_res": ["res_at_rail", "elt_q_saturates", "coeff_swap", "coeff_conv_for_both"]}[p.meta["elt_mode"]]
+        if p.elt[1]:           # a relu behind the sum: no negative byte leaves the launch
+            want = [w for w in want if w not in ("elt_tie_neg", "elt_minus_half", "elt_rail_lo")] if p.meta["elt_mode"] in COEFF_MODES else want
         return want
     want = ["tie_even_pos", "tie_odd_pos", "plus_half"]
     if p.mode == "conv":
@@ -564,7 +590,23 @@ def dw_probe(name, geo, idt, odt, relu, seed=0):
                  meta={"t": tvals, "order_channels": order, "depthwise": True, "acc24": "out of reach: nine taps"})
 
 
-ELT_MODES = ("half", "sum", "order", "below_half")
+COEFF_MODES = ("uneq", "neg", "zero_res")                 # c0 != c1: what a swapped, merged or sign-dropped coefficient pair changes
+ELT_MODES = ("half", "sum", "order", "below_half") + COEFF_MODES
+ELT_COEFFS = {"half": ((1.0, 1.0), 0.5, 0.5), "sum": ((2.0, 2.0), 0.5, 0.5), "order": ((float(F(1.0 / 0.06)),) * 2, 0.05, 0.043),
+              "below_half": ((1.0, 1.0), float(HALF_LO), float(HALF_LO)),
+              "uneq": ((1.0, 3.0), 0.5, 0.5), "neg": ((1.0, -1.0), 0.5, 0.5), "zero_res": ((2.0, 0.0), 0.5, 0.5)}      # mode -> ((c0, c1), s0, s1)
+# 2 t of the uneq mode, t = (q + 3 r) / 2: +-0.5, ties of both parities and signs, both rails from inside and outside, integers
+_UNEQ_2T = np.array([1, -1, 3, -3, 5, -5, 255, 257, -257, -259, 7, -7, 253, -255, 0, 2])
+
+
+def _uneq_residual(q, mix):
+    """r with q + 3 r = the first entry of _UNEQ_2T from position mix on that q reaches exactly (the table holds every residue mod 3)"""
+    tt = _UNEQ_2T[(mix[..., None] + np.arange(16)) % 16]                # [..., 16]: the table rotated to start at mix
+    num = tt - q[..., None]
+    ok = (num % 3 == 0) & (num // 3 >= -128) & (num // 3 <= 127)
+    first = ok.argmax(axis=-1)
+    r = np.take_along_axis(num, first[..., None], axis=-1)[..., 0] // 3
+    return np.where(ok.any(axis=-1), r, 0)
 
 
 def _elt_order_table(c0, c1, s0, s1):
@@ -580,11 +622,12 @@ def _elt_order_table(c0, c1, s0, s1):
 def elt_probe(name, geo, idt, relu, res_relu, elt_mode, seed=0):
     """conv (-> s8, scale 0.5: q's own rounding has ties) + fused eltwise; the residual bytes are chosen per output from q.
     half: c s0 = c s1 = 0.5, t = (q + r) / 2 - ties go half away;  sum: c s = 1, t = q + r in [-256, 254] - both rails;
-    order: the network's kind of coefficients (1 / 0.06, 0.05, 0.043), (q, r) found by search;  below_half: s = 0x1.fffffep-2, t = +-s."""
+    order: the network's kind of coefficients (1 / 0.06, 0.05, 0.043), (q, r) found by search;  below_half: s = 0x1.fffffep-2, t = +-s.
+    c0 != c1 (s0 = s1 = 0.5, every product exact):  uneq: (1, 3), t = (q + 3 r) / 2 - halves of both parities and signs, both rails;
+    neg: (1, -1), t = (q - r) / 2 - a dropped sign;  zero_res: (2, 0), t = q under residual bytes at the rails - the residual must not leak."""
     rng = np.random.default_rng(seed)
     s_i = float(U_SCALE if idt == U8 else 1.0)
-    s0, s1, c = {"half": (0.5, 0.5, 1.0), "sum": (0.5, 0.5, 2.0), "order": (0.05, 0.043, float(F(1.0 / 0.06))),
-                 "below_half": (float(HALF_LO), float(HALF_LO), 1.0)}[elt_mode]
+    (c, c1), s0, s1 = ELT_COEFFS[elt_mode]
     chans = [(s, float(F(0.5) * F(s0)), float(F(bp / 2.0) * (F(0.5) * F(s0)) * F(2.0))) for s, bp in _pow2_channels(S8)]
     order, extra = [], []
     if elt_mode == "half":          # out_scale = 0.5: w_scale / 2 and bias / 2 give the (bias', scale) the search saw, exactly
@@ -595,7 +638,7 @@ def elt_probe(name, geo, idt, relu, res_relu, elt_mode, seed=0):
     sig, ws, b = _channel_params(geo[4], chans)
     x, tv = _image(geo, idt, T_BASE + extra, rng)
     p = Probe(name, geo, idt, S8, relu, x, _weights(geo, sig), ws, b, s_i, s0, mode="elt",
-              elt=(None, bool(res_relu), (c, c), s1), meta={"elt_mode": elt_mode, "t": T_BASE + extra, "order_channels": order})
+              elt=(None, bool(res_relu), (c, c1), s1), meta={"elt_mode": elt_mode, "t": T_BASE + extra, "order_channels": order})
     d = p.d()
     q = np.clip(_rne(np.maximum(d, F(0)) if relu else d), -128, 127).astype(np.int64)
     N, oh, ow, K = q.shape
@@ -610,6 +653,13 @@ def elt_probe(name, geo, idt, relu, res_relu, elt_mode, seed=0):
         r = target - q
     elif elt_mode == "below_half":
         r = np.where(mix % 2 == 0, 1, -1) - q
+    elif elt_mode == "uneq":
+        r = _uneq_residual(q, mix + np.zeros_like(q))
+    elif elt_mode == "neg":                 # q - r = 2 t
+        r = q - np.array([1, -1, 3, -3, 5, -5, 253, 254, -255, -256, -257, 0, 2, 7, -7, 251])[mix]
+    elif elt_mode == "zero_res":            # any r but q itself (a swapped pair gives r), half of them on a rail
+        r = np.array([127, -128, 100, -100, 127, -128, 1, -1, 127, -128, 64, -64, 127, -128, 3, -3])[mix] + np.zeros_like(q)
+        r = np.where(r == q, -1 - q, r)
     else:
         tab = _elt_order_table(c, c, s0, s1)
         r = rng.integers(-128, 128, q.shape)
@@ -622,7 +672,7 @@ def elt_probe(name, geo, idt, relu, res_relu, elt_mode, seed=0):
                         if len(cand):
                             r[n_, y_, x_, k_] = cand[(y_ + x_ + k_) % len(cand)] - 128
     res = np.clip(r, -128, 127).astype(np.int8)
-    p.elt = (res, bool(res_relu), (c, c), s1)
+    p.elt = (res, bool(res_relu), (c, c1), s1)
     return p
 
 
@@ -778,6 +828,19 @@ SUM_COMBOS = [(i, o, rd, r, ss) for i, o, rd, r in ((U8, U8, S8, 1), (U8, S8, U8
 FUSED_GEOMETRIES = ("pw_k64", "pw_k72", "pw_k34", "c3x3", "img3x3", "imgres1x1", "imgres3x3")      # the 1x1 and 3x3 single-conv cases
 
 
+# the persistent stage launch (C, N, H, W): C = 64 on two column tiles with a ragged one, four / three tile rows with a ragged last row
+STAGE_PROBE_SHAPES = [(256, 2, 7, 9), (128, 1, 5, 13), (64, 2, 7, 9), (64, 1, 5, 24)]
+
+
+def stage_block_probes(shape):
+    """[(which conv of the block carries the probe, probe name, geometry)] of one stage shape: what tests/test_gpu_int8_probe.py's
+    test_chain_stage_probes_each_epilogue_of_its_first_block builds (a stage's 3x3 convs write u8)"""
+    C, N, H, W = shape
+    out = [(0, "conv/chain3/%su8/relu1" % DT_NAME[i], (N, H, W, C, C, 3, 1, 1)) for i in (U8, S8)]
+    out += [(1, "elt/chain3/u8/relu0_res%d/%s" % (rr, m), (N, H, W, C, 4 * C, 1, 0, 1)) for rr in (0, 1) for m in ELT_MODES]
+    return out + [(2, "conv/chain3b/s8u8/relu1", (N, H, W, 4 * C, C, 1, 0, 1))]
+
+
 GPOOL_NAMES = ["gpool/imgres1x1/%s%s/relu%d" % (DT_NAME[i], DT_NAME[o], r) for i in (S8, U8) for o, r in ((S8, 0), (S8, 1), (U8, 1))]
 
 
@@ -833,8 +896,7 @@ def build(name, geo=None):
 
 
 # ---- the streaming ops: eltwise, quantise, average pooling, fc ---------------------------------------------------------------------------
-ELT_SETS = {"half": (1.0, 0.5, 0.5), "sum": (2.0, 0.5, 0.5), "order": (float(F(1.0 / 0.06)), 0.05, 0.043),
-            "below_half": (1.0, float(HALF_LO), float(HALF_LO))}      # name -> (c0 = c1, s0, s1): elt_probe's coefficient sets
+ELT_SETS = dict(ELT_COEFFS)               # name -> ((c0, c1), s0, s1): elt_probe's coefficient sets
 
 
 def eltwise_grid():
@@ -843,7 +905,8 @@ def eltwise_grid():
 
 
 def eltwise_model(a, b, c, s0, s1, relu, defect=None):
-    t = _elt_t(a.astype(np.int64), b.astype(np.int64), c, c, s0, s1, defect)
+    """c: the pair (c0, c1)"""
+    t = _elt_t(a.astype(np.int64), b.astype(np.int64), c[0], c[1], s0, s1, defect)
     if relu:
         t = np.maximum(t, F(0))
     return _sat(_round_elt(t, defect), S8, defect)

@@ -35,9 +35,10 @@ def _quant(w):
 
 class Case:
     """One block: operands, the three ops' parameters, the oracle's two inner edges and result. variant = (idt, residual, project relu,
-    eltwise relu); zero_x: the input all zero bytes and the expand biases positive (the zero-padding case)."""
+    eltwise relu); zero_x: the input all zero bytes and the expand biases positive (the zero-padding case); pair: the project eltwise's
+    coefficients as multiples of c = 1 / y_scale (None: (c, c)) - .coeffs holds the pair, .coeff its first entry."""
 
-    def __init__(self, geo, variant, bias, seed, sat=False, zero_x=False):
+    def __init__(self, geo, variant, bias, seed, sat=False, zero_x=False, pair=None):
         cin, ce, cout, h, w, s, _, n = geo
         idt, res, p_relu, e_relu = variant
         assert not res or (idt == S8 and cin == cout and s == 1 and not p_relu)
@@ -68,23 +69,25 @@ class Case:
         self.p_scale, self.p = stage(self.d, self.d_scale, U8, self.w_p, self.b_p, self.odt, p_relu)
         self.y, self.y_scale = self.p, self.p_scale
         if res:
-            f = np.float32(self.p_scale) * self.p.astype(np.float32) + np.float32(IN_SCALE) * self.x.astype(np.float32)
+            m0, m1 = (1.0, 1.0) if pair is None else pair
+            f = np.float32(m0) * np.float32(self.p_scale) * self.p.astype(np.float32) + np.float32(m1) * np.float32(IN_SCALE) * self.x.astype(np.float32)
             self.y_scale = max(float(np.abs(np.maximum(f, 0) if e_relu else f).max()), 1e-6) / 127.0 / div
             c = np.float32(1.0 / self.y_scale)
-            self.coeff = float(c)
-            self.y = O.eltwise_i8(self.p, self.x, self.p_scale, IN_SCALE, c, c, bool(e_relu))
+            self.coeffs = (float(np.float32(m0) * c), float(np.float32(m1) * c))
+            self.coeff = self.coeffs[0]
+            self.y = O.eltwise_i8(self.p, self.x, self.p_scale, IN_SCALE, self.coeffs[0], self.coeffs[1], bool(e_relu))
 
 
-def case(name, vi=None, sat=False, zero_x=False):
+def case(name, vi=None, sat=False, zero_x=False, pair=None):
     """geometry `name` with variant vi (None: the geometry's own residual flag, s8 input, no relus); cached"""
     geo = GEOMETRIES[name]
     variant = (S8, geo[6], 0, 0) if vi is None else VARIANTS[vi]
-    key = (name, variant, sat, zero_x)
+    key = (name, variant, sat, zero_x, pair)
     if key not in _cache:
         gi = sorted(GEOMETRIES).index(name)
         bi = (gi + (0 if vi is None else vi + 1)) % len(BIASES)
         _cache[key] = Case(geo, variant, BIASES[bi], 30270 + 16 * gi + (0 if vi is None else vi + 1) + (1000 if sat else 0) + (2000 if zero_x else 0),
-                           sat, zero_x)
+                           sat, zero_x, pair)
     return _cache[key]
 
 

@@ -35,27 +35,35 @@ def gpool_case(H, W, N, cout, epi):
     return wq, ws, b, xs, rs
 
 
-def gpool_oracle(wq, ws, b, x, res, epi):
-    """(y, y_pool) of the oracle: conv (+ eltwise), then the INT8 pooling op's global average of those bytes"""
+def gpool_coeff(pair):
+    """the eltwise's coefficient pair: `pair` as multiples of c = 1 / S_OUT (None: the network's (c, c))"""
+    c = 1.0 / S_OUT
+    return (c, c) if pair is None else (float(np.float32(pair[0] * c)), float(np.float32(pair[1] * c)))
+
+
+def gpool_oracle(wq, ws, b, x, res, epi, pair=None, detail=None):
+    """(y, y_pool) of the oracle: conv (+ eltwise), then the INT8 pooling op's global average of those bytes;
+    detail: a dict that receives the conv's own bytes (the eltwise's first operand)"""
     from oracle import oracle as O
     name, elt, res_relu, relu, odt = epi
     od = O.U8 if odt == "u8" else O.S8
     bp, sc = O.conv_i8_prepare(ws, b, S_IN, S_OUT, O.U8, od)
     y = O.conv_i8(x, wq, bp, sc, od, int(relu))
     if elt:
-        c = 1.0 / S_OUT
-        y = O.eltwise_i8(y, res, S_OUT, S_RES, c, c, res_relu)
+        c = gpool_coeff(pair)
+        if detail is not None:
+            detail["t1"] = y
+        y = O.eltwise_i8(y, res, S_OUT, S_RES, c[0], c[1], res_relu)
     return y, O.pool_i8_nhwc(y, None, None, None, 1, global_pool=True)
 
 
-def gpool_op(N, H, W, cout, wq, ws, b, epi):
+def gpool_op(N, H, W, cout, wq, ws, b, epi, pair=None):
     from anakin_amd import lib as L
     from anakin_amd import saber as S
     name, elt, res_relu, relu, odt = epi
     p = S.ConvParam(wq, b, 1, (0, 0), (1, 1), (1, 1), bool(relu), ws)
     if elt:
-        c = 1.0 / S_OUT
-        p.res_mode, p.res_relu, p.sum_scale, p.coeff, p.scale_res = L.RES_ELTWISE, bool(res_relu), 1.0, (c, c), S_RES
+        p.res_mode, p.res_relu, p.sum_scale, p.coeff, p.scale_res = L.RES_ELTWISE, bool(res_relu), 1.0, gpool_coeff(pair), S_RES
     conv = S.SaberConv2D(int8=True).init((N, CIN, H, W), p, L.U8, L.U8 if odt == "u8" else L.S8, S_IN, S_OUT)
     conv.set_global_pooling()
     return conv

@@ -655,22 +655,27 @@ def _stage_tensors(ops, tail_op=None):
     return outs
 
 
-@pytest.mark.parametrize("shape", [(256, 2, 7, 9, 2), (128, 1, 5, 13, 2)])
+@pytest.mark.parametrize("shape", [(256, 2, 7, 9, 2), (128, 1, 5, 13, 2), (64, 2, 7, 9, 3)])
 def test_chain_stage(shape):
-    """a run of 3x3-led chains as one persistent launch (conv_stage_coop.hip): the same object for every run - its counters run on"""
+    """a run of 3x3-led chains as one persistent launch (conv_stage_coop.hip): the same object for every run - its counters run on.
+    C = 64 (conv_stage1_c64_kernel; three blocks whose hand-over dtype alternates) also in the form with the inner blocks' y1 pointers
+    null: the inner tensors stay guarded tensors the launch is not given, and come back sentinel throughout"""
     Cc, N, H, W, nblk = shape
     rng = np.random.default_rng(4100 + N + H + nblk + Cc)
     x, res, ops, wants = TP._res4_blocks(rng, N, H, W, nblk, Cc=Cc)
     chains = [S.SaberConvChain(ca, cb, conv3x3=c0) for c0, ca, cb in ops]
     stage = S.SaberChainStage(chains)
     outs = _stage_tensors(ops)
-
-    def launch(T, ws):
-        stage.dispatch(T["x"], T["res"], [T["y1_%d" % k] for k in range(nblk)], [T["y2_%d" % k] for k in range(nblk)])
-    name = "stage_c%d" % Cc
-    got = guard_launch("stage", name, {"x": x, "res": res}, outs, launch)
-    print("chain stage %s: %s" % (shape, name))
-    _check_outputs(got, {"y%d_%d" % (j + 1, k): wants[k][j] for k in range(nblk) for j in (0, 1)}, name)
+    for skip in ((), range(nblk - 1)) if Cc == 64 else ((),):
+        def launch(T, ws):
+            stage.dispatch(T["x"], T["res"], [None if k in skip else T["y1_%d" % k] for k in range(nblk)], [T["y2_%d" % k] for k in range(nblk)])
+        name = "stage_c%d" % Cc + ("_inner_y1_null" if skip else "")
+        got = guard_launch("stage", name, {"x": x, "res": res}, outs, launch)
+        print("chain stage %s: %s" % (shape, name))
+        for k in skip:
+            y = got.pop("y1_%d" % k).view(np.uint8)
+            assert (y == GU.SENTINEL).all(), "%s: the y1 of block %d the launch was not given was written: %d bytes" % (name, k, int((y != GU.SENTINEL).sum()))
+        _check_outputs(got, {n: wants[int(n[3:])][int(n[1]) - 1] for n in got}, name)
 
 
 @pytest.mark.parametrize("case", TT.TAIL_CASES[:2])
@@ -1231,6 +1236,7 @@ def test_guarded_launches_reached_every_form_family():
             print("%s (%d): %s" % (fam, len(names), " ".join(sorted(names))))
     assert all(want.values()), sorted(k for k, v in want.items() if not v)
     # the 3x3-led chain runs its cooperative forms where the device places them, and both chain kinds more than one form
+    assert {"stage_c256", "stage_c128", "stage_c64", "stage_c64_inner_y1_null"} <= reached["stage"], sorted(reached["stage"])
     assert len(reached["chain1x1"]) >= 8 and len(reached["chain3x3"]) >= 12, (sorted(reached["chain1x1"]), sorted(reached["chain3x3"]))
     stream = {"pooling_i8", "pooling_f32_nchw", "pooling_f32_nhwc", "eltwise_sum_i8", "eltwise_sum_f32", "quantize_nchw_to_nhwc",
               "dequantize_nhwc_to_nchw", "transpose_nchw_to_nhwc", "transpose_nhwc_to_nchw", "quantize_flat_s8", "softmax", "gemm_f32"}

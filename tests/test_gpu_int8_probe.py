@@ -114,6 +114,10 @@ def test_conv_i8_probes_every_accepted_form(group):
         P.assert_classes(p)
         runs += run_forms(p, seen)
     assert seen and runs, group
+    if group.startswith("elt/"):                # three (relu, res_relu) settings x every coefficient set, the three with c0 != c1 among them
+        n_new = sum(name.rsplit("/", 1)[1] in P.COEFF_MODES for name in GROUPS[group])
+        assert len(GROUPS[group]) == 3 * len(P.ELT_MODES) and n_new == 9, (group, len(GROUPS[group]), n_new)
+        print("%s: %d elt probes, %d of them with c0 != c1" % (group, len(GROUPS[group]), n_new))
     if group.startswith(("elt/", "sum/")):      # the forms of the plain conv on this geometry that this mode does not have
         plain = {a for _, a in _forms(make_conv(P.build("conv/%s/u8u8/relu1" % group.split("/")[1])))}
         key = "/".join(group.split("/")[:2])
@@ -184,15 +188,16 @@ def _random_conv(rng, shape_in, K, idt, odt, relu, in_scale, out_scale):
 
 @pytest.mark.parametrize("case", CHAIN_CASES)
 def test_conv1x1_chain_first_epilogue_probes(case):
-    """[1x1 conv + fused eltwise] -> 1x1 conv in one launch (chain_elt_pack): the first epilogue through y1 with all four coefficient
-    sets, s8 and u8 input; the second conv reads y1, so its output is checked against the oracle too."""
+    """[1x1 conv + fused eltwise] -> 1x1 conv in one launch (chain_elt_pack): the first epilogue through y1 with every coefficient
+    set (three of them with c0 != c1), s8 and u8 input; the second conv reads y1, so its output is checked against the oracle too."""
     Cc, HW, tn = case
     geo = (1, HW, HW, Cc, 4 * Cc, 1, 0, 1)
     rng = np.random.default_rng(Cc + HW)
-    runs = 0
+    runs, n_new = 0, 0
     for idt, relu, res_relu, mode in P.ELT_COMBOS:
         if relu:
             continue                                   # (the chain's first conv has no relu of its own)
+        n_new += mode in P.COEFF_MODES
         p = P.build("elt/chain/%s/relu%d_res%d/%s" % (P.DT_NAME[idt], relu, res_relu, mode), geo)
         P.assert_classes(p)
         want1 = P.oracle_bytes(p)
@@ -212,8 +217,8 @@ def test_conv1x1_chain_first_epilogue_probes(case):
         check(p, host(z1), want1, "chain y1, tile %s" % chain.tile())
         check(None, host(z2), want2, "chain y2, tile %s" % chain.tile())
         runs += 1
-    assert runs
-    print("chain C=%d %dx%d tile %s: %d probes" % (Cc, HW, HW, tn, runs))
+    assert runs == 4 * len(P.ELT_MODES) and n_new == 12, (runs, n_new)
+    print("chain C=%d %dx%d tile %s: %d elt probes, %d of them with c0 != c1" % (Cc, HW, HW, tn, runs, n_new))
 
 
 @pytest.mark.parametrize("case", CHAIN_CASES)
@@ -343,15 +348,17 @@ _BLOCK_PROBES = [(0, "conv/chain3/%s/relu%d", (P.U8, P.U8)), (0, "conv/chain3/%s
 @pytest.mark.parametrize("case", CHAIN3_CASES)
 def test_conv3x3_chain_probes_each_of_its_three_epilogues(case):
     """3x3 conv -> [1x1 conv + eltwise] -> 1x1 conv in one launch (conv1x1_chain.hip, conv_chain_coop.hip), with and without the last conv:
-    the 3x3's internal requantisation through a pass-through 1x1, the fused eltwise with all four coefficient sets, the last epilogue with
+    the 3x3's internal requantisation through a pass-through 1x1, the fused eltwise with every coefficient set, the last epilogue with
     the first 1x1 zeroed. The cooperative forms (tile codes 7, 15) run three launches: their arrival counters are never reset."""
     Cc, H, Wd, tn = case
     rng = np.random.default_rng(Cc + H)
-    runs = 0
+    runs, n_elt, n_new = 0, 0, 0
     for which, name, (idt, mdt) in _BLOCK_PROBES:
         for odt2, relu2 in ((P.U8, 1), (P.S8, 0)):
             if which != 2 and odt2 == P.S8:
                 continue
+            n_elt += which == 1
+            n_new += which == 1 and name.rsplit("/", 1)[1] in P.COEFF_MODES
             b = _Block(which, name, 1, H, Wd, Cc, idt, mdt, odt2, relu2, rng)
             chain = S.SaberConvChain(b.ca, b.cb, conv3x3=b.c0)
             if tn is not None:
@@ -372,19 +379,23 @@ def test_conv3x3_chain_probes_each_of_its_three_epilogues(case):
                 double.dispatch(xd, rd, z1)
                 b.check(host(z1), b.want2, "3x3 + 1x1 only, tile %s" % double.tile())
             runs += 1
-    print("chain3 C=%d %dx%d tile %s: %d probes" % (Cc, H, Wd, tn, runs))
+    assert n_elt == 4 * len(P.ELT_MODES) and n_new == 12, (n_elt, n_new)
+    print("chain3 C=%d %dx%d tile %s: %d probes, %d elt probes, %d of them with c0 != c1" % (Cc, H, Wd, tn, runs, n_elt, n_new))
 
 
-@pytest.mark.parametrize("shape", [(256, 2, 7, 9), (128, 1, 5, 13)])
+@pytest.mark.parametrize("shape", P.STAGE_PROBE_SHAPES)
 def test_chain_stage_probes_each_epilogue_of_its_first_block(shape):
-    """Two blocks in one persistent launch (conv_stage_coop.hip): block 1 carries the probe in one of its three convs, block 2 reads block
+    """Two blocks in one persistent launch (conv_stage_coop.hip; C = 256, 128 and 64 - conv_stage1_c64_kernel on two column tiles with a
+    ragged one, four and three tile rows with a ragged last one, two images): block 1 carries the probe in one of its three convs, block 2 reads block
     1's two outputs through pass-through convs, so its outputs show the bytes that crossed the edge barrier. Three launches each."""
     Cc, N, H, Wd = shape
     rng = np.random.default_rng(Cc + N)
-    runs = 0
+    runs, n_elt, n_new = 0, 0, 0
     for which, name, (idt, mdt) in _BLOCK_PROBES:
         if mdt != P.U8:
             continue                                   # (a stage's 3x3 convs write u8, as the network's do)
+        n_elt += which == 1
+        n_new += which == 1 and name.rsplit("/", 1)[1] in P.COEFF_MODES
         b1 = _Block(which, name, N, H, Wd, Cc, idt, mdt, P.U8, 1, rng)
         # block 2: 3x3 pass-through of block 1's y2 (u8), 1x1 pass-through - 128 + eltwise adding block 1's y1, an ordinary last conv
         K1 = 4 * Cc
@@ -407,20 +418,20 @@ def test_chain_stage_probes_each_epilogue_of_its_first_block(shape):
             check(None, host(y1[1]), want1, "stage block 2 y1 (block 1's outputs passed through), launch %d, probe %s" % (rep, b1.p.name))
             check(None, host(y2[1]), want2, "stage block 2 y2, launch %d, probe %s" % (rep, b1.p.name))
         runs += 1
-    assert runs
-    print("stage C=%d N=%d %dx%d: %d probes x 3 launches" % (Cc, N, H, Wd, runs))
+    assert runs == len(P.stage_block_probes(shape)) and n_elt == 2 * len(P.ELT_MODES) and n_new == 6, (runs, n_elt, n_new)
+    print("stage C=%d N=%d %dx%d: %d probes x 3 launches, %d elt probes, %d of them with c0 != c1" % (Cc, N, H, Wd, runs, n_elt, n_new))
 
 
 # ---- the streaming ops -------------------------------------------------------------------------------------------------------------------
 @pytest.mark.parametrize("mode", sorted(P.ELT_SETS))
 def test_eltwise_sum_s8_every_pair_of_bytes(mode):
     """SaberEltwise<AK_INT8> sum on ALL 65536 (a, b) pairs per coefficient set, relu on and off: ties go half away, both rails, the
-    association (c * a) * s, t = +-0x1.fffffep-2 (the roundf identity's edge)."""
+    association (c * a) * s, t = +-0x1.fffffep-2 (the roundf identity's edge), and three sets with c0 != c1."""
     c, s0, s1 = P.ELT_SETS[mode]
     a, b = P.eltwise_grid()
     for relu in (False, True):
-        want = O.eltwise_i8(a, b, s0, s1, c, c, relu)
-        got = host(S.eltwise_sum(dev(a), dev(b), (c, c), relu, s0, s1))
+        want = O.eltwise_i8(a, b, s0, s1, c[0], c[1], relu)
+        got = host(S.eltwise_sum(dev(a), dev(b), c, relu, s0, s1))
         if not np.array_equal(got, want):
             i = tuple(int(v) for v in np.argwhere(got != want)[0])
             raise AssertionError("eltwise %s relu %d: %d bytes differ, first a %d b %d: got %d, oracle %d" %
@@ -584,7 +595,7 @@ def test_image_resident_conv_with_fused_global_pooling_probes():
 # ---- the strided-head chain, depthwise -------------------------------------------------------------------------------------------------
 def test_strided_head_chain_probes():
     """3x3 / stride 2 -> [1x1 + eltwise on the sub-sampled shortcut] in one launch (C = 64, 9x7 -> 5x4): the 3x3's requantisation through
-    a pass-through 1x1, then the fused eltwise (all four coefficient sets) behind a pass-through 3x3."""
+    a pass-through 1x1, then the fused eltwise (every coefficient set) behind a pass-through 3x3."""
     N, H, Wd, Cc, K1 = 1, 9, 7, 64, 256
     Ho, Wo = 5, 4
     runs = 0
@@ -633,7 +644,8 @@ def test_strided_head_chain_probes():
             chain.dispatch(dev(x), dev(res), z1)
             check(p, host(z1), P.oracle_bytes(p), "strided head, eltwise")
             runs += 1
-    print("strided head: %d probes" % runs)
+    assert runs == 1 + 2 * len(P.ELT_MODES)
+    print("strided head: %d probes, %d elt probes, %d of them with c0 != c1" % (runs, runs - 1, 2 * len(P.COEFF_MODES)))
 
 
 @pytest.mark.parametrize("group", sorted(g for g in GROUPS if g.startswith("dw/")))

@@ -48,21 +48,22 @@ def forms_of(ir):
 
 
 def make_block(n, cin, ce, cout, h, w, stride, idt, odt, p_relu, we, be, wse, wd, bd, wsd, wp, bp, wsp, scales, elt=None):
-    """scales = (in, expand, dw, project); elt = (coeff, scale_res, relu) for a project conv with the fused eltwise"""
+    """scales = (in, expand, dw, project); elt = (coeff, scale_res, relu) for a project conv with the fused eltwise (coeff: one
+    coefficient for both operands, or the pair)"""
     s_in, s_e, s_d, s_p = scales
     ex = S.SaberConv2D(True).init((n, cin, h, w), S.ConvParam(we, be, 1, (0, 0), (1, 1), (1, 1), True, wse), idt, L.U8, s_in, s_e, **NHWC)
     dw = S.SaberConv2D(True).init((n, ce, h, w), S.ConvParam(wd, bd, ce, (1, 1), (stride, stride), (1, 1), True, wsd), L.U8, L.U8, s_e, s_d, **NHWC)
     oh, ow = dw.out_hw
     prm = S.ConvParam(wp, bp, 1, (0, 0), (1, 1), (1, 1), bool(p_relu), wsp)
     if elt is not None:
-        prm.res_mode, prm.coeff, prm.scale_res, prm.res_relu = L.RES_ELTWISE, (elt[0], elt[0]), elt[1], bool(elt[2])
+        prm.res_mode, prm.coeff, prm.scale_res, prm.res_relu = L.RES_ELTWISE, (tuple(elt[0]) if isinstance(elt[0], (tuple, list)) else (elt[0], elt[0])), elt[1], bool(elt[2])
     pr = S.SaberConv2D(True).init((n, ce, oh, ow), prm, L.U8, odt, s_d, s_p, **NHWC)
     return ex, dw, pr
 
 
 def block_of(cs):
     cin, ce, cout, h, w, s, _, n = cs.geo
-    elt = (cs.coeff, IU.IN_SCALE, cs.e_relu) if cs.res else None
+    elt = (cs.coeffs, IU.IN_SCALE, cs.e_relu) if cs.res else None
     return make_block(n, cin, ce, cout, h, w, s, cs.idt, cs.odt, cs.p_relu, cs.w_e, cs.b_e, None, cs.w_d, cs.b_d, None, cs.w_p, cs.b_p, None,
                       (IU.IN_SCALE, cs.e_scale, cs.d_scale, cs.p_scale), elt)
 

@@ -1702,8 +1702,32 @@ def test_softmax_vs_oracle():
     assert np.abs(got - want).max() <= FP32_RTOL * want.max() and np.allclose(got.sum(1), 1.0, atol=1e-5)
 
 
-@pytest.mark.parametrize("geo", [(2, 56, 64, 256, 2), (3, 28, 128, 512, 2), (8, 14, 256, 1024, 2), (2, 15, 64, 128, 2), (1, 30, 32, 64, 3)])
+def _coeff_pair(c, pair):
+    """the eltwise's coefficients: `pair` as multiples of c (None: the network's (c, c), c as it is)"""
+    return (c, c) if pair is None else (float(np.float32(pair[0] * c)), float(np.float32(pair[1] * c)))
+
+
+def _coeff_conditions(t1, r, s0, s1, cc, relu, what):
+    """tests/block_table.py: from the oracle alone, a swapped pair and the conv's coefficient for both each change a quarter of the bytes"""
+    from tests import block_table as BT
+    print("%s: (swapped, conv's for both, between the rails) = %s" % (what, BT.coeff_conditions(t1, r, s0, s1, cc[0], cc[1], relu, what)))
+
+
+SUBSAMPLED_GEOS = [(2, 56, 64, 256, 2), (3, 28, 128, 512, 2), (8, 14, 256, 1024, 2), (2, 15, 64, 128, 2), (1, 30, 32, 64, 3)]
+
+
+@pytest.mark.parametrize("geo", SUBSAMPLED_GEOS)
 def test_conv_i8_fused_eltwise_with_subsampled_residual(geo):
+    _subsampled_residual(geo)
+
+
+@pytest.mark.parametrize("pair", [(1.0, -0.5), (0.5, 1.0)])
+def test_conv_i8_fused_eltwise_with_subsampled_residual_unequal_coefficients(pair):
+    """the smallest geometry above (15 x 15 x 64 -> 128 under a 29 x 29 shortcut) with (c, -c / 2) and (c / 2, c)"""
+    _subsampled_residual(SUBSAMPLED_GEOS[3], pair)
+
+
+def _subsampled_residual(geo, pair=None):
     """saber_hip_conv_desc::res_stride: the 1x1 / stride-s shortcut pooling of the reference's stride-up pass folded into
     the fused eltwise epilogue's residual read == max-pooling the shortcut first (oracle: pool_i8 floor mode, then
     conv(->s8) + SaberEltwise), every implicit-GEMM variant the op offers."""
@@ -1715,15 +1739,17 @@ def test_conv_i8_fused_eltwise_with_subsampled_residual(geo):
     w = (rng.standard_normal((k, c, 1, 1)) * 0.05).astype(np.float32)
     b = (rng.standard_normal(k) * 0.2).astype(np.float32)
     in_scale, conv_scale, res_scale, out_scale = 0.02, 0.11, 0.09, 0.13
-    coeff = 1.0 / out_scale
+    cc = _coeff_pair(1.0 / out_scale, pair)
     pooled = O.pool_i8_nhwc(res_full, (1, 1), (s, s), (0, 0), 0, floor_mode=True)
     assert pooled.shape == (n, ho, ho, k)
     ws = O.weight_scales(w)
     bp, sc = O.conv_i8_prepare(ws, b, in_scale, conv_scale, O.U8, O.S8)
     y = O.conv_i8(x, O.quant_weights(w, ws), bp, sc, O.S8, 0, (0, 0))
-    want = O.eltwise_i8(y, pooled, conv_scale, res_scale, coeff, coeff, True)
+    want = O.eltwise_i8(y, pooled, conv_scale, res_scale, cc[0], cc[1], True)
+    if pair is not None:
+        _coeff_conditions(y, pooled, conv_scale, res_scale, cc, True, "sub-sampled residual %s" % (pair,))
     p = S.ConvParam(w, b, 1, (0, 0), (1, 1), (1, 1), False)
-    p.res_mode, p.res_relu, p.coeff, p.scale_res = L.RES_ELTWISE, True, (coeff, coeff), res_scale
+    p.res_mode, p.res_relu, p.coeff, p.scale_res = L.RES_ELTWISE, True, cc, res_scale
     p.res_stride, p.res_hw = s, (hs, hs)
     conv = S.SaberConv2D(True).init((n, c, ho, ho), p, L.U8, L.S8, in_scale, conv_scale)
     variants = [None] + [tile | (ks << 8) | (var << 16) for var, ks, tiles in
@@ -1740,9 +1766,9 @@ def test_conv_i8_fused_eltwise_with_subsampled_residual(geo):
     ws2 = O.weight_scales(w2)
     bp2, sc2 = O.conv_i8_prepare(ws2, b2, in_scale, conv_scale, O.U8, O.S8)
     want2 = O.eltwise_i8(O.conv_i8(x, O.quant_weights(w2, ws2), bp2, sc2, O.S8, 0, (0, 0)), np.ascontiguousarray(pooled[..., :k2]),
-                         conv_scale, res_scale, coeff, coeff, True)
+                         conv_scale, res_scale, cc[0], cc[1], True)
     p2 = S.ConvParam(w2, b2, 1, (0, 0), (1, 1), (1, 1), False)
-    p2.res_mode, p2.res_relu, p2.coeff, p2.scale_res = L.RES_ELTWISE, True, (coeff, coeff), res_scale
+    p2.res_mode, p2.res_relu, p2.coeff, p2.scale_res = L.RES_ELTWISE, True, cc, res_scale
     p2.res_stride, p2.res_hw = s, (hs, hs)
     conv2 = S.SaberConv2D(True).init((n, c, ho, ho), p2, L.U8, L.S8, in_scale, conv_scale)
     out2 = conv2.new_output()
@@ -2164,9 +2190,22 @@ STRIDED_HEAD_CASES = [
 ]
 
 
-@pytest.mark.parametrize("case", [(2, 56, 56, O.U8, O.U8, 1, 512, None), (1, 27, 41, O.U8, O.U8, 1, 512, 2), (2, 30, 22, O.S8, O.S8, 0, 128, 4),
-                                  (1, 56, 56, O.U8, O.U8, 1, 608, 2)])
+HEAD_PAIR_CASES = [(2, 56, 56, O.U8, O.U8, 1, 512, None), (1, 27, 41, O.U8, O.U8, 1, 512, 2), (2, 30, 22, O.S8, O.S8, 0, 128, 4),
+                   (1, 56, 56, O.U8, O.U8, 1, 608, 2)]
+
+
+@pytest.mark.parametrize("case", HEAD_PAIR_CASES)
 def test_strided_head_chain_runs_the_next_stages_sibling_pair(case):
+    _strided_head_pair(case)
+
+
+@pytest.mark.parametrize("pair", [(1.0, -0.5), (0.5, 1.0)])
+def test_strided_head_chain_with_sibling_pair_unequal_coefficients(pair):
+    """the smallest case above (27 x 41, ragged) with (c, -c / 2) and (c / 2, c) on the head's eltwise"""
+    _strided_head_pair(HEAD_PAIR_CASES[1], pair)
+
+
+def _strided_head_pair(case, pair=None):
     """saber_hip_conv2d_chain_create3_pair: res2c as the reference's stride-up leaves it (3x3 / stride 2, 1x1 + eltwise on the sub-sampled
     shortcut, C = 64) AND the two 1x1 convs that read its output (res3a_branch1 / res3a_branch2a) in ONE launch: all three written tensors
     are the bits of the four operators one after the other (ragged tiles, both pixel-tile heights, either split of the 640 channels)."""
@@ -2182,7 +2221,7 @@ def test_strided_head_chain_runs_the_next_stages_sibling_pair(case):
     w1 = (rng.standard_normal((K1, Cc, 1, 1)) * np.sqrt(2.0 / Cc)).astype(np.float32)
     b1 = (rng.standard_normal(K1) * 0.5).astype(np.float32)
     s_x, s_in, s_mid, s_res, s_sum = 0.023, 0.02, 0.05, 0.043, 0.06
-    c = 1.0 / s_sum
+    cc = _coeff_pair(1.0 / s_sum, pair)
     relu0 = mdt == O.U8
     ws0 = O.weight_scales(w0)
     bp0, sc0 = O.conv_i8_prepare(ws0, b0, s_x, s_in, idt, mdt)
@@ -2190,10 +2229,13 @@ def test_strided_head_chain_runs_the_next_stages_sibling_pair(case):
     ws1 = O.weight_scales(w1)
     bp1, sc1 = O.conv_i8_prepare(ws1, b1, s_in, s_mid, mdt, O.S8)
     t1 = O.conv_i8(t0, O.quant_weights(w1, ws1), bp1, sc1, O.S8, 0)
-    y1_want = O.eltwise_i8(t1, O.pool_i8_nhwc(res_full, (1, 1), (2, 2), (0, 0), 0, floor_mode=True), s_mid, s_res, c, c, bool(res_relu))
+    pooled = O.pool_i8_nhwc(res_full, (1, 1), (2, 2), (0, 0), 0, floor_mode=True)
+    y1_want = O.eltwise_i8(t1, pooled, s_mid, s_res, cc[0], cc[1], bool(res_relu))
+    if pair is not None:
+        _coeff_conditions(t1, pooled, s_mid, s_res, cc, bool(res_relu), "strided head + pair %s" % (pair,))
     c0 = S.SaberConv2D(int8=True).init((N, Cc, H, Wd), S.ConvParam(w0, b0, 1, (1, 1), (2, 2), (1, 1), bool(relu0)), idt, mdt, s_x, s_in)
     pa = S.ConvParam(w1, b1, 1, (0, 0), (1, 1), (1, 1), False)
-    pa.res_mode, pa.res_relu, pa.sum_scale, pa.coeff, pa.scale_res = L.RES_ELTWISE, bool(res_relu), 1.0, (c, c), s_res
+    pa.res_mode, pa.res_relu, pa.sum_scale, pa.coeff, pa.scale_res = L.RES_ELTWISE, bool(res_relu), 1.0, cc, s_res
     pa.res_stride, pa.res_hw = 2, (Hs, Ws)
     ca = S.SaberConv2D(int8=True).init((N, Cc, Ho, Wo), pa, mdt, O.S8, s_in, s_mid)
     pair, wants = [], []
@@ -2221,6 +2263,16 @@ def test_strided_head_chain_runs_the_next_stages_sibling_pair(case):
 
 @pytest.mark.parametrize("case", STRIDED_HEAD_CASES)
 def test_strided_conv3x3_conv1x1_chain_with_subsampled_shortcut(case):
+    _strided_head(case)
+
+
+@pytest.mark.parametrize("pair", [(1.0, -0.5), (0.5, 1.0)])
+def test_strided_conv3x3_conv1x1_chain_unequal_coefficients(pair):
+    """the smallest case above (C = 256, 9 x 7, u8 -> s8) with (c, -c / 2) and (c / 2, c) on the head's eltwise"""
+    _strided_head(STRIDED_HEAD_CASES[-1], pair)
+
+
+def _strided_head(case, pair=None):
     """The last block of a stage as the reference's stride-up leaves it: 3x3 / stride 2 (C -> C), then 1x1 (C -> 4C) + eltwise
     whose shortcut is the previous block's output sub-sampled by 2 (the absorbed 1x1 / stride-2 pooling, res_stride) — ONE
     launch (saber_hip_conv2d_chain_create3 with a stride-2 head and no second 1x1 conv), the bits of pooling + the two convs."""
@@ -2239,6 +2291,7 @@ def test_strided_conv3x3_conv1x1_chain_with_subsampled_shortcut(case):
     b1 = (rng.standard_normal(K1) * 0.5).astype(np.float32)
     s_x, s_in, s_mid, s_res, s_sum = 0.023, 0.02, 0.05, 0.043, 0.06
     c = 1.0 / s_sum
+    cc = _coeff_pair(c, pair)
     relu0 = mdt == O.U8
     ws0 = O.weight_scales(w0)
     bp0, sc0 = O.conv_i8_prepare(ws0, b0, s_x, s_in, idt, mdt)
@@ -2248,11 +2301,13 @@ def test_strided_conv3x3_conv1x1_chain_with_subsampled_shortcut(case):
     bp1, sc1 = O.conv_i8_prepare(ws1, b1, s_in, s_mid, mdt, O.S8)
     t1 = O.conv_i8(t0, O.quant_weights(w1, ws1), bp1, sc1, O.S8, 0)
     pooled = O.pool_i8_nhwc(res_full, (1, 1), (2, 2), (0, 0), 0, floor_mode=True)
-    want = O.eltwise_i8(t1, pooled, s_mid, s_res, c, c, bool(res_relu))
+    want = O.eltwise_i8(t1, pooled, s_mid, s_res, cc[0], cc[1], bool(res_relu))
+    if pair is not None:
+        _coeff_conditions(t1, pooled, s_mid, s_res, cc, bool(res_relu), "strided head %s" % (pair,))
     c0 = S.SaberConv2D(int8=True).init((N, Cc, H, Wd), S.ConvParam(w0, b0, 1, (1, 1), (2, 2), (1, 1), bool(relu0)), idt, mdt,
                                        s_x, s_in)
     pa = S.ConvParam(w1, b1, 1, (0, 0), (1, 1), (1, 1), False)
-    pa.res_mode, pa.res_relu, pa.sum_scale, pa.coeff, pa.scale_res = L.RES_ELTWISE, bool(res_relu), 1.0, (c, c), s_res
+    pa.res_mode, pa.res_relu, pa.sum_scale, pa.coeff, pa.scale_res = L.RES_ELTWISE, bool(res_relu), 1.0, cc, s_res
     pa.res_stride, pa.res_hw = 2, (Hs, Ws)
     ca = S.SaberConv2D(int8=True).init((N, Cc, Ho, Wo), pa, mdt, O.S8, s_in, s_mid)
     y0, y1 = c0.new_output(), ca.new_output()
@@ -2660,6 +2715,9 @@ def test_layout_quant_softmax_gemm_random_shapes_vs_oracle(seed):
     assert ran == 3 * 7 + 3 + 3
 
 
+RANDOM_FUSED_PAIRS = [None, (1.0, -0.5), (0.5, 1.0)]
+
+
 @pytest.mark.parametrize("seed", range(16))
 def test_conv_i8_fused_eltwise_random_geometry_every_accepted_selection(seed):
     """The executor's fused epilogue (conv -> s8, + residual x its scale, coefficients, optional relu, requantise: RES_ELTWISE) on random
@@ -2682,9 +2740,13 @@ def test_conv_i8_fused_eltwise_random_geometry_every_accepted_selection(seed):
     bp, sc = O.conv_i8_prepare(ws, b, in_scale, out_scale, idt, O.S8)
     y1 = O.conv_i8(x, wq, bp, sc, O.S8, 0, (pad, pad), (stride, stride), (dil, dil))
     res = rng.integers(-128, 128, y1.shape).astype(np.int8)
-    want = O.eltwise_i8(y1, res, out_scale, s_res, c, c, relu)
+    pair = RANDOM_FUSED_PAIRS[seed % 3]         # per seed: the network's (c, c), (c, -c / 2), (c / 2, c)
+    cc = _coeff_pair(c, pair)
+    want = O.eltwise_i8(y1, res, out_scale, s_res, cc[0], cc[1], relu)
+    if pair is not None:
+        _coeff_conditions(y1, res, out_scale, s_res, cc, relu, "random geometry, seed %d %s" % (seed, pair))
     p = S.ConvParam(w, b, 1, (pad, pad), (stride, stride), (dil, dil), False, None)
-    p.res_mode, p.res_relu, p.sum_scale, p.coeff, p.scale_res = L.RES_ELTWISE, relu, 1.0, (c, c), s_res
+    p.res_mode, p.res_relu, p.sum_scale, p.coeff, p.scale_res = L.RES_ELTWISE, relu, 1.0, cc, s_res
     conv = S.SaberConv2D(int8=True).init((N, C, H, Wd), p, idt, O.S8, in_scale, out_scale)
     xin, rd = dev(x), dev(res)
 

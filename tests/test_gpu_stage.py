@@ -28,26 +28,34 @@ def host(t):
     return t.cpu().numpy()
 
 
-def conv(rng, N, H, W, cin, cout, k, relu, idt, odt, s_in, s_out, elt=None):
+def conv(rng, N, H, W, cin, cout, k, relu, idt, odt, s_in, s_out, elt=None, pair=None, keep=None):
+    """pair: the eltwise's coefficients as multiples of c = 1 / s_sum (None: (c, c)); keep: a dict that receives what an oracle walk
+    needs (weights, bias, coefficients) under the op's id"""
     w = (rng.standard_normal((cout, cin, k, k)) * np.sqrt(2.0 / (k * k * cin))).astype(np.float32)
     b = (rng.standard_normal(cout) * 0.5).astype(np.float32)
     p = S.ConvParam(w, b, 1, (k // 2, k // 2), (1, 1), (1, 1), bool(relu))
     if elt is not None:
         s_res, s_sum = elt
         c = 1.0 / s_sum
-        p.res_mode, p.res_relu, p.sum_scale, p.coeff, p.scale_res = L.RES_ELTWISE, True, 1.0, (c, c), s_res
-    return S.SaberConv2D(int8=True).init((N, cin, H, W), p, idt, odt, s_in, s_out)
+        cc = (c, c) if pair is None else (float(np.float32(pair[0] * c)), float(np.float32(pair[1] * c)))
+        p.res_mode, p.res_relu, p.sum_scale, p.coeff, p.scale_res = L.RES_ELTWISE, True, 1.0, cc, s_res
+    op = S.SaberConv2D(int8=True).init((N, cin, H, W), p, idt, odt, s_in, s_out)
+    if keep is not None:
+        keep[id(op)] = dict(w=w, b=b, k=k, relu=int(bool(relu)), idt=idt, odt=odt, s_in=s_in, s_out=s_out, s_res=elt[0] if elt else None,
+                            coeff=p.coeff if elt else None)
+    return op
 
 
-def res5(rng, N, H=7, W=7, blocks=3):
-    """[(conv, in, out, res)] of res5a (projection shortcut) + identity blocks, tensor slot 0 = the stage's input"""
+def res5(rng, N, H=7, W=7, blocks=3, pairs=None, keep=None):
+    """[(conv, in, out, res)] of res5a (projection shortcut) + identity blocks, tensor slot 0 = the stage's input;
+    pairs: block b's eltwise coefficients pairs[b % len(pairs)] (conv's pair / keep parameters)"""
     ph, t = [], 1
     s = {0: 0.05}
 
-    def add(cin, cout, k, relu, src, odt, s_out, res=None):
+    def add(cin, cout, k, relu, src, odt, s_out, res=None, pair=None):
         nonlocal t
         idt = O.U8 if src in u8 else O.S8
-        c = conv(rng, N, H, W, cin, cout, k, relu, idt, odt, s[src], s_out, None if res is None else (s[res], s_out))
+        c = conv(rng, N, H, W, cin, cout, k, relu, idt, odt, s[src], s_out, None if res is None else (s[res], s_out), pair, keep)
         ph.append((c, src, t, -1 if res is None else res))
         s[t] = s_out
         if odt == O.U8:
@@ -60,7 +68,7 @@ def res5(rng, N, H=7, W=7, blocks=3):
     for b in range(blocks):
         a = add(1024 if b == 0 else 2048, 512, 1, True, x, O.U8, 0.03)
         m = add(512, 512, 3, True, a, O.U8, 0.025)
-        x = add(512, 2048, 1, False, m, O.S8, 0.06 + 0.01 * b, res=short)
+        x = add(512, 2048, 1, False, m, O.S8, 0.06 + 0.01 * b, res=short, pair=None if pairs is None else pairs[b % len(pairs)])
         short = x
     return ph, t
 

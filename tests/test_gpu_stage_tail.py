@@ -73,9 +73,10 @@ def _res4_blocks(rng, N, H, Wd, nblk, first_u8=True, Cc=256):
     return x, res, ops, wants
 
 
-def _head(rng, N, H, Wd, idt, mdt, res_relu, Cc=256, stride=2, res_stride=2, x_in=None, res_in=None, res_hw=None):
+def _head(rng, N, H, Wd, idt, mdt, res_relu, Cc=256, stride=2, res_stride=2, x_in=None, res_in=None, res_hw=None, coeff=(1.0, 1.0), detail=None):
     """the strided head behind a run of blocks: conv 3x3 / stride `stride` / pad 1 (C -> C, reads dtype idt, writes mdt) and conv 1x1 (C -> 4C)
-    + eltwise on the shortcut [N][H][Wd][4C] sub-sampled by res_stride. Returns the two device ops and - given the oracle's inputs - its output."""
+    + eltwise on the shortcut [N][H][Wd][4C] sub-sampled by res_stride. Returns the two device ops and - given the oracle's inputs - its output.
+    coeff: the eltwise's pair as multiples of 1 / s_sum; detail: a dict that receives the eltwise's operands, scales and coefficients."""
     K1 = 4 * Cc
     Ho, Wo = (H + 2 - 3) // stride + 1, (Wd + 2 - 3) // stride + 1
     w0 = (rng.standard_normal((Cc, Cc, 3, 3)) * np.sqrt(2.0 / (9 * Cc))).astype(np.float32)
@@ -84,10 +85,11 @@ def _head(rng, N, H, Wd, idt, mdt, res_relu, Cc=256, stride=2, res_stride=2, x_i
     b1 = (rng.standard_normal(K1) * 0.5).astype(np.float32)
     s_x, s_in, s_mid, s_res, s_sum = 0.031, 0.02, 0.05, 0.06, 0.07
     c = 1.0 / s_sum
+    cc = (float(np.float32(coeff[0] * c)), float(np.float32(coeff[1] * c))) if tuple(coeff) != (1.0, 1.0) else (c, c)
     relu0 = mdt == O.U8
     c0 = S.SaberConv2D(int8=True).init((N, Cc, H, Wd), S.ConvParam(w0, b0, 1, (1, 1), (stride, stride), (1, 1), bool(relu0)), idt, mdt, s_x, s_in)
     pa = S.ConvParam(w1, b1, 1, (0, 0), (1, 1), (1, 1), False)
-    pa.res_mode, pa.res_relu, pa.sum_scale, pa.coeff, pa.scale_res = L.RES_ELTWISE, bool(res_relu), 1.0, (c, c), s_res
+    pa.res_mode, pa.res_relu, pa.sum_scale, pa.coeff, pa.scale_res = L.RES_ELTWISE, bool(res_relu), 1.0, cc, s_res
     if res_stride > 1:
         pa.res_stride, pa.res_hw = res_stride, res_hw or (H, Wd)
     ca = S.SaberConv2D(int8=True).init((N, Cc, Ho, Wo), pa, mdt, O.S8, s_in, s_mid)
@@ -100,7 +102,9 @@ def _head(rng, N, H, Wd, idt, mdt, res_relu, Cc=256, stride=2, res_stride=2, x_i
         bp1, sc1 = O.conv_i8_prepare(ws1, b1, s_in, s_mid, mdt, O.S8)
         t1 = O.conv_i8(t0, O.quant_weights(w1, ws1), bp1, sc1, O.S8, 0)
         sub = O.pool_i8_nhwc(res_in, (1, 1), (2, 2), (0, 0), 0, floor_mode=True)
-        want = O.eltwise_i8(t1, sub, s_mid, s_res, c, c, bool(res_relu))
+        want = O.eltwise_i8(t1, sub, s_mid, s_res, cc[0], cc[1], bool(res_relu))
+        if detail is not None:
+            detail.update(t1=t1, res=sub, s0=s_mid, s1=s_res, coeff=cc, relu=bool(res_relu), want=want)
     return c0, ca, want
 
 

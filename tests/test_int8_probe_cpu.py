@@ -105,14 +105,67 @@ def test_eltwise_grid_model_equals_the_oracle_and_its_defects_show(mode):
     c, s0, s1 = P.ELT_SETS[mode]
     a, b = P.eltwise_grid()
     detects = {"half": ("elt_rne",), "sum": ("wrap", "clamp_m127"), "order": ("elt_assoc", "elt_fma", "elt_premul"),
-               "below_half": ("half_identity_05",)}[mode]
+               "below_half": ("half_identity_05",), "uneq": ("coeff_swap", "coeff_conv_for_both"), "neg": P.COEFF_DEFECTS,
+               "zero_res": ("coeff_swap", "coeff_conv_for_both")}[mode]
+    assert (c[0] != c[1]) == (mode in P.COEFF_MODES)
     for relu in (False, True):
-        want = O.eltwise_i8(a, b, s0, s1, c, c, relu)
+        want = O.eltwise_i8(a, b, s0, s1, c[0], c[1], relu)
         assert np.array_equal(P.eltwise_model(a, b, c, s0, s1, relu), want), (mode, relu)
         for defect in detects:
             if defect == "clamp_m127" and relu:
                 continue
             assert (P.eltwise_model(a, b, c, s0, s1, relu, defect) != want).any(), (mode, relu, defect)
+
+
+NEW_ELT_PROBES = [n for g in sorted(GROUPS) if g.startswith("elt/") for n in GROUPS[g] if n.rsplit("/", 1)[1] in P.COEFF_MODES]
+
+
+def test_unequal_coefficient_probes_model_equals_the_oracle_and_every_coefficient_defect_shows():
+    """The three modes with c0 != c1 on every fused geometry: products exact in float32 (t is a multiple of one half), the clean model is
+    the oracle byte for byte, and a swapped pair, the conv's coefficient used for both and (mode neg) a dropped sign each change bytes
+    of every probe - in two lane positions k % 4 (assert_classes)."""
+    assert len(NEW_ELT_PROBES) == len(P.FUSED_GEOMETRIES) * 2 * 3 * len(P.COEFF_MODES)
+    n_def = 0
+    for name in NEW_ELT_PROBES:
+        p = P.build(name)
+        (c0, c1), s0, s1 = P.ELT_COEFFS[p.meta["elt_mode"]]
+        assert c0 != c1 and p.elt[2] == (c0, c1) and (p.out_scale, p.elt[3]) == (s0, s1) == (0.5, 0.5)
+        t2 = 2.0 * p.t().astype(np.float64)
+        assert np.array_equal(t2, np.rint(t2)), name
+        assert np.array_equal(P.emulate(p), P.oracle_bytes(p)), name
+        P.assert_classes(p)
+        for defect in P.COEFF_DEFECTS:
+            assert p.applies(defect) == (defect != "coeff_sign_dropped" or p.meta["elt_mode"] == "neg")
+            if p.applies(defect):
+                assert (P.emulate(p, defect) != P.oracle_bytes(p)).any(), (name, defect)
+                n_def += 1
+    assert n_def == len(NEW_ELT_PROBES) // 3 * 7
+
+
+@pytest.mark.parametrize("shape", P.STAGE_PROBE_SHAPES)
+def test_stage_probe_shapes_build_and_hold_every_class(shape):
+    """the probes of the stage launch's first block at its own shapes (two images, ragged tiles; C = 64 among them): they build, hold
+    every class in two lane positions, the model is the oracle, and every coefficient defect shows where it applies"""
+    probes = P.stage_block_probes(shape)
+    assert len(probes) == 3 + 2 * len(P.ELT_MODES)
+    for which, name, geo in probes:
+        p = P.build(name, geo)
+        assert p.acc.shape[:3] == (shape[1], shape[2], shape[3])
+        P.assert_classes(p)
+        assert np.array_equal(P.emulate(p), P.oracle_bytes(p)), (shape, name)
+        for defect in P.COEFF_DEFECTS:
+            assert not p.applies(defect) or p.designated(defect).any(), (shape, name, defect)
+    c64 = [s for s in P.STAGE_PROBE_SHAPES if s[0] == 64]      # tiles of 2 rows x 16 columns
+    assert all(-(-s[2] // 2) >= 3 and s[2] % 2 for s in c64), "at least three tile rows with a ragged last row"
+    assert any(-(-s[3] // 16) == 2 and s[3] % 16 for s in c64) and any(s[1] == 2 for s in c64), "two column tiles with a ragged one; two images"
+
+
+def test_the_four_earlier_coefficient_sets_are_unchanged():
+    assert P.ELT_MODES[:4] == ("half", "sum", "order", "below_half")
+    assert [P.ELT_COEFFS[m] for m in P.ELT_MODES[:4]] == [((1.0, 1.0), 0.5, 0.5), ((2.0, 2.0), 0.5, 0.5), ((float(P.F(1.0 / 0.06)),) * 2, 0.05, 0.043),
+                                                          ((1.0, 1.0), float(P.HALF_LO), float(P.HALF_LO))]
+    for m in P.ELT_MODES[:4]:
+        assert not any(P.build("elt/pw_k64/s8/relu0_res0/" + m).applies(d) for d in P.COEFF_DEFECTS)
 
 
 @pytest.mark.parametrize("odt", [P.S8, P.U8])

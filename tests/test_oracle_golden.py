@@ -80,6 +80,14 @@ def test_conv_i8_properties():
     rp = O.Residual(O.RES_ELTWISE, 1, 0.0, O.S8, 20.0, 20.0, 0.05, 0.07)
     fused = O.conv_i8(x1, wq, None, scale, O.S8, 0, (1, 1), residual=rp, res=res)
     assert np.array_equal(two_op, fused)
+    # coeff_conv goes with the conv's output and coeff_res with the residual, whatever the pair (tests/test_oracle_vs_ref.py holds the
+    # eltwise op itself to the compiled reference for these pairs)
+    for c0, c1 in [(20.0, 12.5), (20.0, -10.0), (-1.0, 1.0), (20.0, 0.0), (0.0, 20.0)]:
+        for relu in (0, 1):
+            rp = O.Residual(O.RES_ELTWISE, relu, 0.0, O.S8, c0, c1, 0.05, 0.07)
+            fused = O.conv_i8(x1, wq, None, scale, O.S8, 0, (1, 1), residual=rp, res=res)
+            assert np.array_equal(O.eltwise_i8(y, res, 0.05, 0.07, c0, c1, bool(relu)), fused), (c0, c1, relu)
+            assert (O.eltwise_i8(y, res, 0.05, 0.07, c1, c0, bool(relu)) != fused).any(), (c0, c1, relu)
 
 
 def test_round_identity_exhaustive():

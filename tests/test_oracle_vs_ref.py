@@ -84,14 +84,39 @@ def test_quant_dequant_reorder_matches_reference(dt):
     assert np.array_equal(f, O.ref_reorder(q, 1, O.F32, 0.05))
 
 
+# coefficient pairs with c0 != c1: unequal positive, (c, -c/2), (-1, 1), (c, 0), (0, c)
+UNEQUAL_COEFFS = [(20.0, 12.5), (20.0, -10.0), (-1.0, 1.0), (20.0, 0.0), (0.0, 20.0)]
+
+
 @pytest.mark.parametrize("relu", [0, 1])
 def test_eltwise_i8_matches_reference(relu):
     rng = np.random.default_rng(5)
     a = rng.integers(-128, 128, (2, 7, 7, 32)).astype(np.int8)
     b = rng.integers(-128, 128, (2, 7, 7, 32)).astype(np.int8)
-    for (sa, sb, c0, c1) in [(0.031, 0.047, 1.0, 1.0), (0.5, 0.25, 1.0, 1.0), (0.02, 0.03, 20.0, 20.0)]:
+    for (sa, sb, c0, c1) in [(0.031, 0.047, 1.0, 1.0), (0.5, 0.25, 1.0, 1.0), (0.02, 0.03, 20.0, 20.0)] + \
+            [(0.02, 0.03, c0, c1) for c0, c1 in UNEQUAL_COEFFS] + [(0.5, 0.5, 1.0, 3.0), (0.5, 0.5, 1.0, -1.0), (0.5, 0.5, 2.0, 0.0)]:
         got = O.eltwise_i8(a, b, sa, sb, c0, c1, relu)
-        assert np.array_equal(got, O.ref_eltwise_i8(a, b, sa, sb, c0, c1, relu))
+        assert np.array_equal(got, O.ref_eltwise_i8(a, b, sa, sb, c0, c1, relu)), (sa, sb, c0, c1)
+        if c0 != c1:       # the pair is told apart: the operands exchanged with the coefficients kept give other bytes
+            assert (got != O.eltwise_i8(b, a, sa, sb, c0, c1, relu)).mean() >= 0.25, (sa, sb, c0, c1)
+
+
+@pytest.mark.parametrize("relu", [0, 1])
+def test_conv_i8_fused_eltwise_is_conv_then_eltwise_for_unequal_coefficients(relu):
+    """orc_conv_i8's RES_ELTWISE branch == orc_conv_i8 followed by orc_eltwise_i8 (which the reference pins above): coeff[0] and scale[0]
+    belong to the convolution's output, coeff[1] and scale[1] to the residual, for every coefficient pair."""
+    rng = np.random.default_rng(15)
+    x = rng.integers(-60, 60, (1, 9, 9, 32)).astype(np.int8)
+    wq = rng.integers(-127, 128, (16, 32, 3, 3)).astype(np.int8)
+    scale = np.full(16, 3e-4, np.float32)
+    y = O.conv_i8(x, wq, None, scale, O.S8, 0, (1, 1))
+    res = rng.integers(-128, 128, y.shape).astype(np.int8)
+    for c0, c1 in UNEQUAL_COEFFS + [(20.0, 20.0)]:
+        two_op = O.eltwise_i8(y, res, 0.05, 0.07, c0, c1, relu)
+        rp = O.Residual(O.RES_ELTWISE, relu, 0.0, O.S8, c0, c1, 0.05, 0.07)
+        fused = O.conv_i8(x, wq, None, scale, O.S8, 0, (1, 1), residual=rp, res=res)
+        assert np.array_equal(two_op, fused), (c0, c1)
+        assert np.array_equal(two_op, O.ref_eltwise_i8(y, res, 0.05, 0.07, c0, c1, relu)), (c0, c1)
 
 
 def test_eltwise_f32_matches_reference():
