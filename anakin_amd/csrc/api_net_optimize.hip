@@ -249,8 +249,9 @@ int saber_hip_net_optimize(saber_hip_net_t* net, int flags) {
                 const int pr = producer(tr, (int)i);
                 if (pr >= p) continue;   // the residual must exist when the conv runs (external tensors: pr == -1)
                 // the fused conv writes e.out at the CONV's position: no live op in (p, i) may read or write that tensor,
-                // and it must not alias the residual (in-place eltwise)
-                bool clash = e.out == tr;
+                // and it must not alias the residual or the conv's own output (in-place eltwise: e.out == tc would become the fused
+                // conv's output AND the edge whose storage is freed below)
+                bool clash = e.out == tr || e.out == tc;
                 for (int j = p + 1; j < (int)i && !clash; ++j)
                     if (!dead[j]) clash = op_touches(ops[j], e.out);
                 if (clash) continue;
@@ -315,6 +316,13 @@ int saber_hip_net_optimize(saber_hip_net_t* net, int flags) {
             NetOp& q = ops[i];
             const int p = producer(q.in, (int)i);
             if (p < 0 || !plain_i8_conv(ops[p]) || consumers(q.in) != 1) continue;
+            {   // the pooled tensor is written at the CONV's position instead: nothing in (p, i) may read or write it, and it must
+                // not be the conv's own output (an in-place pooling: the edge whose storage is freed below)
+                bool clash = q.out == q.in;
+                for (int j = p + 1; j < (int)i && !clash; ++j)
+                    if (!dead[j]) clash = op_touches(ops[j], q.out);
+                if (clash) continue;
+            }
             const saber_hip_conv* src = ops[p].conv;
             saber_hip_conv* fused = nullptr;
             int rc = clone_conv_i8(src, src->d, &fused);
