@@ -133,18 +133,18 @@ static void pack_frag3(const int8_t* w, int C, int ch_base, int tap, int ks, std
 //   3x3, channels q*64 + nt*16 .. +15:        [tap][k-step kh*2 + {0, 1}]                                        18 fragments
 //   1x1 + eltwise, channels q*256 + w*32 ..:  [k-step (q + i) % 4, i = 0..3][accumulator 0, 1]                    8 (its own mid k-step first)
 //   1x1, channels q*64 + nt*16 .. +15:        k-steps (q*4 + j) % 16, j = kh*2 + {0, 1} then 4 + kh*6 + {0..5}    8 (its own y1 channels first)
-static void pack_coop4_stream(const saber_hip_conv* c3, const saber_hip_conv* a, const saber_hip_conv* b, std::vector<uint8_t>& out) {
+static void pack_coop4_stream(const int8_t* w3, const int8_t* wa, const int8_t* wb, std::vector<uint8_t>& out) {
     const int C = 256, K1 = 1024;
     for (int q = 0; q < 4; ++q)
         for (int w = 0; w < 8; ++w) {
             const int nt = w & 3, kh = w >> 2;
             for (int tap = 0; tap < 9; ++tap)
-                for (int kl = 0; kl < 2; ++kl) pack_frag3(c3->wq_oihw.data(), C, q * 64 + nt * 16, tap, kh * 2 + kl, out);
+                for (int kl = 0; kl < 2; ++kl) pack_frag3(w3, C, q * 64 + nt * 16, tap, kh * 2 + kl, out);
             for (int i = 0; i < 4; ++i)
-                for (int mf = 0; mf < 2; ++mf) pack_frag1(a->wq_oihw.data(), C, q * 256 + w * 32, 2, mf, (q + i) & 3, out);
-            for (int jj = 0; b && jj < 8; ++jj) {      // (b == nullptr: a stage's tail has no second 1x1 conv - 26 fragments per (quarter, wave))
+                for (int mf = 0; mf < 2; ++mf) pack_frag1(wa, C, q * 256 + w * 32, 2, mf, (q + i) & 3, out);
+            for (int jj = 0; wb && jj < 8; ++jj) {      // (wb == nullptr: a stage's tail has no second 1x1 conv - 26 fragments per (quarter, wave))
                 const int j = jj < 2 ? kh * 2 + jj : 4 + kh * 6 + (jj - 2);
-                pack_frag1(b->wq_oihw.data(), K1, q * 64 + nt * 16, 1, 0, (q * 4 + j) & 15, out);
+                pack_frag1(wb, K1, q * 64 + nt * 16, 1, 0, (q * 4 + j) & 15, out);
             }
         }
 }
@@ -307,7 +307,7 @@ static int stage_build(saber_hip_chain* const* chains, int n, bool per_image, sa
         saber_mi355x::StageBlk B;
         std::memset(&B, 0, sizeof B);
         B.wstream = stream; B.prm0 = ch->d_prm0.p; B.prm1 = ch->d_prm1.p; B.prm2 = ch->d_prm2.p;
-        B.coeff_conv = da.coeff_conv; B.scale_conv = ch->a->out_scale; B.coeff_res = da.coeff_res; B.scale_res = da.scale_res;
+        B.coeff_conv = da.coeff_conv; B.scale_conv = ch->scale_conv; B.coeff_res = da.coeff_res; B.scale_res = da.scale_res;
         B.in0_u8 = ch->c3->x_dtype == DT_U8; B.relu0 = ch->c3->d.act == SABER_HIP_ACT_RELU;
         B.in_u8 = ch->a->x_dtype == DT_U8; B.relu1 = da.act == SABER_HIP_ACT_RELU; B.res_relu = da.res_act == SABER_HIP_ACT_RELU;
         B.relu2 = ch->b->d.act == SABER_HIP_ACT_RELU; B.out_u8_2 = ch->b->d.out_dtype == SABER_HIP_U8;
@@ -345,13 +345,17 @@ static int stage_build(saber_hip_chain* const* chains, int n, bool per_image, sa
     hipError_t e = hipSuccess;
     if (tail) {      // its constants are block n of the table (prm2: unused, the launch copies it like a block's - any readable constants do)
         std::vector<uint8_t> ts;
-        pack_coop4_stream(tail->c3, tail->a, nullptr, ts);
+        if (tail->tail_w3.empty() || tail->tail_wa.empty()) {
+            delete st;
+            return fail(SABER_HIP_INVALID_VALUE, "stage: the tail chain holds no copy of its members' weights");
+        }
+        pack_coop4_stream(tail->tail_w3.data(), tail->tail_wa.data(), nullptr, ts);      // (the weights the CHAIN was created with, like its constants)
         e = st->d_tail_stream.upload(ts);
         const saber_hip_conv_desc& da = tail->a->d;
         saber_mi355x::StageBlk B;
         std::memset(&B, 0, sizeof B);
         B.wstream = st->d_tail_stream.p; B.prm0 = tail->d_prm0.p; B.prm1 = tail->d_prm1.p; B.prm2 = tail->d_prm0.p;
-        B.coeff_conv = da.coeff_conv; B.scale_conv = tail->a->out_scale; B.coeff_res = da.coeff_res; B.scale_res = da.scale_res;
+        B.coeff_conv = da.coeff_conv; B.scale_conv = tail->scale_conv; B.coeff_res = da.coeff_res; B.scale_res = da.scale_res;
         B.in0_u8 = tail->c3->x_dtype == DT_U8; B.relu0 = tail->c3->d.act == SABER_HIP_ACT_RELU;
         B.in_u8 = tail->a->x_dtype == DT_U8; B.relu1 = da.act == SABER_HIP_ACT_RELU; B.res_relu = da.res_act == SABER_HIP_ACT_RELU;
         blk.push_back(B);
@@ -493,7 +497,7 @@ static void pack_chain_stream(const saber_hip_chain* ch, ChainStream layout, std
                 pack_chain_weights(wb, k2w, c2, 1, w, out, half * k2w, nw, half * (c2 / 128));
             }
         break;
-    default: pack_coop4_stream(c3, a, b, out);      // CS_COOP4
+    default: pack_coop4_stream(w3, wa, wb, out);      // CS_COOP4
     }
 }
 static int chain_build(saber_hip_conv* c3, saber_hip_conv* a, saber_hip_conv* b, saber_hip_chain_t** out, saber_hip_conv* b2 = nullptr) {
@@ -540,6 +544,11 @@ static int chain_build(saber_hip_conv* c3, saber_hip_conv* a, saber_hip_conv* b,
     saber_hip_chain* ch = new saber_hip_chain();
     const int k2 = b ? b->d.k + (pair2 ? b2->d.k : 0) : 0;
     ch->c3 = c3; ch->a = a; ch->b = b; ch->b2 = b2; ch->c1 = da.c; ch->k1 = da.k; ch->k2 = k2;
+    ch->scale_conv = a->out_scale;
+    if (c3 && !b && da.c == 256 && strided) {      // a possible tail of a stage launch: the stage packs its stream from THESE weights (copies at create)
+        ch->tail_w3 = c3->wq_oihw;
+        ch->tail_wa = a->wq_oihw;
+    }
     ch->form = chain_form_default(ch);
     // one stream per layout that some form of this chain reads; the placement-dependent ones only where the device places workgroups the
     // way their hand-off relies on (probed once per device)
@@ -636,7 +645,7 @@ int saber_hip_conv2d_chain_run3(saber_hip_chain_t* ch, const void* x, const void
     k.in_u8 = a->x_dtype == DT_U8;
     k.relu1 = a->d.act == SABER_HIP_ACT_RELU;
     k.res_relu = a->d.res_act == SABER_HIP_ACT_RELU;
-    k.coeff_conv = a->d.coeff_conv; k.scale_conv = a->out_scale; k.coeff_res = a->d.coeff_res; k.scale_res = a->d.scale_res;
+    k.coeff_conv = a->d.coeff_conv; k.scale_conv = ch->scale_conv; k.coeff_res = a->d.coeff_res; k.scale_res = a->d.scale_res;
     if (b) {
         k.relu2 = b->d.act == SABER_HIP_ACT_RELU;
         k.out_u8_2 = b->d.out_dtype == SABER_HIP_U8;

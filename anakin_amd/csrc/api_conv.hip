@@ -312,6 +312,9 @@ int group_static_form(const saber_hip_conv* op) {
 int saber_hip_conv2d_set_weights(saber_hip_conv_t* op, const void* w, int w_dtype, const float* w_scale,
                                  const float* bias, float in_scale, float out_scale) {
     if (!op || !w) return fail(SABER_HIP_INVALID_VALUE, "null argument");
+    // a sibling pair holds its members' rows one behind the other ([k1][k2 padded to 128]), not one conv's K rows: it cannot be repacked from
+    // one weight tensor here - set the members' weights and create the pair again
+    if (op->pair_k2) return fail(SABER_HIP_INVALID_VALUE, "set_weights on a sibling pair: set the members' weights and create the pair again");
     const saber_hip_conv_desc& d = op->d;
     const int K = d.k, Cg = d.c / d.group, kh = d.kh, kw = d.kw;
     const size_t inner = (size_t)Cg * kh * kw;
@@ -412,6 +415,15 @@ int saber_hip_conv2d_set_weights(saber_hip_conv_t* op, const void* w, int w_dtyp
         HIP_TRY(op->d_scale.upload(scale));
         op->has_comp = !comp.empty();
         if (op->has_comp) HIP_TRY(op->d_comp.upload(comp));
+        // weights set again on a live op: the image-resident kernel's own packing (img_stage: its weight fragments, the {scale, bias', comp}
+        // table and scale_conv, built from the mirrors above) follows too; the selection and the fused global pooling stay
+        if (op->img_stage) {
+            img_conv_release(op);
+            if (op->sel.fam == FAM_IMG1 || op->gpool) {
+                const int rc = img_conv_prepare(op);
+                if (rc) return rc;
+            }
+        }
     } else {
         if (w_dtype != SABER_HIP_F32) return fail(SABER_HIP_INVALID_VALUE, "FP32 conv needs f32 weights");
         const float* wf = (const float*)w;

@@ -231,6 +231,10 @@ struct saber_hip_chain {
     saber_hip_conv* b = nullptr;
     saber_hip_conv* b2 = nullptr;   // strided head + sibling pair (saber_hip_conv2d_chain_create3_pair): b and b2 both read a's output
     int c1 = 0, k1 = 0, k2 = 0;
+    float scale_conv = 1.f;         // a's out_scale WHEN THE CHAIN WAS CREATED (the fused eltwise's first scale): copied like the weights and constants, so that
+                                    // every form of the chain and every stage built from it use the value a's packed per-channel scale was made with
+    std::vector<int8_t> tail_w3, tail_wa;   // strided head at C = 256 (no second 1x1 conv): c3's and a's quantised weights as they were when the chain was
+                                    // created - a stage that takes the chain as its tail packs its own stream layout from them
     ChainForm form;                 // the selected form (written by chain_build, set_tile and the fall-back from a placement-dependent form)
     DevBuf<uint8_t> d_stream[CS_COUNT];   // one stream per layout that some form of this chain reads (chain_build)
     DevBuf<uint8_t> d_prm0, d_prm1, d_prm2;
@@ -287,6 +291,7 @@ struct saber_hip_ir {
     saber_hip_conv* dw = nullptr;
     saber_hip_conv* project = nullptr;
     int form = 0;                   // the selected row of conv_ir.hip's form table (its code)
+    float scale_conv = 1.f;         // project's out_scale when the block was created (the fused eltwise's first scale): copied like the constant tables
     DevBuf<uint8_t> d_we, d_eprm, d_wdw, d_wp, d_pprm;
     DevBuf<float> d_dw_bias, d_dw_scale;
     std::string name;               // "ir_expand_dw_project_i8_<form>" of the selected form

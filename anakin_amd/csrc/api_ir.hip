@@ -124,6 +124,7 @@ int saber_hip_conv2d_ir_create(saber_hip_conv_t* ex, saber_hip_conv_t* dw, saber
     if (dw->has_bias && (int)dw->bias_p_host.size() >= Ce) std::copy(dw->bias_p_host.begin(), dw->bias_p_host.begin() + Ce, dbias.begin());
     auto* ir = new saber_hip_ir();
     ir->expand = ex; ir->dw = dw; ir->project = pr;
+    ir->scale_conv = pr->out_scale;
     hipError_t e = ir->d_we.upload(we);
     if (e == hipSuccess) e = ir->d_wp.upload(wp);
     if (e == hipSuccess) e = ir->d_wdw.upload(wdw);
@@ -163,7 +164,7 @@ int saber_hip_conv2d_ir_run(saber_hip_ir_t* ir, const void* x, void* y_expand, v
     a.stride = dw->d.stride_h;
     a.out_u8 = pr->d.out_dtype == SABER_HIP_U8; a.p_relu = pr->d.act == SABER_HIP_ACT_RELU;
     a.elt = pr->d.res_mode == SABER_HIP_RES_ELTWISE; a.res_relu = pr->d.res_act == SABER_HIP_ACT_RELU;
-    a.coeff_conv = pr->d.coeff_conv; a.scale_conv = pr->out_scale; a.coeff_res = pr->d.coeff_res; a.scale_res = pr->d.scale_res;
+    a.coeff_conv = pr->d.coeff_conv; a.scale_conv = ir->scale_conv; a.coeff_res = pr->d.coeff_res; a.scale_res = pr->d.scale_res;
     HIP_TRY(launch_conv_ir(ir->form, ex->x_dtype == DT_U8, a, (hipStream_t)stream));
     return SABER_HIP_OK;
 }

@@ -62,6 +62,9 @@ int saber_hip_fc_set_weights(saber_hip_fc_t* fc, const void* w, int w_dtype, con
     saber_hip_conv* op = fc->conv;
     if (!fc->d.int8_weights) return saber_hip_conv2d_set_weights(op, wnk, w_dtype, w_scale, bias, 1.f, 1.f);
     // INT8: the conv-style set_weights gives us quantised weights + comp; then override scale/bias
+    // (the inner conv's host mirrors scale_host / bias_p_host / comp_host keep the conv-style values. Nothing reads them for an fc: their readers
+    // - pairs, chains, stages, the image-resident kernel, separable / inverted-residual / Fire launches - take saber_hip_conv_t operands with
+    // epi == EPI_I8_CONV, the inner conv has an fc epilogue and is reachable through saber_hip_fc_t alone: for its selection, never as an operand)
     int rc = saber_hip_conv2d_set_weights(op, wnk, w_dtype, w_scale, nullptr, in_scale, out_scale);
     if (rc) return rc;
     const int K_pad = round_up(N, 128);

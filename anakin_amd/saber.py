@@ -560,6 +560,16 @@ class SaberFc:
         self.ws = torch.empty(max(nbytes, 16), dtype=torch.uint8, device="cuda") if nbytes else None
         return self
 
+    def set_weights(self, weight, bias=None, w_scale=None, in_scale=1.0, out_scale=1.0):
+        """New weights / bias / scales on the live op (saber_hip_fc_set_weights a second time): same shape, the kernel selection stays."""
+        w_np = np.ascontiguousarray(weight)
+        assert w_np.size == self.desc.n * self.desc.k, w_np.shape
+        w_dt = L.F32 if w_np.dtype == np.float32 else L.S8
+        ws = None if w_scale is None else np.ascontiguousarray(w_scale, np.float32)
+        b = None if bias is None else np.ascontiguousarray(bias, np.float32)
+        L.check(L.load().saber_hip_fc_set_weights(self.h, _np_ptr(w_np), w_dt, _np_ptr(ws), _np_ptr(b), float(in_scale), float(out_scale)))
+        return self
+
     def dispatch(self, x, y):
         L.check(L.load().saber_hip_fc_run(self.h, _p(x), _p(y), _p(self.ws), _stream()))
         return y

@@ -21,9 +21,24 @@
  *   *_create           once per operator ("init"/"create": shapes, algorithm choice)
  *   *_set_weights      at "init" (quantise + repack weights, pre-scale bias — HOST pointers, cold path); saber_hip_conv2d_set_weights
  *                      may be called again on a live op: every packing of the op follows the new weights and bias (the FP32 stem
- *                      launch's and the pointwise kernels' planes included) and the kernel selection stays. It synchronises the
+ *                      launch's and the pointwise kernels' planes, the image-resident kernel's packing and the conv with fused global
+ *                      pooling included) and the kernel selection stays. It synchronises the
  *                      device. Pairs, chains and stages COPY their members' weights when they are created: they keep the weights
- *                      their members had then.
+ *                      their members had then. Per composite object, after set_weights on a member:
+ *                        sibling pair                      a, b COPIED (weights, bias', scale, comp). set_weights on the pair op itself is
+ *                                                          refused with SABER_HIP_INVALID_VALUE: set the members, create the pair again
+ *                        chain (1x1, 3x3-led, strided      every member COPIED: weights, constants and a's out_scale as the fused eltwise's
+ *                          head, head + pair)              first scale - the same stored values in every form of the chain
+ *                        chain stage (+ tail, + head)      copies of its chains' copies (their stored scale too, also when the stage is built
+ *                                                          after a member's second set_weights); head_a / head_b COPIED at stage create
+ *                        XCD stage (saber_hip_stage_*)     every phase's conv COPIED
+ *                        stem pair                         `stem` LIVE (the launch reads the stem op's own buffers: it follows), a, b COPIED
+ *                        separable pair, inverted-         every member COPIED (the block's eltwise scale too)
+ *                          residual block, Fire module
+ *                      No output mixes old and new parameters of ONE member: a member is either wholly the copy or wholly live.
+ *                      set_weights REALLOCATES the op's device buffers: a graph captured before it (saber_hip_net_capture, or the caller's own
+ *                      stream capture of *_run calls) holds the old addresses and must be captured again. A net after
+ *                      saber_hip_net_optimize has re-created ops of its own: after set_weights on an op of it, build the net again.
  *   *_run              every inference ("dispatch"): enqueues on the given hipStream_t, never syncs.
  * All tensor pointers given to *_run are DEVICE pointers owned by the caller.
  * Memory contract of every *_run entry point, of saber_hip_net_bind_tensor and of the pointers a captured list records:
@@ -212,7 +227,8 @@ int saber_hip_conv2d_autotune_pair(saber_hip_conv_t* pair, const void* x, void* 
  * branch2a) run as ONE launch on shared pixel tiles. Shapes C -> 4C -> C with C in {64, 128, 256, 512}. Both outputs are
  * written and hold the same bits as  saber_hip_conv2d_run(a) ; saber_hip_conv2d_run(b)  (reference: the two
  * GemmX8S8S32XConv::dispatch calls + SaberEltwise, gemm_x8s8s32x_conv.cpp:184-257). The chain refers to a and b (they
- * must outlive it and keep their weights) and owns only the repacked weight stream. */
+ * must outlive it: their descriptors are read at every run) and owns the repacked weight streams, the constant tables and a's out_scale as
+ * they were when it was created: a later set_weights on a member does not reach it. */
 typedef struct saber_hip_chain saber_hip_chain_t;
 int saber_hip_conv2d_chain_create(saber_hip_conv_t* a, saber_hip_conv_t* b, saber_hip_chain_t** out);
 /* ... led by the block's 3x3 conv (stride 1, pad 1, C -> C with C in {64, 128, 256}, 8-bit output = a's input): three
