@@ -12,6 +12,7 @@
 //   api_net_optimize.hip  executor-level fusions (saber_hip_net_optimize)
 //   api_net_autotune.hip  whole-net autotuner, selection save / restore
 //   api_gemm.hip          FP32 GEMM on the bf16-plane kernels (device-side plane split, per-thread plan cache)
+//   api_deconv.hip        transposed convolution (FP32): create / set_weights (repack + fragment stream) / run, its forms and static rule
 //   api_capture.hip       op-list capture: the *_run calls of a caller's own op loop recorded into a saber_hip_net
 #pragma once
 #include "../../include/saber_hip.h"
@@ -308,6 +309,19 @@ struct saber_hip_fire {
     std::string name;               // "fire_squeeze_expand_i8_<form>" of the selected form
 };
 
+// a transposed convolution (api_deconv.hip, deconv.hip): FP32 only, a type of its own - nothing of saber_hip_conv reads it
+struct saber_hip_deconv {
+    saber_hip_conv_desc d;
+    int oh = 0, ow = 0;
+    int form = 0;            // 0: deconv_direct_f32; 1 / 2: deconv_b3_f32_4x16 / _2x16 (written by deconv_set_form only)
+    bool b3_ok = false;      // the bf16-plane forms exist for this descriptor
+    bool weights_set = false, has_bias = false;
+    std::vector<float> w_host;        // [c][k / group][kh][kw] as handed to set_weights (the fragment stream is packed from it on demand)
+    DevBuf<float> d_w, d_bias;        // the direct kernel's [tap][c][k / group] repack; the bias
+    DevBuf<uint8_t> d_wfrag;          // the bf16-plane forms' fragment stream (deconv_b3_pack)
+    std::string algo_name;
+};
+
 struct saber_hip_fc {
     saber_hip_fc_desc d;
     saber_hip_conv* conv = nullptr;
@@ -410,7 +424,7 @@ struct ColdScope {
 
 // op-list executor
 namespace saber_api {
-enum OpKind { OP_CONV, OP_CONV_PAIR, OP_FC, OP_QUANT, OP_DEQUANT, OP_TRANSPOSE_IN, OP_ELT_I8, OP_ELT_F32, OP_POOL_I8, OP_POOL_F32, OP_POOL_F32_I8, OP_FC_Q, OP_SOFTMAX, OP_RELU_F32, OP_ACT_F32, OP_CONCAT };
+enum OpKind { OP_CONV, OP_CONV_PAIR, OP_FC, OP_QUANT, OP_DEQUANT, OP_TRANSPOSE_IN, OP_ELT_I8, OP_ELT_F32, OP_POOL_I8, OP_POOL_F32, OP_POOL_F32_I8, OP_FC_Q, OP_SOFTMAX, OP_RELU_F32, OP_ACT_F32, OP_CONCAT, OP_DECONV };
 // What an op launches in the current selection: DERIVED from the sites' decisions by net_resolve (api_net_optimize.hip), never set elsewhere
 enum Launch { LAUNCH_NONE, LAUNCH_OWN, LAUNCH_CHAIN, LAUNCH_CHAIN3, LAUNCH_STAGE, LAUNCH_STEM_PAIR, LAUNCH_SEP, LAUNCH_IR, LAUNCH_FIRE };
 // A SITE is a group of adjacent ops that can run as one launch. The op that heads a site holds the site's object and its DECISION (*_on: stored
@@ -422,6 +436,7 @@ struct NetOp {
     std::string name;
     saber_hip_conv* conv = nullptr;
     saber_hip_fc* fc = nullptr;
+    saber_hip_deconv* deconv = nullptr;      // OP_DECONV
     int in = -1, in2 = -1, out = -1, out2 = -1;
     // OP_CONCAT: EVERY input id in channel order (in = ins[0], in2 stays -1), their channel counts in elements and - u8 with rescaling - the
     // per-input multipliers (empty: a copy). Whatever asks which tensors an op reads goes through op_for_each_input / op_reads below.
@@ -560,6 +575,7 @@ extern thread_local Capture* g_capture;
 int capture_conv(saber_hip_conv* op, const void* x, void* y, const void* res);
 int capture_fc(saber_hip_fc* fc, const void* x, float* y, bool quantised_input);
 int capture_unsupported(const char* what);
+int capture_deconv(saber_hip_deconv* op, const void* x, void* y);
 int capture_concat(size_t pixels, int n_inputs, const void* const* xs, const int* channels, const float* mult, int dtype, void* y);
 // streaming ops: kind + the argument block of the matching saber_hip_net_add_* call; in2 / out2 may be null
 int capture_stream_op(OpKind kind, const char* name, const int* p, int np, const float* f, int nf, size_t count, const void* in,
@@ -634,6 +650,10 @@ bool fire_form_valid(const saber_hip_fire* fr, int code);
 void for_each_fire_form(const saber_hip_fire* fr, const std::function<void(int code)>& fn);
 int fire_static_form(const saber_hip_fire* fr);      // the executor's static choice: a form code, or 0 = four launches
 void net_set_fire(saber_hip_net* net, int i, int code);      // api_net_optimize.hip: the site headed by ops[i] on (a valid form code) / off (0)
+// transposed convolutions (api_deconv.hip)
+bool deconv_form_valid(const saber_hip_deconv* op, int form);      // the form exists for this op
+int deconv_static_form(const saber_hip_deconv* op);      // create's choice: measured rows only (profiles/deconv/README.md), else 0
+void for_each_deconv_form(const saber_hip_deconv* op, const std::function<void(int form)>& fn);      // the autotuner's candidates, form 0 first
 // api_chain.hip; y_tail: the tail's output - the tail then runs inside the launch (a stage created with one), null: the blocks only
 // y_head: the second output of the stage's head - the pair then runs inside the launch (a stage created with one), x is the PAIR's input and res is not read
 int stage_run(saber_hip_chain_stage* st, const void* x, const void* res, void* const* y1, void* const* y2, hipStream_t s, void* y_tail = nullptr,

@@ -99,6 +99,7 @@ int net_launch(saber_hip_net* net, const NetOp& o, hipStream_t s) {
         for (size_t k = 0; k < o.ins.size(); ++k) xs[k] = T(o.ins[k]);
         return saber_hip_concat_nhwc(o.count, (int)o.ins.size(), xs, o.cat_c.data(), o.cat_m.empty() ? nullptr : o.cat_m.data(), o.p[0], T(o.out), s);
     }
+    case OP_DECONV: return saber_hip_deconv2d_run(o.deconv, T(o.in), T(o.out), s);
     }
     return SABER_HIP_UNIMPL;
 }
@@ -272,6 +273,18 @@ int saber_hip_net_add_concat(saber_hip_net_t* net, size_t pixels, int n_inputs, 
     o.cat_c.assign(channels, channels + n_inputs);
     if (mult) o.cat_m.assign(mult, mult + n_inputs);
     o.p[0] = dtype;
+    return push(net, std::move(o));
+}
+int saber_hip_net_add_deconv(saber_hip_net_t* net, saber_hip_deconv_t* op, int in_id, int out_id) {
+    if (!net || !op) return fail(SABER_HIP_INVALID_VALUE, "null argument");
+    const int nt = (int)net->tensor_bytes.size();
+    if (in_id < 0 || in_id >= nt || out_id < 0 || out_id >= nt || in_id == out_id) return fail(SABER_HIP_INVALID_VALUE, "bad tensor id");
+    const saber_hip_conv_desc& d = op->d;
+    if (net->tensor_bytes[in_id] < (size_t)d.n * d.h * d.w * d.c * 4) return fail(SABER_HIP_INVALID_VALUE, "deconv: the input tensor is smaller than n x h x w x c floats");
+    if (net->tensor_bytes[out_id] < (size_t)d.n * op->oh * op->ow * d.k * 4) return fail(SABER_HIP_INVALID_VALUE, "deconv: the output tensor is smaller than n x oh x ow x k floats");
+    NetOp o;
+    o.kind = OP_DECONV; o.deconv = op; o.in = in_id; o.out = out_id;
+    o.name = std::string("deconv:") + op->algo_name;
     return push(net, std::move(o));
 }
 int saber_hip_net_add_softmax(saber_hip_net_t* net, int rows, int cols, int in_id, int out_id) {
@@ -595,6 +608,13 @@ int saber_hip_net_op_work(const saber_hip_net_t* net, int index, double* bytes, 
         *bytes = (double)d.m * d.k * (o.kind == OP_FC_Q || d.in_dtype != SABER_HIP_F32 ? 1 : 4) + (double)d.m * d.n * 4 + (double)d.n * d.k * esz;
         *flops = 2.0 * d.m * d.n * d.k;
         if (o.out2 >= 0) *bytes += 2.0 * tb(o.out2);      // + the softmax it runs (flag 4096): the logits read back, the probabilities written
+        return SABER_HIP_OK;
+    }
+    case OP_DECONV: {      // input + output once, the weights once; a MAC per (input element, output channel of its group, tap)
+        const saber_hip_conv_desc& d = o.deconv->d;
+        const double wel = (double)d.c * (d.k / d.group) * d.kh * d.kw;
+        *bytes = 4.0 * ((double)d.n * d.h * d.w * d.c + (double)d.n * o.deconv->oh * o.deconv->ow * d.k + wel);
+        *flops = 2.0 * d.n * d.h * d.w * wel;
         return SABER_HIP_OK;
     }
     default:

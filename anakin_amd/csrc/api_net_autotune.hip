@@ -19,6 +19,8 @@ static saber_hip_conv* net_op_conv(saber_hip_net* net, int index) {
 // bit 30, a plain 1x1 conv without residual heads no chain (bit 28), leads none (bit 29) and is no depthwise op (28 and 29) - and a word
 // with bit 31 but not bit 30 changed nothing on any op before the flag existed.
 int saber_hip_net_get_choice(saber_hip_net_t* net, int index) {
+    if (net && index >= 0 && index < (int)net->ops.size() && net->ops[index].kind == OP_DECONV)
+        return (18 << 16) | saber_hip_deconv2d_get_tile(net->ops[index].deconv);      // a deconv op: variant 18, its form code in the low byte
     saber_hip_conv* c = net_op_conv(net, index);
     int choice = (c && !c->pool_fused && (c->algo <= ALGO_IGEMM_F32 || dw_ok(c) || group_ok(c))) ? saber_hip_conv2d_get_tile(c) : 0;
     if (!c) return choice;
@@ -46,6 +48,14 @@ int saber_hip_net_stage_head(const saber_hip_net_t* net, int index) {
     return net->ops[index - 1].head_of == index ? index - 1 : -1;
 }
 int saber_hip_net_set_choice(saber_hip_net_t* net, int index, int choice) {
+    if (net && index >= 0 && index < (int)net->ops.size() && net->ops[index].kind == OP_DECONV) {
+        if (net->reproducible_fp32 || ((choice >> 16) & 0xff) != 18) return SABER_HIP_OK;      // flag 8192: FP32 ops keep the static selection; a word without a deconv decision changes nothing
+        const int rc = saber_hip_deconv2d_set_tile(net->ops[index].deconv, choice & 0xffff);
+        if (rc) return rc;
+        net_resolve(net);
+        net_drop_graph(net);
+        return SABER_HIP_OK;
+    }
     saber_hip_conv* c = net_op_conv(net, index);
     // the block decision this choice carries (bit 31 without bit 30 on the expand op of a site); a code with no form for that block is refused
     // before anything changes. An expand op on the direct path (Cin % 16 == 8) has no selection of its own: the decision is all its word holds
@@ -223,6 +233,24 @@ int saber_hip_net_autotune(saber_hip_net_t* net, saber_hip_stream_t stream, int 
         int rc = saber_hip_conv2d_autotune(c, xin, T(o.out), T(o.in2), net->arena + net->ws_off, stream, iters);
         if (rc) return rc;
         o.res_note.clear();
+    }
+    // deconv ops: every form the op accepts, cold L2, on the real tensors; a bf16-plane form is kept only where it is faster than form 0
+    for (NetOp& o : net->ops) {
+        if (o.kind != OP_DECONV || net->reproducible_fp32) continue;
+        hipStream_t s = (hipStream_t)stream;
+        auto run = [&]() -> int { return net_launch(net, o, s); };
+        float best = 0.f;
+        int best_form = -1;
+        for_each_deconv_form(o.deconv, [&](int form) {
+            float us = -1.f;
+            if (saber_hip_deconv2d_set_tile(o.deconv, form) != SABER_HIP_OK) return;
+            if (time_enqueued(s, run, 20, &us) != SABER_HIP_OK) return;
+            if (best_form < 0 || us < best) { best = us; best_form = form; }
+        });
+        if (best_form < 0) return fail(SABER_HIP_RUNTIME_ERROR, "autotune: no form of a deconv op could be timed");
+        int rc = saber_hip_deconv2d_set_tile(o.deconv, best_form);
+        if (!rc) rc = run();      // the output holds the selected form's result
+        if (rc) return rc;
     }
     net_resolve(net);      // (the names of the tuned selections)
     const char* log_env = std::getenv("SABER_HIP_AUTOTUNE_LOG");

@@ -82,6 +82,8 @@ void net_resolve(saber_hip_net* net) {
         o.skip = o.launch == LAUNCH_NONE;
         if (o.kind == OP_CONCAT) {
             o.name = "concat" + std::to_string(o.ins.size()) + (o.skip ? " (in the fire launch)" : "");
+        } else if (o.kind == OP_DECONV) {
+            o.name = std::string("deconv:") + o.deconv->algo_name;
         } else if (o.kind == OP_SOFTMAX) {
             o.name = o.skip ? "softmax_f32 (in the fc launch)" : "softmax_f32";
         } else if (o.kind == OP_FC || o.kind == OP_FC_Q) {

@@ -452,6 +452,29 @@ bool conv_fire_geom(int code, int c, int s, int e1, int e3, int h, int w, FireGe
 hipError_t conv_fire_prepare();
 hipError_t launch_conv_fire(int code, bool in_u8, const FireKArgs& a, hipStream_t s);      // sets the tile fields of `a` from the form
 
+// FP32 transposed convolution (deconv.hip). x [N, C, H, W] logical, w: direct kernel = the weights repacked to [tap][C][K / group],
+// wfrag: the bf16-plane kernels' fragment stream (deconv_b3_pack), y [N, K, OH, OW] logical; gather kernels, no workspace.
+struct DeconvKArgs {
+    const float* x;
+    const float* w;
+    const void* wfrag;
+    const float* bias;    // [K] or null
+    float* y;
+    int N, H, W, C, K, OH, OW;
+    int kh, kw, stride_h, stride_w, pad_h, pad_w, dil_h, dil_w, group;
+    int in_nchw, out_nchw, relu;
+    int q0_h, q0_w, tiles_y, tiles_x;      // deconv_b3: first cell row / column, cell tiles per image (set by the launcher)
+};
+hipError_t launch_deconv_direct_f32(const DeconvKArgs& a, hipStream_t s);
+// the bf16-plane kernel: group 1, dilation 1, stride 2 x 2, kh == kw in {2, 3, 4}, pad <= k - 1, C % 32 == 0, K % 16 == 0, NHWC in and out;
+// form 1 = 4 x 16 cells per workgroup, 2 = 2 x 16 (a cell = the 2 x 2 output pixels of the four phases); same bits in both
+constexpr int DECONV_B3_FORMS = 2;
+bool deconv_b3_form(int form, int* th);
+bool deconv_b3_ok(int n, int h, int w, int c, int k, int kh, int kw, int stride_h, int stride_w, int pad_h, int pad_w, int dil_h, int dil_w, int group);
+int deconv_b3_taps(int ks, int (*ab)[2]);      // the stream's [phase][tap] order as (a, b) pairs; returns ks * ks
+void deconv_b3_pack(const float* w_ckab, int c, int k, int ks, std::vector<uint8_t>& out);      // [phase][tap][slab][tile][plane][lane] x 16 B
+hipError_t launch_deconv_b3_f32(int form, const DeconvKArgs& a, hipStream_t s);
+
 // reads `bytes` of device memory through every XCD (autotuning: the timed launch then finds none of its operands in
 // an L2, which is how it runs inside the op list)
 hipError_t launch_l2_flush(const void* buf, size_t bytes, unsigned* sink, hipStream_t s);

@@ -59,6 +59,9 @@ SYMBOLS = [
     "saber_hip_concat_nhwc", "saber_hip_net_add_concat",
     "saber_hip_conv2d_fire_create", "saber_hip_conv2d_fire_run", "saber_hip_conv2d_fire_set_tile", "saber_hip_conv2d_fire_get_tile",
     "saber_hip_conv2d_fire_algo", "saber_hip_conv2d_fire_destroy",
+    "saber_hip_deconv2d_create", "saber_hip_deconv2d_set_weights", "saber_hip_deconv2d_out_shape", "saber_hip_deconv2d_run",
+    "saber_hip_deconv2d_algo", "saber_hip_deconv2d_set_tile", "saber_hip_deconv2d_get_tile", "saber_hip_deconv2d_destroy",
+    "saber_hip_net_add_deconv",
 ]
 
 
@@ -277,6 +280,18 @@ def load():
     lib.saber_hip_conv2d_fire_destroy.restype = None
     lib.saber_hip_concat_nhwc.argtypes = [Z, I, C.POINTER(P), C.POINTER(I), C.POINTER(F), I, P, P]
     lib.saber_hip_net_add_concat.argtypes = [P, Z, I, C.POINTER(I), C.POINTER(I), C.POINTER(F), I, I]
+    lib.saber_hip_deconv2d_create.argtypes = [C.POINTER(ConvDesc), C.POINTER(P)]
+    lib.saber_hip_deconv2d_set_weights.argtypes = [P, P, P]
+    lib.saber_hip_deconv2d_out_shape.argtypes = [P, C.POINTER(I), C.POINTER(I)]
+    lib.saber_hip_deconv2d_out_shape.restype = None
+    lib.saber_hip_deconv2d_run.argtypes = [P, P, P, P]
+    lib.saber_hip_deconv2d_algo.argtypes = [P]
+    lib.saber_hip_deconv2d_algo.restype = C.c_char_p
+    lib.saber_hip_deconv2d_set_tile.argtypes = [P, I]
+    lib.saber_hip_deconv2d_get_tile.argtypes = [P]
+    lib.saber_hip_deconv2d_destroy.argtypes = [P]
+    lib.saber_hip_deconv2d_destroy.restype = None
+    lib.saber_hip_net_add_deconv.argtypes = [P, P, I, I]
     _lib = lib
     return lib
 

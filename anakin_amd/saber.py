@@ -181,6 +181,86 @@ class SaberConv2D:
             pass
 
 
+class SaberDeconv2D:
+    """SaberDeconv2D<MI355X, AK_FLOAT> (saber/funcs/deconv.h): transposed convolution, FP32 only.
+
+    init takes the NCHW-logical input shape and a ConvParam whose weight is [C, K / group, kh, kw] (the layout the reference's deconv hands
+    to its GEMM); relu is a clamp at 0. Output (h - 1) * stride + dilation * (k - 1) + 1 - 2 * pad per axis."""
+
+    def __init__(self):
+        self.h = C.c_void_p()
+
+    def init(self, in_shape_nchw, param, in_layout=L.NHWC, out_layout=L.NHWC):
+        lib = L.load()
+        n, c, h, w = in_shape_nchw
+        cw, kg, kh, kw = param.weight.shape
+        assert cw == c, (cw, c)
+        d = L.ConvDesc()
+        d.n, d.h, d.w, d.c, d.k, d.kh, d.kw = n, h, w, c, kg * param.group, kh, kw
+        d.pad_h, d.pad_w = param.pad
+        d.stride_h, d.stride_w = param.stride
+        d.dil_h, d.dil_w = param.dilation
+        d.group = param.group
+        d.in_dtype = d.out_dtype = L.F32
+        d.in_layout, d.out_layout = in_layout, out_layout
+        d.act = L.ACT_RELU if param.relu else L.ACT_NONE
+        d.act_negative_slope = float(getattr(param, "negative_slope", 0.0))
+        self.desc = d
+        L.check(lib.saber_hip_deconv2d_create(C.byref(d), C.byref(self.h)))
+        self.set_weights(param.weight, param.bias)
+        oh, ow = C.c_int(), C.c_int()
+        lib.saber_hip_deconv2d_out_shape(self.h, C.byref(oh), C.byref(ow))
+        self.out_hw = (oh.value, ow.value)
+        return self
+
+    def set_weights(self, weight, bias=None):
+        """New weights / bias on the live op: same shapes, every packing follows, the kernel selection stays."""
+        d = self.desc
+        w_np = np.ascontiguousarray(weight, np.float32)
+        assert w_np.shape == (d.c, d.k // d.group, d.kh, d.kw), w_np.shape
+        b = None if bias is None else np.ascontiguousarray(bias, np.float32)
+        assert b is None or b.shape == (d.k,)
+        L.check(L.load().saber_hip_deconv2d_set_weights(self.h, _np_ptr(w_np), _np_ptr(b)))
+        return self
+
+    def out_shape(self):
+        d = self.desc
+        oh, ow = self.out_hw
+        return (d.n, oh, ow, d.k) if d.out_layout == L.NHWC else (d.n, d.k, oh, ow)
+
+    def new_output(self):
+        return torch.empty(self.out_shape(), dtype=torch.float32, device="cuda")
+
+    def dispatch(self, x, y):
+        L.check(L.load().saber_hip_deconv2d_run(self.h, _p(x), _p(y), _stream()))
+        return y
+
+    def algo(self):
+        return L.load().saber_hip_deconv2d_algo(self.h).decode()
+
+    def set_tile(self, form):
+        L.check(L.load().saber_hip_deconv2d_set_tile(self.h, int(form)))
+
+    def tile(self):
+        return L.load().saber_hip_deconv2d_get_tile(self.h)
+
+    def forms(self):
+        """every form code this op accepts, form 0 (the direct kernel) first; the selection is left as it was"""
+        cur, ok = self.tile(), []
+        for f in range(3):
+            if L.load().saber_hip_deconv2d_set_tile(self.h, f) == 0:
+                ok.append(f)
+        self.set_tile(cur)
+        return ok
+
+    def __del__(self):
+        try:
+            if self.h:
+                L.load().saber_hip_deconv2d_destroy(self.h)
+        except Exception:
+            pass
+
+
 class SaberConv2DPooling:
     """SaberConv2DPooling<MI355X, AK_INT8> (saber/funcs/conv_pooling.h, ConvPoolingParam): conv followed by pooling.
     One fused kernel where the library has one (saber_hip_conv2d_set_pooling: the ResNet stem + 3x3/2 max pooling);
@@ -914,6 +994,11 @@ class Net:
         if concat is not None and concat.mult is not None:
             m = (C.c_float * n)(*[float(v) for v in concat.mult])
         return self._chk(L.load().saber_hip_net_add_concat(self.h, pixels, n, (C.c_int * n)(*tids), (C.c_int * n)(*chans), m, code, self.tid(out)))
+
+    def add_deconv(self, deconv, x, y):
+        """a SaberDeconv2D inside the op list (saber_hip_net_add_deconv), named deconv:<algo>"""
+        self.keep.append(deconv)
+        return self._chk(L.load().saber_hip_net_add_deconv(self.h, deconv.h, self.tid(x), self.tid(y)))
 
     def add_softmax(self, rows, cols, x, y):
         return self._chk(L.load().saber_hip_net_add_softmax(self.h, rows, cols, self.tid(x), self.tid(y)))

@@ -360,6 +360,37 @@ int saber_hip_conv2d_fire_get_tile(const saber_hip_fire_t* fire);
 const char* saber_hip_conv2d_fire_algo(const saber_hip_fire_t* fire);
 void saber_hip_conv2d_fire_destroy(saber_hip_fire_t* fire);
 
+/* ------------------------------------------------------------------------------------------- */
+/* Transposed convolution (Deconv<T,D>: saber/funcs/deconv.h; x86: SaberCol2ImDeconv<AK_FLOAT>), FP32 only */
+/* ------------------------------------------------------------------------------------------- */
+/* The descriptor is saber_hip_conv_desc read for a deconvolution: input [n, c, h, w], k OUTPUT channels, weights [c, k / group, kh, kw]
+ * (the layout SaberCol2ImDeconv hands to its GEMM), optional bias [k]:
+ *   y[n, ko, oh, ow] = bias[ko] + sum x[n, ci, ih, iw] * w[ci, ko mod (k / group), a, b]   over ci in ko's group and the taps (a, b) with
+ *                      oh = ih * stride_h - pad_h + a * dil_h, ow likewise, 0 <= ih < h, 0 <= iw < w
+ *   OH = (h - 1) * stride_h + dil_h * (kh - 1) + 1 - 2 * pad_h   (deconv_compute_shape, funcs_utils.h:56-82; no output padding)
+ * act: NONE or RELU as a clamp at 0 (the reference ignores negative_slope here: a non-zero act_negative_slope is SABER_HIP_INVALID_VALUE).
+ * FP32 only, as in the reference (its AK_INT8 deconv is an unimplemented stub): int8_weights != 0 or a dtype other than F32 returns
+ * SABER_HIP_UNIMPL; res_mode, res_act, res_stride, res_h, res_w, res_has_dtype, res_dtype != 0 return SABER_HIP_INVALID_VALUE (a deconv
+ * has no residual mode, no pooling and no pair). A separate object type: nothing about saber_hip_conv2d_* changes. create selects the kernel
+ * host-side from shapes alone and validates without a device.
+ * Kernels (anakin_amd/csrc/deconv.hip; both gather - one lane per output element, fixed order, no atomics, no workspace):
+ *   form 0 "deconv_direct_f32": every accepted descriptor (any group, dilation, per-axis kernel / stride / pad, NCHW or NHWC on either side);
+ *   form 1 | 2 "deconv_b3_f32_4x16" | "deconv_b3_f32_2x16": group 1, dilation 1, NHWC f32 in and out, c % 32 == 0, k % 16 == 0, stride 2 x 2,
+ *     kh == kw in {2, 3, 4}, pad <= kh - 1: the bf16 matrix cores on three operand planes, by output phase (4 x 16 or 2 x 16 cells of
+ *     2 x 2 output pixels per workgroup). Both b3 forms compute the same bits; they differ from form 0 within the FP32 contract (1e-4).
+ * set_tile takes a form code; a code the op is not eligible for returns SABER_HIP_INVALID_VALUE and changes nothing. get_tile returns it.
+ * set_weights: w, bias HOST pointers (f32); may be called again on a live op - every packing follows, the selection stays; it
+ * synchronises the device and reallocates the op's device buffers (a captured graph must be captured again). */
+typedef struct saber_hip_deconv saber_hip_deconv_t;
+int saber_hip_deconv2d_create(const saber_hip_conv_desc* desc, saber_hip_deconv_t** out);
+int saber_hip_deconv2d_set_weights(saber_hip_deconv_t* op, const float* w, const float* bias);
+void saber_hip_deconv2d_out_shape(const saber_hip_deconv_t* op, int* oh, int* ow);
+int saber_hip_deconv2d_run(saber_hip_deconv_t* op, const void* x, void* y, saber_hip_stream_t stream);
+const char* saber_hip_deconv2d_algo(const saber_hip_deconv_t* op);
+int saber_hip_deconv2d_set_tile(saber_hip_deconv_t* op, int form);
+int saber_hip_deconv2d_get_tile(const saber_hip_deconv_t* op);
+void saber_hip_deconv2d_destroy(saber_hip_deconv_t* op);
+
 /* XCD-resident stage: a run of INT8 convolutions over SMALL feature maps (h * w <= 64 pixels per image: ResNet's res5) as
  * ONE persistent launch. Image i is computed entirely on XCD i % 8 (32 CUs, one workgroup each); the convolutions
  * ("phases") follow each other inside the kernel, separated by an XCD-local barrier where one reads what an earlier one
@@ -717,6 +748,11 @@ int saber_hip_net_add_activation_f32(saber_hip_net_t* net, int active, size_t co
  * see every input. */
 int saber_hip_net_add_concat(saber_hip_net_t* net, size_t pixels, int n_inputs, const int* in_ids, const int* channels,
                              const float* mult, int dtype, int out_id);
+/* saber_hip_deconv2d_run inside an op list, named deconv:<algo>. The arena planner, saber_hip_net_op_work (bytes and MACs), capture /
+ * replay, the op-list capture and saber_hip_net_run_op see it; saber_hip_net_autotune times every form the op accepts (not under
+ * SABER_HIP_NET_REPRODUCIBLE_FP32) and saber_hip_net_get_choice / _set_choice carry the form code as (18 << 16) | form. No
+ * saber_hip_net_optimize rewrite touches it. The handle must outlive the net. */
+int saber_hip_net_add_deconv(saber_hip_net_t* net, saber_hip_deconv_t* op, int in_id, int out_id);
 /* Caller-owned storage for tensor `id` instead of a slot of the net's arena (the net's inputs and outputs when the caller
  * has buffers of its own: the reference's Net owns its edge tensors). Before finalize any tensor can be bound (ptr != NULL)
  * or returned to the arena (NULL); after finalize only the address of an already external tensor can change. A captured

@@ -10,7 +10,7 @@
 //   SoftmaxParam                                         saber/saber_funcs_param.h:48-110,470-677,1077-1140,1236-1279,2085-2153
 //   ImplBase<T, Op, Param>                               saber/funcs/impl/impl_base.h:33-69
 //   SaberConv2D / SaberConvEltwise / SaberConv2DPooling / SaberFc / SaberPooling / SaberEltwise / SaberSoftmax /
-//   SaberActivation <MI355X, OpDtype>, Gemm<MI355X>      the per-target specialisations of saber/funcs/impl/<target>/
+//   SaberActivation / SaberConcat / SaberDeconv2D <MI355X, OpDtype>, Gemm<MI355X>      the per-target specialisations of saber/funcs/impl/<target>/
 // As in the reference, weights and bias are TENSORS OF THE TARGET (device memory here); the implementations copy them to
 // the host once per init (saber_mi355x_impl.h: mi355x_host_view). HostBlob below is a convenience that builds such a tensor
 // from host data.
@@ -336,6 +336,8 @@ template <typename TargetType, DataType OpDtype>
 using SaberSoftmax = SaberSoftmaxMI355X<TargetType, OpDtype>;
 template <typename TargetType, DataType OpDtype>
 using SaberConcat = SaberConcatMI355X<TargetType, OpDtype>;
+template <typename TargetType, DataType OpDtype>
+using SaberDeconv2D = SaberDeconv2DMI355X<TargetType, OpDtype>;
 template <typename TargetType, DataType OpDtype>
 using SaberActivation = SaberActivationMI355X<TargetType, OpDtype>;
 template <typename TargetType>

@@ -463,6 +463,70 @@ public:
     }
 };
 
+// SaberDeconv2D<MI355X, AK_FLOAT> (saber/funcs/deconv.h; x86: SaberCol2ImDeconv<AK_FLOAT>, saber_col2im_deconv.cpp = GEMM + col2im). The
+// weight tensor is read as the x86 impl's GEMM reads it - [c][k / group][kh][kw], k = weight()->num() * group (deconv_compute_shape) -
+// and handed to saber_hip_deconv2d_set_weights as it is. Only Active_relu (a clamp at 0: fill_relu); a non-zero negative_slope is refused
+// by the C ABI. OpDtype AK_INT8: SaberUnImplError, as the reference's stub (saber_deconv.cpp:66-76).
+template <typename TargetType, DataType OpDtype>
+class SaberDeconv2DMI355X : public ImplBase<TargetType, OpDtype, ConvParam<TargetType> > {
+public:
+    SaberDeconv2DMI355X() : _op(nullptr) {}
+    ~SaberDeconv2DMI355X() {
+        if (_op) saber_hip_deconv2d_destroy(_op);
+    }
+    virtual SaberStatus init(const std::vector<Tensor<TargetType>*>& inputs, std::vector<Tensor<TargetType>*>& outputs,
+                             ConvParam<TargetType>& param, Context<TargetType>& ctx) {
+        this->_ctx = &ctx;
+        return create(inputs, outputs, param, ctx);
+    }
+    virtual SaberStatus create(const std::vector<Tensor<TargetType>*>& inputs, std::vector<Tensor<TargetType>*>& outputs,
+                               ConvParam<TargetType>& param, Context<TargetType>& ctx) {
+        this->_ctx = &ctx;
+        if (OpDtype != AK_FLOAT) return SaberUnImplError;
+        Tensor<TargetType>* in = inputs[0];
+        Tensor<TargetType>* out = outputs[0];
+        if (param.activation_param.has_active && param.activation_param.active != Active_relu) return SaberUnImplError;
+        saber_hip_conv_desc d;
+        memset(&d, 0, sizeof d);
+        d.n = in->num(); d.c = in->channel(); d.h = in->height(); d.w = in->width();
+        d.k = param.weight()->num() * param.group; d.kh = param.weight()->height(); d.kw = param.weight()->width();
+        d.pad_h = param.pad_h; d.pad_w = param.pad_w; d.stride_h = param.stride_h; d.stride_w = param.stride_w;
+        d.dil_h = param.dilation_h; d.dil_w = param.dilation_w; d.group = param.group;
+        d.in_dtype = mi355x_dtype(in->get_dtype());
+        d.out_dtype = mi355x_dtype(out->get_dtype());
+        d.in_layout = mi355x_layout(in->get_layout());
+        d.out_layout = mi355x_layout(out->get_layout());
+        d.act = param.activation_param.has_active ? SABER_HIP_ACT_RELU : SABER_HIP_ACT_NONE;
+        d.act_negative_slope = d.act == SABER_HIP_ACT_RELU ? param.activation_param.negative_slope : 0.f;
+        if (_op) { saber_hip_deconv2d_destroy(_op); _op = nullptr; }
+        int rc = saber_hip_deconv2d_create(&d, &_op);
+        if (rc) return mi355x_status(rc);
+        int oh = 0, ow = 0;
+        saber_hip_deconv2d_out_shape(_op, &oh, &ow);
+        if (out->num() != d.n || out->channel() != d.k || out->height() != oh || out->width() != ow) return SaberInvalidValue;
+        const Tensor<TargetType>* w = param.weight();
+        const Tensor<TargetType>* b = param.bias();
+        if (w->get_dtype() != AK_FLOAT || (long long)w->valid_size() != (long long)d.c * (d.k / d.group) * d.kh * d.kw) return SaberInvalidValue;
+        std::vector<char> wbuf, bbuf;
+        const void* wh = mi355x_host_view(*w, wbuf);
+        const void* bh = (b && b->valid_size() > 0) ? mi355x_host_view(*b, bbuf) : nullptr;
+        return mi355x_status(saber_hip_deconv2d_set_weights(_op, (const float*)wh, (const float*)bh));
+    }
+    virtual SaberStatus dispatch(const std::vector<Tensor<TargetType>*>& inputs, std::vector<Tensor<TargetType>*>& outputs,
+                                 ConvParam<TargetType>& param) {
+        if (!_op) return SaberNotInitialized;      // (a failed create() is not reported by BaseFunc::init: see SaberConvEltwiseMI355X::dispatch)
+        return mi355x_status(saber_hip_deconv2d_run(_op, inputs[0]->data(), outputs[0]->mutable_data(),
+                                                    (saber_hip_stream_t)this->_ctx->get_compute_stream()));
+    }
+    // Deconv<>::trans_weights static_casts to this (deconv.h:94-110): the repack happened in create()
+    SaberStatus trans_weights(Tensor<TargetType>&, Tensor<TargetType>&, int, int, int, int, int, int, int) { return SaberSuccess; }
+    const char* algo() const { return _op ? saber_hip_deconv2d_algo(_op) : ""; }
+    int set_tile(int form) { return _op ? saber_hip_deconv2d_set_tile(_op, form) : SABER_HIP_INVALID_VALUE; }
+
+private:
+    saber_hip_deconv_t* _op;
+};
+
 // Concat<MI355X, OpDtype> (saber/funcs/concat.h; x86: saber_concat.cpp) along the channel axis of 1 .. 8 tensors of one dtype:
 // NHWC (axis 3: the 8-bit edges and the target's FP32 edges) or any layout whose pixels collapse to one (NCHW [n, c, 1, 1], axis 1).
 // f32 and s8: a copy. u8: the x86 create's loops as they are written (saber_concat.cpp:163-201) - scale_max starts at the first

@@ -20,8 +20,10 @@
 #include "saber/funcs/conv.h"
 #include "saber/funcs/conv_eltwise.h"
 #include "saber/funcs/activation.h"
+#include "saber/funcs/deconv.h"
 #include "saber/funcs/timer.h"
 
+#include <cmath>
 #include <cstdio>
 #include <random>
 #include <vector>
@@ -228,6 +230,56 @@ int main() {
             if (st != SaberSuccess || worst > 1e-5) { printf("FAIL Activation<MI355X,AK_FLOAT> %s: status %d, max error %.3g\n", k.name, (int)st, worst); ++g_fail; }
             else printf("ok   Activation<MI355X,AK_FLOAT> %s under BaseFunc, max error %.2g\n", k.name, worst);
         }
+    }
+    {   // Deconv<MI355X, AK_FLOAT> under the reference's own BaseFunc (saber/funcs/deconv.h): compute_output_shape, init, operator() ->
+        // SaberDeconv2D<MI355X> -> saber_hip_deconv2d_*; NCHW f32 tensors as the x86 impl takes them, weights [c][k / group][kh][kw]; against
+        // a double-precision scatter of the col2im rule (saber_col2im_deconv.cpp). k3 / stride 2 / pad 1, group 2, bias + relu.
+        const int n = 2, c = 8, h = 5, w = 6, group = 2, kg = 3, k = kg * group, ks = 3, stride = 2, pad = 1;
+        Tensor<X86> hx(Shape({n, c, h, w}, Layout_NCHW), AK_FLOAT), hw(Shape({kg, c, ks, ks}, Layout_NCHW), AK_FLOAT), hb(Shape({1, k, 1, 1}, Layout_NCHW), AK_FLOAT);
+        float* px = (float*)hx.mutable_data();
+        float* pw = (float*)hw.mutable_data();
+        float* pb = (float*)hb.mutable_data();
+        for (int i = 0; i < n * c * h * w; ++i) px[i] = ((i * 37) % 101 - 50) * 0.02f;
+        for (int i = 0; i < c * kg * ks * ks; ++i) pw[i] = ((i * 53) % 97 - 48) * 0.01f;
+        for (int i = 0; i < k; ++i) pb[i] = 0.1f * (i - 2);
+        Tensor<MI355X> dx(hx.valid_shape(), AK_FLOAT), dw(hw.valid_shape(), AK_FLOAT), db(hb.valid_shape(), AK_FLOAT), dy;
+        dx.copy_from(hx); dw.copy_from(hw); db.copy_from(hb);
+        ConvParam<MI355X> param(group, pad, pad, stride, stride, 1, 1, &dw, &db, ActivationParam<MI355X>(Active_relu));
+        std::vector<Tensor<MI355X>*> ins{&dx}, outs{&dy};
+        Deconv<MI355X, AK_FLOAT> op;
+        SaberStatus st = op.compute_output_shape(ins, outs, param);
+        const int oh = (h - 1) * stride + ks - 2 * pad, ow = (w - 1) * stride + ks - 2 * pad;
+        const bool shape_ok = dy.valid_shape() == Shape({n, k, oh, ow}, Layout_NCHW);
+        dy.re_alloc(dy.valid_shape(), AK_FLOAT);
+        if (st == SaberSuccess) st = op.init(ins, outs, param, SPECIFY, SABER_IMPL, ctx);
+        if (st == SaberSuccess) st = op(ins, outs, param, ctx);
+        outs[0]->record_event(ctx.get_compute_stream());
+        outs[0]->sync();
+        Tensor<X86> hy(dy.valid_shape(), AK_FLOAT);
+        hy.copy_from(dy);
+        std::vector<double> want((size_t)n * k * oh * ow, 0.0);
+        for (int b = 0; b < n; ++b)
+            for (int ci = 0; ci < c; ++ci)
+                for (int ih = 0; ih < h; ++ih)
+                    for (int iw = 0; iw < w; ++iw)
+                        for (int a = 0; a < ks; ++a)
+                            for (int bb = 0; bb < ks; ++bb) {
+                                const int y = ih * stride - pad + a, x = iw * stride - pad + bb;
+                                if (y < 0 || y >= oh || x < 0 || x >= ow) continue;
+                                for (int kl = 0; kl < kg; ++kl)
+                                    want[(((size_t)b * k + (ci / (c / group)) * kg + kl) * oh + y) * ow + x] +=
+                                        (double)px[((b * c + ci) * h + ih) * w + iw] * pw[((ci * kg + kl) * ks + a) * ks + bb];
+                            }
+        double worst = 0, vmax = 0;
+        for (size_t i = 0; i < want.size() && shape_ok; ++i) {
+            double v = want[i] + pb[i / ((size_t)oh * ow) % k];
+            v = v > 0 ? v : 0;
+            vmax = std::max(vmax, v);
+            worst = std::max(worst, std::fabs((double)((const float*)hy.data())[i] - v));
+        }
+        ++g_run;
+        if (st != SaberSuccess || !shape_ok || !(worst <= 1e-4 * vmax)) { printf("FAIL Deconv<MI355X,AK_FLOAT>: status %d, shape %d, max error %.3g of %.3g\n", (int)st, (int)shape_ok, worst, vmax); ++g_fail; }
+        else printf("ok   Deconv<MI355X,AK_FLOAT> k3 s2 p1 group 2 under BaseFunc, max error %.2g of %.3g\n", worst, vmax);
     }
     printf("%d cases, %d failed\n", g_run, g_fail);
     return g_fail ? 1 : 0;
