@@ -4,6 +4,9 @@ existing FP32 1x1 conv C -> 4K (it moves the same bytes: the bar a deconv kernel
   python scripts/bench_deconv.py shapes [--out DIR]   every row x batch, every form the op accepts -> DIR/shapes.json
   python scripts/bench_deconv.py table  [--out DIR]   DIR/shapes.json -> DIR/README.md (no GPU needed); exit status 1 when the static rule
                                                       (what saber_hip_deconv2d_create selects) does not hold on a row
+  python scripts/bench_deconv.py check  [--out DIR]   every row x batch once per accepted form, nothing timed: each output against the float64
+                                                      rule of tests/deconv_util.py (computed on the CPU) on the project's two 1e-4 criteria, forms
+                                                      1 and 2 byte for byte -> DIR/check.txt; exit status 1 when a line fails
 
 The protocol is scripts/bench_group.py's: ONE process, the forms alternating, after a warm-up, with device events:
   cold  one launch per window with the operands cold in L2 - between two timed launches a 64 MB buffer is streamed through the L2s, as the
@@ -109,6 +112,67 @@ def shapes(out_dir):
     json.dump(rows, open(os.path.join(out_dir, "shapes.json"), "w"), indent=1)
 
 
+def _row_batches():
+    for (c, k, h, ks, pad) in ROWS:
+        for n in (1, 8):
+            oh = (h - 1) * 2 + ks - 2 * pad
+            if n * oh * oh * k * 4 < 256 << 20:
+                yield c, k, h, ks, pad, n
+
+
+def check(out_dir):
+    """the shapes of shapes.json, which are the ones create names a bf16-plane form for, compared with a reference (the timing runs compare
+    nothing). A batch-8 row is compared on its first and its last image: that covers the batch stride, and the float64 rule stays at two
+    images a row."""
+    import torch
+    from anakin_amd import lib as L
+    from anakin_amd import saber as S
+    from tests import deconv_util as DU
+    L.require_device()
+    rng = np.random.default_rng(0)
+    lines, bad = ["# scripts/bench_deconv.py check: f32 NHWC, bias and relu, stride 2; every accepted form once against the float64 rule "
+                  "(tests/deconv_util.py deconv_ref)",
+                  "# criteria: the largest error over the largest value, and every error over |value| + mean |value|, both <= 1e-4; forms 1 and 2 byte for byte",
+                  "# a batch-8 row is compared on its first and its last image (the batch stride); a batch-1 row in full"], 0
+    for (c, k, h, ks, pad, n) in _row_batches():
+        cs = DU.case(n, h, h, c, k, ks, pad=(pad, pad))
+        x, w, b = DU.make(cs, rng)
+        w *= np.float32(1.0 / (0.3 * np.sqrt(c)))
+        op = S.SaberDeconv2D().init((n, c, h, h), S.ConvParam(w, b, 1, (pad, pad), (2, 2), (1, 1), True))
+        static, forms = op.tile(), op.forms()
+        images = sorted({0, n - 1})
+        want = DU.deconv_ref(x[images], w, b, dict(cs, n=len(images)), True)
+        xd = torch.from_numpy(np.ascontiguousarray(x.transpose(0, 2, 3, 1))).cuda()
+        tag = "%d -> %d @ %d^2 k%d p%d batch %d" % (c, k, h, ks, pad, n)
+        got = {}
+        for f in forms:
+            op.set_tile(f)
+            y = op.new_output()
+            y.fill_(float("nan"))
+            op.dispatch(xd, y)
+            torch.cuda.synchronize()
+            got[f] = y.cpu().numpy()
+            try:
+                e_max, e_el = DU.fp32_close(got[f][images].transpose(0, 3, 1, 2), want, tag)
+                ok = True
+            except AssertionError as e:
+                (_, e_max, e_el), ok = e.args[0], False
+            bad += not ok
+            lines.append("%s: form %d %s%s images %s e_max %.3g e_el %.3g %s" % (tag, f, NAMES[f], " (static)" if f == static else "", images, e_max, e_el,
+                                                                                 "ok" if ok else "FAILED"))
+            print(lines[-1], flush=True)
+        same = got[1].tobytes() == got[2].tobytes() if 1 in got and 2 in got else None
+        bad += same is not True or forms != [0, 1, 2]
+        lines.append("%s: forms %s; forms 1 and 2 byte for byte over all %d images: %s" % (tag, forms, n, {True: "identical", False: "DIFFERENT", None: "NOT RUN"}[same]))
+        print(lines[-1], flush=True)
+        op.set_tile(static)
+    lines.append("%d row x batch combinations, %d failures" % (len(list(_row_batches())), bad))
+    print(lines[-1])
+    os.makedirs(out_dir, exist_ok=True)
+    open(os.path.join(out_dir, "check.txt"), "w").write("\n".join(lines) + "\n")
+    return 1 if bad else 0
+
+
 def _judge(r):
     """(form 0 cold, cold spread, form 0 warm, warm spread, {b3 form: within form 0's spread on both protocols})"""
     us, uw = r["us"], r["us_warm"]
@@ -193,7 +257,7 @@ def table(out_dir):
 
 if __name__ == "__main__":
     ap = argparse.ArgumentParser()
-    ap.add_argument("step", choices=["shapes", "table"])
+    ap.add_argument("step", choices=["shapes", "table", "check"])
     ap.add_argument("--out", default=os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "profiles", "deconv"))
     a = ap.parse_args()
-    sys.exit({"shapes": lambda: shapes(a.out), "table": lambda: table(a.out)}[a.step]() or 0)
+    sys.exit({"shapes": lambda: shapes(a.out), "table": lambda: table(a.out), "check": lambda: check(a.out)}[a.step]() or 0)

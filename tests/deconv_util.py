@@ -26,7 +26,25 @@ B3_CASES = {
     "k4s2p3": case(1, 4, 4, 32, 16, 4, pad=(3, 3)),
     "ragged": case(3, 17, 9, 96, 80, 4, pad=(1, 1)),                  # partial cell tiles, three slabs, batch stride, two channel blocks
 }
-PROBE_CASES = ("k2s2p0", "k4s2p1", "k3s2p1")
+OLD_B3 = tuple(B3_CASES)      # one cell tile along x each (b3_classes): what the seam cases below were added to
+# more than one cell tile along x: tile tx takes its left halo from columns of tile tx - 1. (cells h x w; column tiles; what it reaches)
+B3_CASES.update({
+    "seam_k4p1": case(1, 3, 16, 32, 16, 4, pad=(1, 1)),               # 4 x 17; 2, the last 1 column wide: the k4 halo column read across the seam
+    "seam_k2p0": case(2, 2, 17, 32, 16, 2),                           # 2 x 17; 2: no halo, two images
+    "seam_k3p1": case(1, 9, 33, 96, 80, 3, pad=(1, 1)),               # 9 x 33; 3: a middle tile, slab 2 lands in LDS buffer 0, two channel blocks
+    "seam_k4p2x0": case(2, 9, 20, 64, 144, 4, pad=(2, 0)),            # 8 x 21; 2: q0_h != q0_w, the third channel block has one live tile of four
+    "seam_k3p0x2": case(1, 5, 18, 32, 64, 3, pad=(0, 2)),             # 6 x 17; 2: the other pad order, K exactly 64
+    "seam_k4p1_twin": case(2, 16, 33, 128, 128, 4, pad=(1, 1)),       # 17 x 34; 3: a scaled twin of the measured k4 p1 rows, four slabs
+    "seam_k2p0_twin": case(2, 5, 17, 96, 16, 2),                      # 5 x 17; 2: the measured k2 rows' (k, pad): >= 2 tiles both ways, three slabs
+    "seam_k3p1_twin": case(2, 5, 17, 96, 16, 3, pad=(1, 1)),          # 5 x 17; 2: the measured k3 row's (k, pad) likewise
+    "seam_k4p1x2_full": case(1, 2, 33, 32, 16, 4, pad=(1, 2)),        # 3 x 32; 2 full column tiles starting at cell q0_w = 1
+    "seam_k4p1_probe": case(1, 3, 17, 64, 32, 4, pad=(1, 1)),         # 4 x 18; 2, two slabs: small enough for the single-term probes
+    "seam_k3p1_probe": case(1, 2, 17, 64, 32, 3, pad=(1, 1)),         # 2 x 17; 2, two slabs
+})
+PROBE_CASES = ("k2s2p0", "k4s2p1", "k3s2p1", "seam_k4p1_probe", "seam_k3p1_probe")
+# form 0 beyond one grid stride: launch_deconv_direct_f32 caps the grid at 16 384 blocks of 256 lanes, this case has 4 259 840 outputs
+STRIDE_CASES = {"two_grid_strides": case(2, 64, 64, 2, 130, 2)}
+MAC_BUDGET = 3e8              # multiply-adds of a case's float64 reference (under a second)
 # direct kernel only
 DIRECT_CASES = {
     "group2": case(2, 4, 5, 8, 6, 3, pad=(1, 1), group=2),
@@ -42,6 +60,54 @@ ALL_CASES = dict(B3_CASES, **DIRECT_CASES)
 
 def out_hw(cs):
     return tuple((cs[d] - 1) * cs["stride"][i] + cs["dil"][i] * (cs[kk] - 1) + 1 - 2 * cs["pad"][i] for i, (d, kk) in enumerate((("h", "kh"), ("w", "kw"))))
+
+
+def macs(cs):
+    """multiply-adds of deconv_ref"""
+    return cs["n"] * cs["h"] * cs["w"] * cs["c"] * (cs["k"] // cs["group"]) * cs["kh"] * cs["kw"]
+
+
+def b3_classes(cs):
+    """what a bf16-plane launch of the case looks like, computed as launch_deconv_b3_f32 and deconv_b3_f32_kernel do (deconv.hip): the
+    first cell q0 = pad div 2 per axis, the cell counts over t = o + pad in [pad, O - 1 + pad], the tiles of TH x 16 cells per form,
+    the 32-channel slabs, the 64-channel blocks"""
+    (ph, pw), (oh, ow) = cs["pad"], out_hw(cs)
+    q0h, q0w = ph // 2, pw // 2
+    qh, qw = (oh - 1 + ph) // 2 - q0h + 1, (ow - 1 + pw) // 2 - q0w + 1
+    tiles_x = (qw + 15) // 16
+    return dict(q0=(q0h, q0w), cells=(qh, qw), tiles_x=tiles_x, tiles_y={1: (qh + 3) // 4, 2: (qh + 1) // 2}, last_cols=qw - 16 * (tiles_x - 1),
+                nslab=cs["c"] // 32, ntile=cs["k"] // 16, nky=(cs["k"] + 63) // 64, pads_equal=ph == pw)
+
+
+def _at_least(v, top=3):
+    return min(v, top)
+
+
+def b3_coverage(cases):
+    """the classes a set of bf16-plane cases reaches, as the set of the names below; REQUIRED_CLASSES is what tests/test_deconv_cpu.py asks of
+    B3_CASES and of the sweep's draws"""
+    got = set()
+    for cs in cases:
+        cl = b3_classes(cs)
+        tx = cl["tiles_x"]
+        got.add("tiles_x %d" % _at_least(tx))
+        got.add("nslab %d" % _at_least(cl["nslab"]))
+        got.add("nky %d" % _at_least(cl["nky"]))
+        if cl["last_cols"] in (1, 16):
+            got.add("last tile %d" % cl["last_cols"])
+        if tx >= 2 and min(cl["tiles_y"].values()) >= 2:
+            got.add("tiles both ways")
+        if cs["pad"][0] != cs["pad"][1]:
+            got.add("pad_h < pad_w" if cs["pad"][0] < cs["pad"][1] else "pad_h > pad_w")
+        if tx >= 2:
+            got.add("k%d seam" % cs["kh"])
+            if cs["n"] > 1:
+                got.add("batch seam")
+    return got
+
+
+REQUIRED_CLASSES = {"tiles_x 1", "tiles_x 2", "tiles_x 3", "last tile 1", "last tile 16", "tiles both ways", "nslab 1", "nslab 2", "nslab 3",
+                    "nky 1", "nky 2", "nky 3", "pad_h < pad_w", "pad_h > pad_w", "k2 seam", "k3 seam", "k4 seam", "batch seam"}
 
 
 def make(cs, rng, bias=True):
@@ -264,3 +330,75 @@ def wrong_phase(p):
     w[:, :, [0, 1]] = w[:, :, [1, 0]]
     q = DeconvProbe(p.cs, p.x, w, p.bias, p.out_idx, p.x_idx, p.w_idx)
     return q
+
+
+# ---- random-geometry sweep: the class is drawn first (enumerated from the draw's index), then a shape inside it ----------------------------
+SWEEP_SEEDS = (0, 1, 2)
+SWEEP_DIRECT, SWEEP_B3 = 8, 9      # draws per seed: 24 direct launches, 27 bf16-plane cases x 3 forms
+
+
+def _pick(rng, seq):
+    return seq[int(rng.integers(len(seq)))]
+
+
+def _direct_draw(rng, i, seed):
+    """form 0 only. i enumerates: the layout pair (i mod 4), the group class (1 | depthwise | a proper divisor of gcd(C, K)), whether the
+    strides differ, whether a dilation is 2; the rest is drawn. Ragged C and K, kh != kw in 1 .. 5, stride 1 .. 3, pad 0 .. dil (k - 1)."""
+    j = i + seed
+    while True:
+        gclass = j % 3
+        if gclass == 0:
+            g, c, k = 1, _pick(rng, (1, 3, 5, 7, 9, 11)), _pick(rng, (1, 3, 5, 7, 9, 13))
+        elif gclass == 1:
+            g = _pick(rng, (3, 5, 7, 12))
+            c = k = g
+        else:
+            g = _pick(rng, (2, 3, 5))
+            c, k = g * _pick(rng, (1, 3, 5)), g * _pick(rng, (3, 5, 7))
+        kh = int(rng.integers(1, 6))
+        kw = _pick(rng, [v for v in range(1, 6) if v != kh])
+        sh = int(rng.integers(1, 4))
+        sw = _pick(rng, [v for v in range(1, 4) if v != sh]) if (j // 3) % 2 == 0 else int(rng.integers(1, 4))
+        dh, dw = (2, int(rng.integers(1, 3))) if (j // 2) % 2 == 0 else (int(rng.integers(1, 3)), int(rng.integers(1, 3)))
+        if (j // 2) % 4 == 2:
+            dh, dw = dw, dh
+        cs = case(int(rng.integers(1, 4)), int(rng.integers(1, 10)), int(rng.integers(1, 10)), c, k, kh, kw, stride=(sh, sw),
+                  pad=(int(rng.integers(0, dh * (kh - 1) + 1)), int(rng.integers(0, dw * (kw - 1) + 1))), dil=(dh, dw), group=g)
+        if min(out_hw(cs)) >= 1 and macs(cs) <= MAC_BUDGET:      # an empty output is redrawn inside the same class, never skipped
+            return dict(cs=cs, in_nchw=bool(i & 1), out_nchw=bool(i & 2), bias=bool(rng.integers(2)), relu=bool(rng.integers(2)))
+
+
+def _b3_draw(rng, i, seed):
+    """forms 0, 1, 2. (i, seed) enumerates every (k, column-tile class, row-tile class) of {2, 3, 4} x {1, 2, 3} x {1, 2, >= 3} once over the
+    three seeds - row tiles counted for the 4 x 16 form - and walks the slab count, the channel-block count and the last tile's width
+    (any | 1 | 16 columns); pads, the shape inside the class, the batch, bias and relu are drawn."""
+    txc, tyc = divmod(i, 3)
+    k = (2, 3, 4)[(i + seed) % 3]
+    c = (32, 64, 96, 128)[(i + seed) % 4]
+    kout = _pick(rng, ((16, 32, 48, 64), (80, 96, 112, 128), (144, 160))[(i // 3 + seed) % 3])
+    last = (None, 1, 16)[(i + 2 * seed) % 3]
+    while True:
+        pad = (int(rng.integers(0, k)), int(rng.integers(0, k)))
+        hs, ws = [], []
+        for v in range(1, 64):
+            cs = case(1, v, v, c, kout, k, pad=pad)
+            if min(out_hw(cs)) < 1:
+                continue
+            cl = b3_classes(cs)
+            if _at_least(cl["tiles_y"][1]) == tyc + 1 and cl["tiles_y"][1] <= 3:
+                hs.append(v)
+            if cl["tiles_x"] == txc + 1 and (last is None or cl["last_cols"] == last):
+                ws.append(v)
+        if not hs or not ws:
+            continue
+        cs = case(int(rng.integers(1, 4)), _pick(rng, hs), _pick(rng, ws), c, kout, k, pad=pad)
+        if macs(cs) > MAC_BUDGET:
+            cs["n"] = 1
+        if macs(cs) <= MAC_BUDGET:
+            return dict(cs=cs, bias=bool(rng.integers(2)), relu=bool(rng.integers(2)))
+
+
+def sweep_draws(seed):
+    """{"direct": [draw], "b3": [draw]}: the same draws in the CPU test (coverage, the torch tie) and in the GPU test"""
+    rng = np.random.default_rng([20260, seed])
+    return {"direct": [_direct_draw(rng, i, seed) for i in range(SWEEP_DIRECT)], "b3": [_b3_draw(rng, i, seed) for i in range(SWEEP_B3)]}

@@ -1,6 +1,7 @@
 """The deconv op without a GPU: the expected-value rule of tests/deconv_util.py against two independent statements of a transposed
-convolution, the C ABI's shape / validation / selection, a descriptor fuzz, the fragment stream of the bf16-plane kernel, and the proof that
-the single-term probes separate a right kernel from a wrong one."""
+convolution, the C ABI's shape / validation / selection, a descriptor fuzz, the fragment stream of the bf16-plane kernel, the proof that
+the single-term probes separate a right kernel from a wrong one, the classes of the launch that the cases and the sweep's draws reach, and
+a model of the kernel's tiling that shows which injected defects only the cases with more than one column tile catch."""
 import ctypes as C
 import os
 import subprocess
@@ -42,11 +43,20 @@ def _create(lib, d):
     return rc, h
 
 
-@pytest.mark.parametrize("name", sorted(DU.ALL_CASES))
+TIE_CASES = dict(DU.ALL_CASES, **DU.STRIDE_CASES)
+
+
+def _torch_ref(x, w, b, cs):
+    import torch
+    return torch.nn.functional.conv_transpose2d(torch.from_numpy(x).double(), torch.from_numpy(w).double(), None if b is None else torch.from_numpy(b).double(),
+                                                stride=cs["stride"], padding=cs["pad"], dilation=cs["dil"], groups=cs["group"]).numpy()
+
+
+@pytest.mark.parametrize("name", sorted(TIE_CASES))
 def test_numpy_rule_equals_torch_conv_transpose2d(name):
     """float64, 1e-12 of the largest value: groups, dilation and per-axis geometry included"""
     import torch
-    cs = DU.ALL_CASES[name]
+    cs = TIE_CASES[name]
     x, w, b = DU.make(cs, np.random.default_rng(FP._seed(name)))
     want = torch.nn.functional.conv_transpose2d(torch.from_numpy(x).double(), torch.from_numpy(w).double(), torch.from_numpy(b).double(),
                                                 stride=cs["stride"], padding=cs["pad"], dilation=cs["dil"], groups=cs["group"]).numpy()
@@ -56,11 +66,11 @@ def test_numpy_rule_equals_torch_conv_transpose2d(name):
     assert np.array_equal(DU.deconv_ref(x, w, b, cs, relu=True), np.maximum(got, 0.0))
 
 
-@pytest.mark.parametrize("name", sorted(DU.ALL_CASES))
+@pytest.mark.parametrize("name", sorted(TIE_CASES))
 def test_numpy_rule_equals_the_oracle_conv_on_the_zero_inserted_input(name):
     """the project's FP32 oracle conv (stride 1) on the input with stride - 1 zeros between pixels, weights flipped and transposed. The
-    oracle accumulates in f32 over at most 96 * 16 terms of random sign: 1e-5 on the project's two criteria."""
-    cs = DU.ALL_CASES[name]
+    oracle accumulates in f32 over at most 128 * 16 terms of random sign: 1e-5 on the project's two criteria."""
+    cs = TIE_CASES[name]
     x, w, b = DU.make(cs, np.random.default_rng(FP._seed(name)))
     xz, wc, pad, dil = DU.as_conv(x, w, cs)
     got = O.conv_f32_nchw(xz, wc, b, False, pad, (1, 1), dil, cs["group"])
@@ -211,6 +221,180 @@ def test_probes_pass_the_emulation_and_fail_injected_defects(name):
             assert any(len(p.failures(FP.emulate(p, defect=defect))) for p in _some(passes)), (name, fam, defect)
         # (an activation pass whose weights all sit on taps a >= 2 does not see the swap: the first pass starts at tap (0, 0))
         assert len(passes[0].failures(FP.emulate(DU.wrong_phase(passes[0])))), (name, fam, "wrong phase")
+
+
+def test_b3_cases_reach_every_class_of_the_launch():
+    """the classes of launch_deconv_b3_f32 (deconv_util.b3_classes) that B3_CASES holds: one, two and three or more column tiles, a last
+    column tile of exactly 1 and of exactly 16 columns, two or more tiles both ways under both forms, 1 / 2 / >= 3 slabs and channel blocks,
+    both orders of unequal pads, every k and a batch across a column seam. The cases from before the seam cases had one column tile each."""
+    assert DU.b3_classes(DU.B3_CASES["seam_k4p1"]) == dict(q0=(0, 0), cells=(4, 17), tiles_x=2, tiles_y={1: 1, 2: 2}, last_cols=1, nslab=1, ntile=1,
+                                                           nky=1, pads_equal=True)
+    cl = DU.b3_classes(DU.B3_CASES["seam_k4p2x0"])
+    assert (cl["q0"], cl["cells"], cl["tiles_x"], cl["nky"], cl["ntile"], cl["pads_equal"]) == ((1, 0), (8, 21), 2, 3, 9, False)
+    cl = DU.b3_classes(DU.B3_CASES["seam_k4p1_twin"])
+    assert (cl["cells"], cl["tiles_x"], cl["tiles_y"], cl["nslab"], cl["nky"]) == ((17, 34), 3, {1: 5, 2: 9}, 4, 2)
+    for name in ("seam_k2p0_twin", "seam_k3p1_twin"):      # the smallest H and W with two tiles both ways under the 4 x 16 form
+        cl = DU.b3_classes(DU.B3_CASES[name])
+        assert cl["cells"] == (5, 17) and cl["nslab"] == 3 and DU.B3_CASES[name]["n"] == 2
+    for name in ("seam_k4p1_probe", "seam_k3p1_probe"):
+        cl = DU.b3_classes(DU.B3_CASES[name])
+        assert cl["tiles_x"] >= 2 and cl["nslab"] >= 2 and name in DU.PROBE_CASES
+    old = DU.b3_coverage(DU.B3_CASES[n] for n in DU.OLD_B3)
+    assert all(DU.b3_classes(DU.B3_CASES[n])["tiles_x"] == 1 and DU.b3_classes(DU.B3_CASES[n])["pads_equal"] for n in DU.OLD_B3)
+    assert not DU.REQUIRED_CLASSES <= old and old & DU.REQUIRED_CLASSES == {"tiles_x 1", "nslab 1", "nslab 2", "nslab 3", "nky 1", "nky 2"}
+    now = DU.b3_coverage(DU.B3_CASES.values())
+    assert DU.REQUIRED_CLASSES <= now, sorted(DU.REQUIRED_CLASSES - now)
+    assert all(DU.macs(cs) <= DU.MAC_BUDGET for cs in list(DU.ALL_CASES.values()) + list(DU.STRIDE_CASES.values()))
+    cs = DU.STRIDE_CASES["two_grid_strides"]
+    assert cs["n"] * cs["k"] * np.prod(DU.out_hw(cs)) == 4259840 > 16384 * 256
+
+
+# ---- a model of the bf16-plane kernel's TILING (float64; the plane arithmetic is the emulation's business above) ----------------------------
+TILING_DEFECTS = {
+    "halo_zero": "the halo columns left of c0 read as zero for tx > 0",
+    "c0_no_q0": "c0 computed without q0_w",
+    "pad_h_twice": "pad_h used for both axes in the epilogue",
+    "stray_tile": "a tile past ntile stored, not skipped (the skip compares the tile's index inside its channel block)",
+    "stale_slab": "slab cc >= 2 not staged: read from the buffer's previous contents (slab cc - 2)",
+    "image_zero": "the image index dropped from the staging offset for tx > 0",
+}
+
+
+def tiled_model(x, w, bias, cs, th, defect=None):
+    """deconv_b3_f32_kernel<KS, TH> restated in numpy, workgroup after workgroup in blockIdx order (channel blocks fastest, then column
+    tiles, row tiles, images): cell origins q0 / c0, a (TH + HAL) x (16 + HAL) x 32-channel patch staged per slab into one of two buffers
+    (pixels outside the image are zeros), the stream's [phase][tap] order reading rows HAL - ja .. and columns HAL - jb .. of the patch, four
+    16-channel tiles per block with the tile index clamped to ntile - 1, the epilogue's (oh, ow) and its skips; stores go to a flat NHWC
+    array at the kernel's offsets (one outside the array is dropped). Returns NCHW float64, NaN where nothing was stored."""
+    N, C, H, W = x.shape
+    K, ks, (ph, pw) = cs["k"], cs["kh"], cs["pad"]
+    oh, ow = DU.out_hw(cs)
+    cl = DU.b3_classes(cs)
+    HAL = (ks + 1) // 2 - 1
+    HWID = 16 + HAL
+    (q0h, q0w), tiles_x, tiles_y = cl["q0"], cl["tiles_x"], cl["tiles_y"][{4: 1, 2: 2}[th]]
+    nslab, ntile, nky = cl["nslab"], cl["ntile"], cl["nky"]
+    xh = np.ascontiguousarray(x.transpose(0, 2, 3, 1)).astype(np.float64)
+    w64 = w.astype(np.float64)
+    b64 = np.zeros(nky * 64)
+    if bias is not None:
+        b64[:K] = bias
+    y = np.full(N * oh * ow * K, np.nan)
+    taps = [(rh, rw, ja, jb) for rh in range(2) for rw in range(2) for ja in range(ks // 2 if rh else (ks + 1) // 2)
+            for jb in range(ks // 2 if rw else (ks + 1) // 2)]
+    assert [(2 * rh + rw, rh + 2 * ja, rw + 2 * jb) for rh, rw, ja, jb in taps] == DU.stream_taps(ks)
+    for blk in range(N * tiles_y * tiles_x * nky):
+        ky, b = blk % nky, blk // nky
+        tx, b = b % tiles_x, b // tiles_x
+        ty, n = b % tiles_y, b // tiles_y
+        q0, c0 = q0h + ty * th, (0 if defect == "c0_no_q0" else q0w) + tx * 16
+        n_stage = 0 if defect == "image_zero" and tx > 0 else n
+        iy, ix = q0 - HAL + np.arange(th + HAL), c0 - HAL + np.arange(HWID)
+        oky, okx = (iy >= 0) & (iy < H), (ix >= 0) & (ix < W)
+        if defect == "halo_zero" and tx > 0:
+            okx[:HAL] = False
+        lds = [np.zeros((th + HAL, HWID, 32)), np.zeros((th + HAL, HWID, 32))]
+
+        def stage(cc, buf):
+            lds[buf][:] = 0.0
+            lds[buf][np.ix_(oky, okx)] = xh[n_stage][np.ix_(iy[oky], ix[okx])][:, :, cc * 32:(cc + 1) * 32]
+        kch = np.concatenate([min(ky * 4 + i, ntile - 1) * 16 + np.arange(16) for i in range(4)])      # the block's 64 channels, clamped
+        acc = np.zeros((4, 64, th, 16))
+        stage(0, 0)
+        for cc in range(nslab):
+            L = lds[cc & 1]
+            for rh, rw, ja, jb in taps:
+                acc[2 * rh + rw] += np.einsum("yxc,ck->kyx", L[HAL - ja:HAL - ja + th, HAL - jb:HAL - jb + 16],
+                                              w64[cc * 32:(cc + 1) * 32, kch, rh + 2 * ja, rw + 2 * jb])
+            if cc + 1 < nslab and not (defect == "stale_slab" and cc + 1 >= 2):
+                stage(cc + 1, (cc & 1) ^ 1)
+        for i in range(4):
+            t = ky * 4 + i
+            if (i if defect == "stray_tile" else t) >= ntile:
+                continue
+            for p in range(4):
+                oy = 2 * (q0 + np.arange(th)) + (p >> 1) - ph
+                ox = 2 * (c0 + np.arange(16)) + (p & 1) - (ph if defect == "pad_h_twice" else pw)
+                ok = ((oy >= 0) & (oy < oh))[:, None] & ((ox >= 0) & (ox < ow))[None, :]
+                off = (((n * oh + oy[:, None]) * ow + ox[None, :]) * K + t * 16)[None] + np.arange(16)[:, None, None]
+                val = acc[p, i * 16:(i + 1) * 16] + b64[t * 16:(t + 1) * 16, None, None]
+                ok = np.broadcast_to(ok[None], off.shape) & (off < y.size)
+                assert defect == "stray_tile" or t * 16 + 16 <= K
+                y[off[ok]] = val[ok]
+    return y.reshape(N, oh, ow, K).transpose(0, 3, 1, 2)
+
+
+def _trips(got, want):
+    try:
+        DU.fp32_close(got, want, "model")
+    except AssertionError:
+        return True
+    return False
+
+
+def test_tiling_model_equals_the_rule_and_every_injected_defect_needs_a_seam_case(capsys):
+    """unmodified, the model is the float64 rule on every bf16-plane case under both tile heights. Each defect of TILING_DEFECTS passes the
+    project's two criteria on every case from before the seam cases - or trips "ragged" alone (three slabs, a second channel block) - and
+    fails at least one seam case: the seam cases see what the older ones could not"""
+    data = {}
+    for name, cs in DU.B3_CASES.items():
+        x, w, b = DU.make(cs, np.random.default_rng(FP._seed(name)))
+        want = DU.deconv_ref(x, w, b, cs)
+        data[name] = (x, w, b, want)
+        for th in (4, 2):
+            got = tiled_model(x, w, b, cs, th)
+            assert not np.isnan(got).any(), (name, th)
+            assert np.abs(got - want).max() <= 1e-12 * np.abs(want).max(), (name, th)
+    report = []
+    for defect, text in TILING_DEFECTS.items():
+        tripped = []
+        for name, cs in DU.B3_CASES.items():
+            x, w, b, want = data[name]
+            if any(_trips(tiled_model(x, w, b, cs, th, defect), want) for th in ((4, 2) if DU.macs(cs) < 3e7 else (4,))):
+                tripped.append(name)
+        old, new = [n for n in tripped if n in DU.OLD_B3], [n for n in tripped if n not in DU.OLD_B3]
+        report.append("%s (%s): older cases tripped %s; seam cases tripped %s" % (defect, text, old or "none", new))
+        assert set(old) <= {"ragged"}, (defect, old)
+        assert new, defect
+    with capsys.disabled():
+        print("\n" + "\n".join(report))
+
+
+@pytest.mark.parametrize("seed", DU.SWEEP_SEEDS)
+def test_sweep_draws_cover_the_classes_and_the_rule_equals_torch_on_each(lib, seed):
+    """deconv_util.sweep_draws, for the seeds the GPU test uses: no empty output, every draw inside the reference's budget and equal to
+    conv_transpose2d; over the seeds (asserted under the last one) every class of the launch, every (k, column tiles, row tiles)
+    combination, every layout pair, groups, depthwise, a dilation of 2, unequal strides"""
+    draws = DU.sweep_draws(seed)
+    assert len(draws["direct"]) == DU.SWEEP_DIRECT and len(draws["b3"]) == DU.SWEEP_B3
+    assert repr(draws) == repr(DU.sweep_draws(seed))
+    for kind in ("direct", "b3"):
+        for d in draws[kind]:
+            cs = d["cs"]
+            assert min(DU.out_hw(cs)) >= 1 and DU.macs(cs) <= DU.MAC_BUDGET, cs
+            x, w, b = DU.make(cs, np.random.default_rng(seed), bias=d["bias"])
+            got, want = DU.deconv_ref(x, w, b, cs), _torch_ref(x, w, b, cs)
+            assert got.shape == want.shape and np.abs(got - want).max() <= 1e-12 * np.abs(want).max(), cs
+            rc, h = _create(lib, _desc(cs, L.NCHW if d.get("in_nchw") else L.NHWC, L.NCHW if d.get("out_nchw") else L.NHWC, d["relu"]))
+            assert rc == 0, (cs, lib.saber_hip_last_error())
+            assert lib.saber_hip_deconv2d_set_tile(h, 1) == lib.saber_hip_deconv2d_set_tile(h, 2) == (0 if kind == "b3" else -2), cs
+            lib.saber_hip_deconv2d_destroy(h)
+    if seed != DU.SWEEP_SEEDS[-1]:
+        return
+    every = [DU.sweep_draws(s) for s in DU.SWEEP_SEEDS]
+    b3 = [d["cs"] for dr in every for d in dr["b3"]]
+    direct = [d for dr in every for d in dr["direct"]]
+    now = DU.b3_coverage(b3)
+    assert DU.REQUIRED_CLASSES <= now, sorted(DU.REQUIRED_CLASSES - now)
+    assert {(cs["kh"], DU.b3_classes(cs)["tiles_x"], DU.b3_classes(cs)["tiles_y"][1]) for cs in b3} == {(k, a, c) for k in (2, 3, 4) for a in (1, 2, 3) for c in (1, 2, 3)}
+    assert {cs["c"] for cs in b3} == {32, 64, 96, 128} and {cs["n"] for cs in b3} == {1, 2, 3}
+    assert {(d["in_nchw"], d["out_nchw"]) for d in direct} == {(a, c) for a in (False, True) for c in (False, True)}
+    cases = [d["cs"] for d in direct]
+    assert all(cs["kh"] != cs["kw"] for cs in cases)
+    assert any(cs["group"] == 1 for cs in cases) and any(1 < cs["group"] < cs["c"] for cs in cases) and any(cs["group"] == cs["c"] == cs["k"] > 1 for cs in cases)
+    assert any(cs["dil"][0] > 1 for cs in cases) and any(cs["dil"][1] > 1 for cs in cases) and any(cs["stride"][0] != cs["stride"][1] for cs in cases)
+    assert any(cs["pad"][0] != cs["pad"][1] for cs in cases) and {d["bias"] for d in direct} == {d["relu"] for d in direct} == {False, True}
+    assert {cs["stride"][0] for cs in cases} == {1, 2, 3} and any(cs["c"] % 2 and cs["k"] % 2 for cs in cases)
 
 
 def test_static_rule_follows_the_measured_table(lib):

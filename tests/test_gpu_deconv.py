@@ -1,5 +1,6 @@
-"""The deconv op on the GPU (anakin_amd/csrc/deconv.hip): every form on the smallest shapes at which each mechanism can fail, against the
-float64 scatter of tests/deconv_util.py; single-term probes at 4 u; guard bands; set_weights on a live op; the op inside the executor (an
+"""The deconv op on the GPU (anakin_amd/csrc/deconv.hip): every form on the smallest shapes at which each mechanism can fail - more than one
+cell tile along x among them - against the float64 scatter of tests/deconv_util.py; single-term probes at 4 u and guard bands, across a
+column seam too; a seeded random-geometry sweep of every form; form 0 beyond one grid stride; set_weights on a live op; the op inside the executor (an
 encoder - decoder list with a skip connection); the Saber-side class through the stand-in C++ driver."""
 import os
 import subprocess
@@ -97,7 +98,7 @@ def test_single_term_probes(name):
             p.check(_run(op, p.x, f), "%s activation probe, %s" % (name, NAMES[f]))
 
 
-@pytest.mark.parametrize("name", ["k4s2p1", "k3s2p0", "ragged", "k2s2p0", "depthwise_k4s2p1", "k5s3p1"])
+@pytest.mark.parametrize("name", ["k4s2p1", "k3s2p0", "ragged", "k2s2p0", "depthwise_k4s2p1", "k5s3p1", "seam_k4p1_probe", "seam_k3p1_probe"])
 def test_every_form_between_guard_bands(name):
     """nothing is written outside the output, the read-only tensors keep their bytes, and the output does not depend on what lies next
     to the tensors (tests/guard_util.py)"""
@@ -119,6 +120,45 @@ def test_every_form_between_guard_bands(name):
                              lambda T, ws: op.dispatch(T["x"], T["y"]), plain=plain, what="%s %s" % (name, NAMES[f]))
         GU.assert_no_sentinel_run(out["y"], "%s %s" % (name, NAMES[f]))
         DU.fp32_close(out["y"].transpose(0, 3, 1, 2), want, (name, NAMES[f]))
+
+
+@pytest.mark.parametrize("seed", DU.SWEEP_SEEDS)
+def test_random_geometry_sweep_of_every_form(seed):
+    """deconv_util.sweep_draws (the class drawn first, then the shape; tests/test_deconv_cpu.py asserts what the seeds cover): the direct
+    kernel over groups, kh != kw, per-axis stride / dilation / pad, ragged channels and the four layout pairs; the bf16-plane forms over
+    k, unequal pads and one to three cell tiles each way - every form against the float64 rule, forms 1 and 2 byte for byte. No draw is
+    left out."""
+    draws = DU.sweep_draws(seed)
+    ran = 0
+    for d in draws["direct"]:
+        cs = d["cs"]
+        x, w, b = DU.make(cs, np.random.default_rng(seed), bias=d["bias"])
+        op = _op(cs, w, b, d["relu"], L.NCHW if d["in_nchw"] else L.NHWC, L.NCHW if d["out_nchw"] else L.NHWC)
+        assert op.forms() == [0], cs
+        DU.fp32_close(_run(op, x, 0), DU.deconv_ref(x, w, b, cs, d["relu"]), (seed, d))
+        ran += 1
+    for d in draws["b3"]:
+        cs = d["cs"]
+        x, w, b = DU.make(cs, np.random.default_rng(seed), bias=d["bias"])
+        op = _op(cs, w, b, d["relu"])
+        assert op.forms() == [0, 1, 2], cs
+        want = DU.deconv_ref(x, w, b, cs, d["relu"])
+        got = [_run(op, x, f) for f in (0, 1, 2)]
+        for f in (0, 1, 2):
+            DU.fp32_close(got[f], want, (seed, NAMES[f], d))
+        assert GU.same_bytes(got[1], got[2]), (seed, d, "the two bf16-plane forms differ")
+        ran += 1
+    assert ran == DU.SWEEP_DIRECT + DU.SWEEP_B3
+
+
+@pytest.mark.parametrize("out_layout", [L.NHWC, L.NCHW])
+def test_direct_kernel_beyond_one_grid_stride(out_layout):
+    """4 259 840 outputs against a grid capped at 16 384 blocks of 256 lanes: the loop's second trip, under both index decompositions"""
+    cs = DU.STRIDE_CASES["two_grid_strides"]
+    x, w, b = DU.make(cs, np.random.default_rng(FP._seed("two_grid_strides")))
+    op = _op(cs, w, b, False, L.NHWC, out_layout)
+    assert op.forms() == [0]
+    DU.fp32_close(_run(op, x, 0), DU.deconv_ref(x, w, b, cs), ("two grid strides", out_layout))
 
 
 def test_set_weights_twice_on_a_live_op():
