@@ -146,6 +146,17 @@ int capture_deconv(saber_hip_deconv* op, const void* x, void* y) {      // (the 
     return SABER_HIP_OK;
 }
 
+int capture_resize(saber_hip_resize* op, const void* x, void* y) {      // (the arguments were checked by saber_hip_resize_run)
+    Capture& c = *g_capture;
+    const saber_hip_resize_desc& d = op->d;
+    const int in = c.read(x, (size_t)d.n * d.h * d.w * d.c * 4);
+    const int out = c.write(y, (size_t)d.n * op->oh * op->ow * d.c * 4);
+    if (c.failed || in < 0 || out < 0) return c.bad("bad tensor");
+    if (saber_hip_net_add_resize(c.net, op, in, out) < 0) return c.bad("saber_hip_net_add_resize failed");
+    ++c.ops;
+    return SABER_HIP_OK;
+}
+
 int capture_fc(saber_hip_fc* fc, const void* x, float* y, bool quantised_input) {
     Capture& c = *g_capture;
     if (!fc || !x || !y) return fail(SABER_HIP_INVALID_VALUE, "null argument");

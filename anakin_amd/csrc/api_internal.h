@@ -13,6 +13,7 @@
 //   api_net_autotune.hip  whole-net autotuner, selection save / restore
 //   api_gemm.hip          FP32 GEMM on the bf16-plane kernels (device-side plane split, per-thread plan cache)
 //   api_deconv.hip        transposed convolution (FP32): create / set_weights (repack + fragment stream) / run, its forms and static rule
+//   api_resize.hip        resize (FP32): create (the host index / fraction tables) / run / run_sum, its forms and static rule
 //   api_capture.hip       op-list capture: the *_run calls of a caller's own op loop recorded into a saber_hip_net
 #pragma once
 #include "../../include/saber_hip.h"
@@ -322,6 +323,17 @@ struct saber_hip_deconv {
     std::string algo_name;
 };
 
+// a resize (api_resize.hip, resize.hip): FP32 only, a type of its own
+struct saber_hip_resize {
+    saber_hip_resize_desc d;
+    int oh = 0, ow = 0;
+    int form = 0;            // 0: resize_direct_f32; 1: resize_rows_f32; 2: resize_x2_f32 (written by resize_set_form only)
+    bool x2_ok = false;      // an integer x2 in mode 1 or 3 whose tables keep every tap within a row / column of o / 2 (form 2, with NHWC and c % 4 == 0)
+    std::vector<saber_mi355x::ResizeTap> th, tw;      // per output row / column: the taps and the fraction, in the reference's float steps (create)
+    DevBuf<saber_mi355x::ResizeTap> d_th, d_tw;       // ... on the device, from the first run or saber_hip_net_add_resize on
+    std::string algo_name;
+};
+
 struct saber_hip_fc {
     saber_hip_fc_desc d;
     saber_hip_conv* conv = nullptr;
@@ -424,9 +436,9 @@ struct ColdScope {
 
 // op-list executor
 namespace saber_api {
-enum OpKind { OP_CONV, OP_CONV_PAIR, OP_FC, OP_QUANT, OP_DEQUANT, OP_TRANSPOSE_IN, OP_ELT_I8, OP_ELT_F32, OP_POOL_I8, OP_POOL_F32, OP_POOL_F32_I8, OP_FC_Q, OP_SOFTMAX, OP_RELU_F32, OP_ACT_F32, OP_CONCAT, OP_DECONV };
+enum OpKind { OP_CONV, OP_CONV_PAIR, OP_FC, OP_QUANT, OP_DEQUANT, OP_TRANSPOSE_IN, OP_ELT_I8, OP_ELT_F32, OP_POOL_I8, OP_POOL_F32, OP_POOL_F32_I8, OP_FC_Q, OP_SOFTMAX, OP_RELU_F32, OP_ACT_F32, OP_CONCAT, OP_DECONV, OP_RESIZE };
 // What an op launches in the current selection: DERIVED from the sites' decisions by net_resolve (api_net_optimize.hip), never set elsewhere
-enum Launch { LAUNCH_NONE, LAUNCH_OWN, LAUNCH_CHAIN, LAUNCH_CHAIN3, LAUNCH_STAGE, LAUNCH_STEM_PAIR, LAUNCH_SEP, LAUNCH_IR, LAUNCH_FIRE };
+enum Launch { LAUNCH_NONE, LAUNCH_OWN, LAUNCH_CHAIN, LAUNCH_CHAIN3, LAUNCH_STAGE, LAUNCH_STEM_PAIR, LAUNCH_SEP, LAUNCH_IR, LAUNCH_FIRE, LAUNCH_RESIZE_SUM };
 // A SITE is a group of adjacent ops that can run as one launch. The op that heads a site holds the site's object and its DECISION (*_on: stored
 // as asked by the net_set_* setters and read back by saber_hip_net_get_choice; a decision is never changed to express what another site
 // does); what every op launches, which ops launch nothing and every conv / pair / fc / softmax op's name follow from the decisions in
@@ -437,6 +449,7 @@ struct NetOp {
     saber_hip_conv* conv = nullptr;
     saber_hip_fc* fc = nullptr;
     saber_hip_deconv* deconv = nullptr;      // OP_DECONV
+    saber_hip_resize* resize = nullptr;      // OP_RESIZE
     int in = -1, in2 = -1, out = -1, out2 = -1;
     // OP_CONCAT: EVERY input id in channel order (in = ins[0], in2 stays -1), their channel counts in elements and - u8 with rescaling - the
     // per-input multipliers (empty: a copy). Whatever asks which tensors an op reads goes through op_for_each_input / op_reads below.
@@ -500,6 +513,9 @@ struct NetOp {
     saber_hip_fire* fire = nullptr;
     int fire_out = -1;
     bool fire_on = false;
+    // a resize and the eltwise_f32 behind it that alone reads it (flag 131072, SABER_HIP_NET_RESIZE_SUM): THIS op is the resize; while rsum_on is
+    // set its launch covers the eltwise op behind it (resize + sum in one launch) and this op's own output edge is not written
+    bool rsum = false, rsum_on = false;
     int lane = 0;            // 0: caller's stream, 1: the net's side stream (graph::Lane, operator_func.h:103-114)
     bool record = false;     // an op on the other lane consumes this op's output: record an event after it
     int p[16] = {0};
@@ -576,6 +592,7 @@ int capture_conv(saber_hip_conv* op, const void* x, void* y, const void* res);
 int capture_fc(saber_hip_fc* fc, const void* x, float* y, bool quantised_input);
 int capture_unsupported(const char* what);
 int capture_deconv(saber_hip_deconv* op, const void* x, void* y);
+int capture_resize(saber_hip_resize* op, const void* x, void* y);
 int capture_concat(size_t pixels, int n_inputs, const void* const* xs, const int* channels, const float* mult, int dtype, void* y);
 // streaming ops: kind + the argument block of the matching saber_hip_net_add_* call; in2 / out2 may be null
 int capture_stream_op(OpKind kind, const char* name, const int* p, int np, const float* f, int nf, size_t count, const void* in,
@@ -654,6 +671,13 @@ void net_set_fire(saber_hip_net* net, int i, int code);      // api_net_optimize
 bool deconv_form_valid(const saber_hip_deconv* op, int form);      // the form exists for this op
 int deconv_static_form(const saber_hip_deconv* op);      // create's choice: measured rows only (profiles/deconv/README.md), else 0
 void for_each_deconv_form(const saber_hip_deconv* op, const std::function<void(int form)>& fn);      // the autotuner's candidates, form 0 first
+// resizes (api_resize.hip)
+bool resize_form_valid(const saber_hip_resize* op, int form);      // the form exists for this op
+int resize_static_form(const saber_hip_resize* op);      // create's choice (profiles/resize/README.md)
+bool resize_sum_static_on(const saber_hip_resize* op);      // the executor's static choice for a resize + sum site (flag 131072)
+void for_each_resize_form(const saber_hip_resize* op, const std::function<void(int form)>& fn);      // the autotuner's candidates, form 0 first
+int resize_prepare(saber_hip_resize* op);      // the tables on the device (not under stream capture)
+void net_set_resize_sum(saber_hip_net* net, int i, bool on);      // api_net_optimize.hip: the site headed by ops[i] on / off
 // api_chain.hip; y_tail: the tail's output - the tail then runs inside the launch (a stage created with one), null: the blocks only
 // y_head: the second output of the stage's head - the pair then runs inside the launch (a stage created with one), x is the PAIR's input and res is not read
 int stage_run(saber_hip_chain_stage* st, const void* x, const void* res, void* const* y1, void* const* y2, hipStream_t s, void* y_tail = nullptr,

@@ -50,6 +50,7 @@ int net_launch(saber_hip_net* net, const NetOp& o, hipStream_t s) {
         case LAUNCH_SEP: return saber_hip_conv2d_sep_run(o.sep, T(o.in), nullptr, T(o.sep_out), s);      // the depthwise edge stays in LDS
         case LAUNCH_IR: return saber_hip_conv2d_ir_run(o.ir, T(o.in), nullptr, nullptr, T(o.ir_out), s);      // both inner edges stay in LDS
         case LAUNCH_FIRE: return saber_hip_conv2d_fire_run(o.fire, T(o.in), nullptr, T(o.fire_out), s);      // the three inner edges stay in LDS
+        case LAUNCH_RESIZE_SUM:      // (a resize op's launch, never a conv's)
         case LAUNCH_OWN: break;
         }
         if (o.conv->gpool) return saber_hip_conv2d_run_gpool(o.conv, T(o.in), T(o.out), T(o.in2), T(o.out2), s);
@@ -73,6 +74,7 @@ int net_launch(saber_hip_net* net, const NetOp& o, hipStream_t s) {
         return saber_hip_eltwise_sum_i8(o.count, (const int8_t*)T(o.in), (const int8_t*)T(o.in2), o.f[0], o.f[1],
                                         o.f[2], o.f[3], o.p[0], (int8_t*)T(o.out), s);
     case OP_ELT_F32:
+        if (o.skip) return SABER_HIP_OK;      // summed by the resize launch in front of it (flag 131072)
         return saber_hip_eltwise_sum_f32(o.count, (const float*)T(o.in), (const float*)T(o.in2), o.f[0], o.f[1],
                                          o.p[0], (float*)T(o.out), s);
     case OP_POOL_I8:
@@ -100,6 +102,14 @@ int net_launch(saber_hip_net* net, const NetOp& o, hipStream_t s) {
         return saber_hip_concat_nhwc(o.count, (int)o.ins.size(), xs, o.cat_c.data(), o.cat_m.empty() ? nullptr : o.cat_m.data(), o.p[0], T(o.out), s);
     }
     case OP_DECONV: return saber_hip_deconv2d_run(o.deconv, T(o.in), T(o.out), s);
+    case OP_RESIZE: {
+        if (o.launch != LAUNCH_RESIZE_SUM) return saber_hip_resize_run(o.resize, T(o.in), T(o.out), s);
+        // resize + the eltwise behind it in one launch (the ops of a net are contiguous): the resized operand's coefficient first - the sum of
+        // the two products commutes bit for bit
+        const NetOp& e = (&o)[1];
+        const bool first = e.in == o.out;
+        return saber_hip_resize_run_sum(o.resize, T(o.in), T(first ? e.in2 : e.in), e.f[first ? 0 : 1], e.f[first ? 1 : 0], e.p[0], T(e.out), s);
+    }
     }
     return SABER_HIP_UNIMPL;
 }
@@ -287,6 +297,20 @@ int saber_hip_net_add_deconv(saber_hip_net_t* net, saber_hip_deconv_t* op, int i
     o.name = std::string("deconv:") + op->algo_name;
     return push(net, std::move(o));
 }
+int saber_hip_net_add_resize(saber_hip_net_t* net, saber_hip_resize_t* op, int in_id, int out_id) {
+    if (!net || !op) return fail(SABER_HIP_INVALID_VALUE, "null argument");
+    const int nt = (int)net->tensor_bytes.size();
+    if (in_id < 0 || in_id >= nt || out_id < 0 || out_id >= nt || in_id == out_id) return fail(SABER_HIP_INVALID_VALUE, "bad tensor id");
+    const saber_hip_resize_desc& d = op->d;
+    if (net->tensor_bytes[in_id] < (size_t)d.n * d.h * d.w * d.c * 4) return fail(SABER_HIP_INVALID_VALUE, "resize: the input tensor is smaller than n x h x w x c floats");
+    if (net->tensor_bytes[out_id] < (size_t)d.n * op->oh * op->ow * d.c * 4) return fail(SABER_HIP_INVALID_VALUE, "resize: the output tensor is smaller than n x oh x ow x c floats");
+    const int rc = resize_prepare(op);      // the tables reach the device here: a pass may be captured into a hipGraph before it ever ran eagerly
+    if (rc) return rc;
+    NetOp o;
+    o.kind = OP_RESIZE; o.resize = op; o.in = in_id; o.out = out_id;
+    o.name = std::string("resize:") + op->algo_name;
+    return push(net, std::move(o));
+}
 int saber_hip_net_add_softmax(saber_hip_net_t* net, int rows, int cols, int in_id, int out_id) {
     NetOp o;
     o.kind = OP_SOFTMAX; o.in = in_id; o.out = out_id; o.name = "softmax_f32";
@@ -357,6 +381,7 @@ int saber_hip_net_compact_arena(saber_hip_net_t* net, const int* keep, int n_kee
         if (o.stem_pair) span(i, 2);
         if (o.sep) span(i, 2);      // (the one launch reads the depthwise conv's input while it writes the pointwise conv's output)
         if (o.fire) span(i, 4);     // (the one launch reads the squeeze conv's input while it writes the concat's output)
+        if (o.rsum) span(i, 2);     // (the one launch reads the resize's input and the eltwise's other operand while it writes the eltwise's output)
         if (o.ir) span(i, 3);       // (the one launch reads the expand conv's input - the residual too - while it writes the project conv's output)
         if ((o.kind == OP_FC || o.kind == OP_FC_Q) && o.out2 >= 0) span(i, 2);
     }
@@ -524,7 +549,7 @@ int saber_hip_net_set_lane(saber_hip_net_t* net, int index, int lane) {
     if (index < 0 || index >= (int)net->ops.size() || lane < 0 || lane > 1) return fail(SABER_HIP_INVALID_VALUE, "bad op index / lane");
     if (net->lanes_ready) return fail(SABER_HIP_INVALID_VALUE, "lanes are fixed after the first run");
     for (const NetOp& o : net->ops)
-        if (lane && (o.chain || o.chain3 || o.stem_pair || o.sep || o.ir || o.fire))
+        if (lane && (o.chain || o.chain3 || o.stem_pair || o.sep || o.ir || o.fire || o.rsum))
             return fail(SABER_HIP_INVALID_VALUE, "the net has launches that span several ops' tensors (conv1x1 chains, the stem pair, separable sites): lanes must be assigned before saber_hip_net_optimize");
     if (lane) {   // both lanes share the arena's single workspace: an op that uses it stays on the main lane
         const NetOp& o = net->ops[index];
@@ -615,6 +640,13 @@ int saber_hip_net_op_work(const saber_hip_net_t* net, int index, double* bytes, 
         const double wel = (double)d.c * (d.k / d.group) * d.kh * d.kw;
         *bytes = 4.0 * ((double)d.n * d.h * d.w * d.c + (double)d.n * o.deconv->oh * o.deconv->ow * d.k + wel);
         *flops = 2.0 * d.n * d.h * d.w * wel;
+        return SABER_HIP_OK;
+    }
+    case OP_RESIZE: {      // input + output once (+ the output's size again: the fused sum's second operand); 7 flops per output element
+        const saber_hip_resize_desc& d = o.resize->d;
+        const double in_el = (double)d.n * d.h * d.w * d.c, out_el = (double)d.n * o.resize->oh * o.resize->ow * d.c;
+        *bytes = 4.0 * (in_el + out_el + (o.launch == LAUNCH_RESIZE_SUM ? out_el : 0.0));
+        *flops = 7.0 * out_el;
         return SABER_HIP_OK;
     }
     default:
@@ -724,6 +756,8 @@ int saber_hip_net_tensor_unwritten(const saber_hip_net_t* net, int id) {
         if (o.out == id && (o.launch == LAUNCH_IR || (o.skip && by == LAUNCH_IR && (int)(&o - net->ops.data()) == o.absorbed_by + 1))) return 1;
         // the three inner edges of a Fire module while its one launch is selected: the squeeze op's and both expand ops' outputs
         if (o.out == id && o.kind == OP_CONV && (o.launch == LAUNCH_FIRE || (o.skip && by == LAUNCH_FIRE))) return 1;
+        // the resized edge while the resize runs the eltwise behind it (flag 131072)
+        if (o.out == id && o.kind == OP_RESIZE && o.launch == LAUNCH_RESIZE_SUM) return 1;
         // the first block's shortcut while the pair that makes it runs as the stage launch's head: it stays in LDS
         if (o.launch == LAUNCH_STAGE && o.head_on && o.chain3_res == id) return 1;
         // a C = 64 stage's inner block outputs that only the launch reads: they stay in LDS too

@@ -21,6 +21,10 @@ static saber_hip_conv* net_op_conv(saber_hip_net* net, int index) {
 int saber_hip_net_get_choice(saber_hip_net_t* net, int index) {
     if (net && index >= 0 && index < (int)net->ops.size() && net->ops[index].kind == OP_DECONV)
         return (18 << 16) | saber_hip_deconv2d_get_tile(net->ops[index].deconv);      // a deconv op: variant 18, its form code in the low byte
+    if (net && index >= 0 && index < (int)net->ops.size() && net->ops[index].kind == OP_RESIZE) {      // a resize op: variant 19, its form code in the low byte; bit 8: its resize + sum site is on
+        const NetOp& o = net->ops[index];
+        return (19 << 16) | (o.rsum && o.rsum_on ? 1 << 8 : 0) | saber_hip_resize_get_tile(o.resize);
+    }
     saber_hip_conv* c = net_op_conv(net, index);
     int choice = (c && !c->pool_fused && (c->algo <= ALGO_IGEMM_F32 || dw_ok(c) || group_ok(c))) ? saber_hip_conv2d_get_tile(c) : 0;
     if (!c) return choice;
@@ -52,6 +56,15 @@ int saber_hip_net_set_choice(saber_hip_net_t* net, int index, int choice) {
         if (net->reproducible_fp32 || ((choice >> 16) & 0xff) != 18) return SABER_HIP_OK;      // flag 8192: FP32 ops keep the static selection; a word without a deconv decision changes nothing
         const int rc = saber_hip_deconv2d_set_tile(net->ops[index].deconv, choice & 0xffff);
         if (rc) return rc;
+        net_resolve(net);
+        net_drop_graph(net);
+        return SABER_HIP_OK;
+    }
+    if (net && index >= 0 && index < (int)net->ops.size() && net->ops[index].kind == OP_RESIZE) {
+        if (((choice >> 16) & 0xff) != 19) return SABER_HIP_OK;      // a word without a resize decision changes nothing (flag 8192 does not hold it back: every form computes the same bits)
+        const int rc = saber_hip_resize_set_tile(net->ops[index].resize, choice & 0xff);
+        if (rc) return rc;
+        net_set_resize_sum(net, index, (choice >> 8) & 1);      // (resolves; an op that heads no site ignores it)
         net_resolve(net);
         net_drop_graph(net);
         return SABER_HIP_OK;
@@ -250,6 +263,32 @@ int saber_hip_net_autotune(saber_hip_net_t* net, saber_hip_stream_t stream, int 
         if (best_form < 0) return fail(SABER_HIP_RUNTIME_ERROR, "autotune: no form of a deconv op could be timed");
         int rc = saber_hip_deconv2d_set_tile(o.deconv, best_form);
         if (!rc) rc = run();      // the output holds the selected form's result
+        if (rc) return rc;
+    }
+    // resize ops: every form the op accepts, cold L2, on the real tensors; where the op heads a resize + sum site (flag 131072) the one launch
+    // against the two launches, the eltwise included, with every form. All candidates write the same bits: nothing here is held back by flag 8192.
+    for (size_t i = 0; i < net->ops.size(); ++i) {
+        NetOp& o = net->ops[i];
+        if (o.kind != OP_RESIZE) continue;
+        hipStream_t s = (hipStream_t)stream;
+        const bool site = o.rsum && i + 1 < net->ops.size();
+        auto run = [&]() -> int { return net_launch(net, net->ops[i], s) | (site ? net_launch(net, net->ops[i + 1], s) : 0); };
+        float best = 0.f;
+        int best_form = -1;
+        bool best_on = false;
+        for (int on = 0; on <= (site ? 1 : 0); ++on) {
+            if (site) net_set_resize_sum(net, (int)i, on != 0);
+            for_each_resize_form(o.resize, [&](int form) {
+                float us = -1.f;
+                if (saber_hip_resize_set_tile(o.resize, form) != SABER_HIP_OK) return;
+                if (time_enqueued(s, run, 20, &us) != SABER_HIP_OK) return;
+                if (best_form < 0 || us < best) { best = us; best_form = form; best_on = on != 0; }
+            });
+        }
+        if (best_form < 0) return fail(SABER_HIP_RUNTIME_ERROR, "autotune: no form of a resize op could be timed");
+        int rc = saber_hip_resize_set_tile(o.resize, best_form);
+        if (site) net_set_resize_sum(net, (int)i, best_on);
+        if (!rc) rc = run();      // every written output holds the selected form's result
         if (rc) return rc;
     }
     net_resolve(net);      // (the names of the tuned selections)

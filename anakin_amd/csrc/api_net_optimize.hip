@@ -44,6 +44,10 @@ void net_resolve(saber_hip_net* net) {
             for (int j = i + 1; j < n; ++j)
                 if (ops[j].kind == OP_SOFTMAX && ops[j].out == o.out2) { absorb(j, i, IN_CHAIN); break; }
         }
+        if (o.kind == OP_RESIZE && o.rsum && o.rsum_on && i + 1 < n) {      // resize + the eltwise behind it (flag 131072)
+            o.launch = LAUNCH_RESIZE_SUM;
+            absorb(i + 1, i, IN_CHAIN);
+        }
         if (o.kind != OP_CONV || i + 1 >= n) continue;
         if (o.stage && o.stage_on) {
             o.launch = LAUNCH_STAGE;
@@ -84,6 +88,10 @@ void net_resolve(saber_hip_net* net) {
             o.name = "concat" + std::to_string(o.ins.size()) + (o.skip ? " (in the fire launch)" : "");
         } else if (o.kind == OP_DECONV) {
             o.name = std::string("deconv:") + o.deconv->algo_name;
+        } else if (o.kind == OP_RESIZE) {
+            o.name = std::string("resize:") + o.resize->algo_name + (o.launch == LAUNCH_RESIZE_SUM ? "+sum" : "");
+        } else if (o.kind == OP_ELT_F32) {
+            o.name = o.skip ? "eltwise_sum_f32 (in the resize launch)" : "eltwise_sum_f32";
         } else if (o.kind == OP_SOFTMAX) {
             o.name = o.skip ? "softmax_f32 (in the fc launch)" : "softmax_f32";
         } else if (o.kind == OP_FC || o.kind == OP_FC_Q) {
@@ -94,6 +102,7 @@ void net_resolve(saber_hip_net* net) {
             const bool kept = o.stage_name_kept && !o.skip;      // (NetOp::stage_name_kept: shown as it was inside the stage launch)
             switch (kept ? (o.stage ? LAUNCH_STAGE : LAUNCH_NONE) : o.launch) {
             case LAUNCH_NONE: o.name = covered[kept ? IN_STAGE : in[i]]; break;
+            case LAUNCH_RESIZE_SUM:      // (a resize op's launch, never a conv's)
             case LAUNCH_OWN: o.name = "conv:" + own + o.res_note; break;
             case LAUNCH_CHAIN: o.name = "conv:" + chain_form_name(o.chain); break;
             case LAUNCH_CHAIN3: o.name = "conv:" + chain_form_name(o.chain3); break;
@@ -176,6 +185,13 @@ void net_set_fire(saber_hip_net* net, int i, int code) {
     if (!Q.fire || i + 3 >= (int)net->ops.size()) return;
     if (code && saber_hip_conv2d_fire_set_tile(Q.fire, code) != SABER_HIP_OK) code = 0;
     Q.fire_on = code != 0;
+    net_resolve(net);
+}
+// The resize + sum site headed by ops[i] (NetOp::rsum): on -> the resize's launch also sums; off -> the two ops launch on their own again.
+void net_set_resize_sum(saber_hip_net* net, int i, bool on) {
+    NetOp& R = net->ops[i];
+    if (!R.rsum || i + 1 >= (int)net->ops.size()) return;
+    R.rsum_on = on;
     net_resolve(net);
 }
 static int clone_conv_i8(const saber_hip_conv* src, const saber_hip_conv_desc& d, saber_hip_conv** out) {
@@ -465,6 +481,28 @@ int saber_hip_net_optimize(saber_hip_net_t* net, int flags) {
     bool two_lanes = false;
     for (const NetOp& o : ops) two_lanes |= o.lane != 0;
     if (two_lanes) flags &= ~(16 | 32);
+    // ---- 131072 (SABER_HIP_NET_RESIZE_SUM): a lane-0 resize op whose output has exactly one reader, the NEXT op, an eltwise_f32 that takes it as
+    // either operand (FPN's top-down merge) -> a site: the resize's launch also sums, in + 2 x out floats instead of in + 4 x out. Both ops
+    // stay; the eltwise's output keeps its bits (resize.hip rounds the resized value to float before the eltwise expression). Declined: a second
+    // reader of the resized edge, an eltwise that is not the next op, a net with a side lane (the launch reads another op's operand: not ordered
+    // across lanes), an eltwise whose other operand is the resize's own input tensor, an eltwise that writes in place (onto an operand or the
+    // resize's input). Counted: the sites formed (each removes one launch while it is on).
+    if ((flags & SABER_HIP_NET_RESIZE_SUM) && !two_lanes) {
+        for (size_t i = 0; i + 1 < ops.size(); ++i) {
+            NetOp& R = ops[i];
+            NetOp& E = ops[i + 1];
+            if (R.kind != OP_RESIZE || !R.resize || R.rsum || R.skip || R.lane || E.kind != OP_ELT_F32 || E.skip || E.lane) continue;
+            if (op_reads(E, R.out) != 1 || readers(R.out) != 1) continue;
+            const int other = E.in == R.out ? E.in2 : E.in;
+            if (other < 0 || other == R.in || E.out == R.in || E.out == R.out || E.out == other) continue;
+            const saber_hip_resize_desc& d = R.resize->d;
+            if (E.count != (size_t)d.n * R.resize->oh * R.resize->ow * d.c) continue;
+            R.rsum = true;
+            net_set_resize_sum(net, (int)i, resize_sum_static_on(R.resize));
+            ++removed;
+            ++i;
+        }
+    }
     // ---- 65536 (SABER_HIP_NET_FIRE): four consecutive lane-0 ops - a 1x1 squeeze conv, the two convs that alone read it (1x1, then 3x3), the u8
     // concat that alone reads exactly those two, in that order, with all multipliers 1 (SqueezeNet's Fire module) - that
     // saber_hip_conv2d_fire_create accepts -> a site of the one-launch form (conv_fire.hip). All four ops stay; which sites are on is

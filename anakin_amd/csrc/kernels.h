@@ -475,6 +475,31 @@ int deconv_b3_taps(int ks, int (*ab)[2]);      // the stream's [phase][tap] orde
 void deconv_b3_pack(const float* w_ckab, int c, int k, int ks, std::vector<uint8_t>& out);      // [phase][tap][slab][tile][plane][lane] x 16 B
 hipError_t launch_deconv_b3_f32(int form, const DeconvKArgs& a, hipStream_t s);
 
+// FP32 resize (resize.hip). x [N, C, H, W] logical, y [N, C, OH, OW] logical; th / tw: DEVICE tables of OH / OW entries (which input rows /
+// columns an output row / column reads and with which fraction), made on the host by resize_axis_table in the reference's float steps.
+struct ResizeTap {
+    int i0, i1;      // the two taps' indices; i1 >= the input size reads as 0 (RESIZE_CUSTOM); nearest: i0 == i1 = the one tap
+    float frac;      // f - float(i0)
+    int pad;
+};
+struct ResizeKArgs {
+    const float* x;
+    const float* b;      // the fused sum's second operand (the output's shape and layout) or null: y = relu?(c0 * resize(x) + c1 * b)
+    float* y;
+    const ResizeTap* th;
+    const ResizeTap* tw;
+    int N, C, H, W, OH, OW;
+    int nearest, in_nchw, out_nchw, relu;
+    float c0, c1;
+};
+// mode 0 BILINEAR_ALIGN, 1 BILINEAR_NO_ALIGN, 2 RESIZE_CUSTOM (scale = the param's scale unless sizes_given), 3 NEAREST_ALIGN; false: a
+// descriptor the reference cannot run (modes 0 / 3 to one output row, a tap at or beyond the input, no positive scale)
+bool resize_axis_table(int mode, int in, int out, float scale, bool sizes_given, std::vector<ResizeTap>& t);
+bool resize_rows_ok(int c, int in_nchw, int out_nchw);      // form 1: NHWC on both sides, c % 4 == 0
+bool resize_x2_tables_ok(bool nearest, int in, const std::vector<ResizeTap>& t);      // form 2: one axis of an integer x2 whose taps stay within a row of o / 2
+// form 0 resize_direct_f32 (every descriptor), 1 resize_rows_f32, 2 resize_x2_f32; the same bits in all, with and without the fused sum
+hipError_t launch_resize_f32(int form, const ResizeKArgs& a, hipStream_t s);
+
 // reads `bytes` of device memory through every XCD (autotuning: the timed launch then finds none of its operands in
 // an L2, which is how it runs inside the op list)
 hipError_t launch_l2_flush(const void* buf, size_t bytes, unsigned* sink, hipStream_t s);

@@ -15,6 +15,7 @@ NHWC, NCHW = 0, 1
 ACT_NONE, ACT_RELU = 0, 1
 POOL_MAX, POOL_AVG_INCL, POOL_AVG_EXCL = 0, 1, 2
 RES_NONE, RES_SUM_INPLACE, RES_ELTWISE = 0, 1, 2
+BILINEAR_ALIGN, BILINEAR_NO_ALIGN, RESIZE_CUSTOM, NEAREST_ALIGN = 0, 1, 2, 3      # ResizeType (saber/saber_types.h)
 TILES = ["32x32", "64x32", "64x64", "128x64", "64x128", "128x128"]
 
 # every symbol include/saber_hip.h declares (tests/test_abi.py checks the .so exports each one)
@@ -62,6 +63,8 @@ SYMBOLS = [
     "saber_hip_deconv2d_create", "saber_hip_deconv2d_set_weights", "saber_hip_deconv2d_out_shape", "saber_hip_deconv2d_run",
     "saber_hip_deconv2d_algo", "saber_hip_deconv2d_set_tile", "saber_hip_deconv2d_get_tile", "saber_hip_deconv2d_destroy",
     "saber_hip_net_add_deconv",
+    "saber_hip_resize_create", "saber_hip_resize_out_shape", "saber_hip_resize_run", "saber_hip_resize_run_sum", "saber_hip_resize_algo",
+    "saber_hip_resize_set_tile", "saber_hip_resize_get_tile", "saber_hip_resize_destroy", "saber_hip_net_add_resize",
 ]
 
 
@@ -77,6 +80,11 @@ class ConvDesc(C.Structure):
                 ("scale_res", C.c_float), ("int8_weights", C.c_int), ("act_negative_slope", C.c_float),
                 ("res_has_dtype", C.c_int), ("res_dtype", C.c_int), ("res_stride", C.c_int), ("res_h", C.c_int),
                 ("res_w", C.c_int)]
+
+
+class ResizeDesc(C.Structure):
+    _fields_ = [("n", C.c_int), ("c", C.c_int), ("h", C.c_int), ("w", C.c_int), ("mode", C.c_int), ("scale_h", C.c_float), ("scale_w", C.c_float),
+                ("out_h", C.c_int), ("out_w", C.c_int), ("in_layout", C.c_int), ("out_layout", C.c_int), ("dtype", C.c_int)]
 
 
 class FcDesc(C.Structure):
@@ -292,6 +300,18 @@ def load():
     lib.saber_hip_deconv2d_destroy.argtypes = [P]
     lib.saber_hip_deconv2d_destroy.restype = None
     lib.saber_hip_net_add_deconv.argtypes = [P, P, I, I]
+    lib.saber_hip_resize_create.argtypes = [C.POINTER(ResizeDesc), C.POINTER(P)]
+    lib.saber_hip_resize_out_shape.argtypes = [P, C.POINTER(I), C.POINTER(I)]
+    lib.saber_hip_resize_out_shape.restype = None
+    lib.saber_hip_resize_run.argtypes = [P, P, P, P]
+    lib.saber_hip_resize_run_sum.argtypes = [P, P, P, F, F, I, P, P]
+    lib.saber_hip_resize_algo.argtypes = [P]
+    lib.saber_hip_resize_algo.restype = C.c_char_p
+    lib.saber_hip_resize_set_tile.argtypes = [P, I]
+    lib.saber_hip_resize_get_tile.argtypes = [P]
+    lib.saber_hip_resize_destroy.argtypes = [P]
+    lib.saber_hip_resize_destroy.restype = None
+    lib.saber_hip_net_add_resize.argtypes = [P, P, I, I]
     _lib = lib
     return lib
 

@@ -261,6 +261,73 @@ class SaberDeconv2D:
             pass
 
 
+class SaberResize:
+    """SaberResize<MI355X, AK_FLOAT> (saber/funcs/resize.h, ResizeParam): bilinear / nearest resize, FP32 only.
+
+    shape is the NCHW-logical input shape, mode a ResizeType (L.BILINEAR_ALIGN, L.BILINEAR_NO_ALIGN, L.RESIZE_CUSTOM, L.NEAREST_ALIGN). The output
+    size is (out_h, out_w) where both are given, else floor(in * scale). layout: one layout for both sides, or an (in, out) pair."""
+
+    def __init__(self, shape, mode, scale_h=0.0, scale_w=0.0, out_h=-1, out_w=-1, layout=L.NHWC, dtype=L.F32):
+        self.h = C.c_void_p()
+        lib = L.load()
+        d = L.ResizeDesc()
+        d.n, d.c, d.h, d.w = (int(v) for v in shape)
+        d.mode = int(mode)
+        d.scale_h, d.scale_w = float(scale_h), float(scale_w)
+        d.out_h, d.out_w = int(out_h), int(out_w)
+        d.in_layout, d.out_layout = layout if isinstance(layout, (tuple, list)) else (layout, layout)
+        d.dtype = dtype
+        self.desc = d
+        L.check(lib.saber_hip_resize_create(C.byref(d), C.byref(self.h)))
+        oh, ow = C.c_int(), C.c_int()
+        lib.saber_hip_resize_out_shape(self.h, C.byref(oh), C.byref(ow))
+        self.out_hw = (oh.value, ow.value)
+
+    def out_shape(self):
+        d = self.desc
+        oh, ow = self.out_hw
+        return (d.n, oh, ow, d.c) if d.out_layout == L.NHWC else (d.n, d.c, oh, ow)
+
+    def new_output(self):
+        return torch.empty(self.out_shape(), dtype=torch.float32, device="cuda")
+
+    def run(self, x, y):
+        L.check(L.load().saber_hip_resize_run(self.h, _p(x), _p(y), _stream()))
+        return y
+
+    dispatch = run
+
+    def run_sum(self, x, b, y, c0=1.0, c1=1.0, relu=False):
+        """y = relu?(c0 * resize(x) + c1 * b) in one launch; b has the output's shape and layout"""
+        L.check(L.load().saber_hip_resize_run_sum(self.h, _p(x), _p(b), float(c0), float(c1), int(bool(relu)), _p(y), _stream()))
+        return y
+
+    def algo(self):
+        return L.load().saber_hip_resize_algo(self.h).decode()
+
+    def set_tile(self, form):
+        L.check(L.load().saber_hip_resize_set_tile(self.h, int(form)))
+
+    def tile(self):
+        return L.load().saber_hip_resize_get_tile(self.h)
+
+    def forms(self):
+        """every form code this op accepts, form 0 (the direct kernel) first; the selection is left as it was"""
+        cur, ok = self.tile(), []
+        for f in range(3):
+            if L.load().saber_hip_resize_set_tile(self.h, f) == 0:
+                ok.append(f)
+        self.set_tile(cur)
+        return ok
+
+    def __del__(self):
+        try:
+            if self.h:
+                L.load().saber_hip_resize_destroy(self.h)
+        except Exception:
+            pass
+
+
 class SaberConv2DPooling:
     """SaberConv2DPooling<MI355X, AK_INT8> (saber/funcs/conv_pooling.h, ConvPoolingParam): conv followed by pooling.
     One fused kernel where the library has one (saber_hip_conv2d_set_pooling: the ResNet stem + 3x3/2 max pooling);
@@ -999,6 +1066,11 @@ class Net:
         """a SaberDeconv2D inside the op list (saber_hip_net_add_deconv), named deconv:<algo>"""
         self.keep.append(deconv)
         return self._chk(L.load().saber_hip_net_add_deconv(self.h, deconv.h, self.tid(x), self.tid(y)))
+
+    def add_resize(self, resize, x, y):
+        """a SaberResize inside the op list (saber_hip_net_add_resize), named resize:<algo>"""
+        self.keep.append(resize)
+        return self._chk(L.load().saber_hip_net_add_resize(self.h, resize.h, self.tid(x), self.tid(y)))
 
     def add_softmax(self, rows, cols, x, y):
         return self._chk(L.load().saber_hip_net_add_softmax(self.h, rows, cols, self.tid(x), self.tid(y)))

@@ -391,6 +391,53 @@ int saber_hip_deconv2d_set_tile(saber_hip_deconv_t* op, int form);
 int saber_hip_deconv2d_get_tile(const saber_hip_deconv_t* op);
 void saber_hip_deconv2d_destroy(saber_hip_deconv_t* op);
 
+/* ------------------------------------------------------------------------------------------- */
+/* Resize (Resize<T,D>: saber/funcs/resize.h; x86: SaberResize<X86, AK_FLOAT>, saber_resize.cpp), FP32 only */
+/* ------------------------------------------------------------------------------------------- */
+/* Input [n, c, h, w] logical, output [n, c, OH, OW]: OH = out_h, OW = out_w where BOTH are given (not -1), else floor(h * scale_h),
+ * floor(w * scale_w) as a float product (Resize::compute_output_shape). mode is the reference's ResizeType. Per axis, with in / out the sizes
+ * and o the output index, every step in float32:
+ *   0 BILINEAR_ALIGN     s = float(in - 1) / float(out - 1); f = float(o) * s;  i0 = (int)f, i1 = i0 + (i0 < in - 1)
+ *   1 BILINEAR_NO_ALIGN  s = float(in) / float(out); f = max(s * (float(o) + 0.5f) - 0.5f, 0);  taps as mode 0
+ *   2 RESIZE_CUSTOM      s = 1.f / scale, scale = float(out) / float(in) where the sizes are given, else scale_h / scale_w; f = float(o) * s;
+ *                        i0 = (int)f, i1 = i0 + 1, a tap with index >= in reads as 0
+ *   3 NEAREST_ALIGN      s as mode 0; the one tap (int)(double(float(o) * s) + 0.5)
+ * frac = f - float(i0); the four weights are float((1.0 - fh) * (1.0 - fw)), float(fw * (1.0 - fh)), float(fh * (1.0 - fw)), float(fw * fh)
+ * (double products); y = ((w00 * tl + w01 * tr) + w10 * bl) + w11 * br, every product and sum rounded to float32. create computes the per-row
+ * and per-column (i0, i1, frac) on the host in exactly these steps; they reach the device as two tables of OH and OW entries with the first
+ * run or saber_hip_net_add_resize (create itself needs no device). SABER_HIP_INVALID_VALUE: a non-positive size, modes 0 / 3 with an output
+ * dimension of 1 (the reference divides by zero), a table entry with i0 >= in, mode 2 without a positive scale or sizes, an unknown mode or
+ * layout. dtype other than SABER_HIP_F32: SABER_HIP_UNIMPL (the reference instantiates AK_FLOAT alone).
+ * Kernels (anakin_amd/csrc/resize.hip), bit-identical to each other:
+ *   form 0 "resize_direct_f32": every accepted descriptor, NCHW or NHWC on either side, one lane per output element;
+ *   form 1 "resize_rows_f32":   NHWC on both sides, c % 4 == 0: a lane owns a float4 of channels of one output pixel;
+ *   form 2 "resize_x2_f32":     as form 1 and OH = 2 h, OW = 2 w in mode 1 or 3: a lane reads the 3 x 3 neighbourhood of one INPUT pixel once
+ *                               (nearest: the pixel alone) and writes the 2 x 2 output pixels of its cell.
+ * create selects by output size from measured rows (profiles/resize/README.md): form 2 from 3 000 000 output elements, form 1 from 1 000 000,
+ * else form 0; saber_hip_net_autotune times every form the op accepts.
+ * set_tile takes a form code; a code the op is not eligible for returns SABER_HIP_INVALID_VALUE and changes nothing. get_tile returns it.
+ * run_sum: y = relu?(c0 * resize(x) + c1 * b), b of the output's shape and layout, in one launch; resize(x) is rounded to float first and the
+ * sum is saber_hip_eltwise_sum_f32's expression, so the result equals run followed by that call bit for bit. y may be b; neither may
+ * overlap x. */
+typedef struct {
+    int n, c, h, w;
+    int mode;
+    float scale_h, scale_w;
+    int out_h, out_w;      /* -1: from the scale */
+    int in_layout, out_layout;
+    int dtype;
+} saber_hip_resize_desc;
+typedef struct saber_hip_resize saber_hip_resize_t;
+int saber_hip_resize_create(const saber_hip_resize_desc* desc, saber_hip_resize_t** out);
+void saber_hip_resize_out_shape(const saber_hip_resize_t* op, int* oh, int* ow);
+int saber_hip_resize_run(saber_hip_resize_t* op, const void* x, void* y, saber_hip_stream_t stream);
+int saber_hip_resize_run_sum(saber_hip_resize_t* op, const void* x, const void* b, float c0, float c1, int relu, void* y,
+                             saber_hip_stream_t stream);
+const char* saber_hip_resize_algo(const saber_hip_resize_t* op);
+int saber_hip_resize_set_tile(saber_hip_resize_t* op, int form);
+int saber_hip_resize_get_tile(const saber_hip_resize_t* op);
+void saber_hip_resize_destroy(saber_hip_resize_t* op);
+
 /* XCD-resident stage: a run of INT8 convolutions over SMALL feature maps (h * w <= 64 pixels per image: ResNet's res5) as
  * ONE persistent launch. Image i is computed entirely on XCD i % 8 (32 CUs, one workgroup each); the convolutions
  * ("phases") follow each other inside the kernel, separated by an XCD-local barrier where one reads what an earlier one
@@ -665,6 +712,15 @@ int saber_hip_net_add_fc_q(saber_hip_net_t* net, saber_hip_fc_t* op, int in_q_id
  * decision travels in the squeeze op's choice word like a block decision (bit 31 without bit 30, form code in bits 24..27). Apply it before
  * the chain and separable flags: no op belongs to two sites. Returns the number of sites formed. */
 #define SABER_HIP_NET_FIRE 65536
+/* 131072 (SABER_HIP_NET_RESIZE_SUM; NOT in 255, never implied): a lane-0 resize op whose output has exactly one reader, the NEXT op, an
+ * eltwise_f32 that takes it as either operand (FPN's top-down merge), becomes a SITE: one launch resizes and sums (saber_hip_resize_run_sum),
+ * in + 2 x out floats moved instead of in + 4 x out. Both ops stay in the list; while the site is on the eltwise op launches nothing and the
+ * resized edge reports saber_hip_net_tensor_unwritten. The eltwise's output is bit for bit what the two launches write. The site is on by
+ * default; saber_hip_net_autotune times it against the two launches and keeps the faster; the decision travels in the resize op's choice
+ * word (bit 8). No site is formed - and every byte stays what it was - where the resized edge has a second reader, the eltwise is not the
+ * next op, the net has a side lane, the eltwise's other operand is the resize's own input tensor, or the eltwise writes in place. Returns
+ * the number of sites formed. */
+#define SABER_HIP_NET_RESIZE_SUM 131072
 int saber_hip_net_optimize(saber_hip_net_t* net, int flags);
 /* How many cooperative launches of this net have reported a failed pass since it was created (each made saber_hip_net_status /
  * the site's next launch return SABER_HIP_RUNTIME_ERROR once and its site fall back to single-workgroup launches): 0 on a net that
@@ -753,6 +809,12 @@ int saber_hip_net_add_concat(saber_hip_net_t* net, size_t pixels, int n_inputs, 
  * SABER_HIP_NET_REPRODUCIBLE_FP32) and saber_hip_net_get_choice / _set_choice carry the form code as (18 << 16) | form. No
  * saber_hip_net_optimize rewrite touches it. The handle must outlive the net. */
 int saber_hip_net_add_deconv(saber_hip_net_t* net, saber_hip_deconv_t* op, int in_id, int out_id);
+/* saber_hip_resize_run inside an op list, named resize:<algo> ("+sum" behind it while it runs the eltwise behind it, flag 131072). The arena
+ * planner, saber_hip_net_op_work (bytes: input + output, + output again for the fused sum's second operand; 7 flops per output element),
+ * capture / replay, the op-list capture and saber_hip_net_run_op see it; saber_hip_net_autotune times every form the op accepts - under
+ * SABER_HIP_NET_REPRODUCIBLE_FP32 too: all forms compute the same bits - and saber_hip_net_get_choice / _set_choice carry the form code as
+ * (19 << 16) | form, bit 8 set while the op's resize + sum site is on. The handle must outlive the net. */
+int saber_hip_net_add_resize(saber_hip_net_t* net, saber_hip_resize_t* op, int in_id, int out_id);
 /* Caller-owned storage for tensor `id` instead of a slot of the net's arena (the net's inputs and outputs when the caller
  * has buffers of its own: the reference's Net owns its edge tensors). Before finalize any tensor can be bound (ptr != NULL)
  * or returned to the arena (NULL); after finalize only the address of an already external tensor can change. A captured

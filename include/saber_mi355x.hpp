@@ -10,7 +10,7 @@
 //   SoftmaxParam                                         saber/saber_funcs_param.h:48-110,470-677,1077-1140,1236-1279,2085-2153
 //   ImplBase<T, Op, Param>                               saber/funcs/impl/impl_base.h:33-69
 //   SaberConv2D / SaberConvEltwise / SaberConv2DPooling / SaberFc / SaberPooling / SaberEltwise / SaberSoftmax /
-//   SaberActivation / SaberConcat / SaberDeconv2D <MI355X, OpDtype>, Gemm<MI355X>      the per-target specialisations of saber/funcs/impl/<target>/
+//   SaberActivation / SaberConcat / SaberDeconv2D / SaberResize <MI355X, OpDtype>, Gemm<MI355X>      the per-target specialisations of saber/funcs/impl/<target>/
 // As in the reference, weights and bias are TENSORS OF THE TARGET (device memory here); the implementations copy them to
 // the host once per init (saber_mi355x_impl.h: mi355x_host_view). HostBlob below is a convenience that builds such a tensor
 // from host data.
@@ -39,6 +39,7 @@ enum ActiveType { Active_unknow = 0, Active_sigmoid = 1, Active_relu = 2, Active
 enum EltwiseType { Eltwise_unknow = 0, Eltwise_prod = 1, Eltwise_sum = 2, Eltwise_max = 3 };
 enum PoolingType { Pooling_unknow = 0, Pooling_max = 1, Pooling_average_include_padding = 2,
                    Pooling_average_exclude_padding = 3 };   // saber_types.h:305-311
+enum ResizeType { BILINEAR_ALIGN = 0, BILINEAR_NO_ALIGN = 1, RESIZE_CUSTOM = 2, NEAREST_ALIGN = 3 };   // saber_types.h:362-367
 
 inline size_t type_bytes(DataType t) { return t == AK_FLOAT || t == AK_INT32 ? 4 : 1; }
 
@@ -280,6 +281,16 @@ struct ConcatParam {   // saber_funcs_param.h:450-467: axis only
     int axis;
 };
 
+template <typename TargetType>
+struct ResizeParam {   // saber_funcs_param.h:2509-2549: the type, the two scales (width first), the output size (-1: from the scale)
+    ResizeParam() : width_scale(0.f), height_scale(0.f), out_width(-1), out_height(-1), resize_type(BILINEAR_ALIGN) {}
+    explicit ResizeParam(ResizeType type, float scale_w, float scale_h, int out_w = -1, int out_h = -1)
+        : width_scale(scale_w), height_scale(scale_h), out_width(out_w), out_height(out_h), resize_type(type) {}
+    float width_scale, height_scale;
+    int out_width, out_height;
+    ResizeType resize_type;
+};
+
 }  // namespace saber
 }  // namespace anakin
 
@@ -338,6 +349,8 @@ template <typename TargetType, DataType OpDtype>
 using SaberConcat = SaberConcatMI355X<TargetType, OpDtype>;
 template <typename TargetType, DataType OpDtype>
 using SaberDeconv2D = SaberDeconv2DMI355X<TargetType, OpDtype>;
+template <typename TargetType, DataType OpDtype>
+using SaberResize = SaberResizeMI355X<TargetType, OpDtype>;
 template <typename TargetType, DataType OpDtype>
 using SaberActivation = SaberActivationMI355X<TargetType, OpDtype>;
 template <typename TargetType>

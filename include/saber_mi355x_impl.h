@@ -527,6 +527,57 @@ private:
     saber_hip_deconv_t* _op;
 };
 
+// SaberResize<MI355X, AK_FLOAT> (saber/funcs/resize.h; x86: saber_resize.cpp, the four ResizeType modes). One input: the reference's second
+// input, a tensor that carries the output size, is not supported (SaberUnImplError). The output tensor must have the shape
+// Resize::compute_output_shape gives it. OpDtype other than AK_FLOAT: SaberUnImplError (the x86 file instantiates AK_FLOAT alone).
+template <typename TargetType, DataType OpDtype>
+class SaberResizeMI355X : public ImplBase<TargetType, OpDtype, ResizeParam<TargetType> > {
+public:
+    SaberResizeMI355X() : _op(nullptr) {}
+    ~SaberResizeMI355X() {
+        if (_op) saber_hip_resize_destroy(_op);
+    }
+    virtual SaberStatus init(const std::vector<Tensor<TargetType>*>& inputs, std::vector<Tensor<TargetType>*>& outputs,
+                             ResizeParam<TargetType>& param, Context<TargetType>& ctx) {
+        this->_ctx = &ctx;
+        return create(inputs, outputs, param, ctx);
+    }
+    virtual SaberStatus create(const std::vector<Tensor<TargetType>*>& inputs, std::vector<Tensor<TargetType>*>& outputs,
+                               ResizeParam<TargetType>& param, Context<TargetType>& ctx) {
+        this->_ctx = &ctx;
+        if (OpDtype != AK_FLOAT || inputs.size() != 1) return SaberUnImplError;
+        Tensor<TargetType>* in = inputs[0];
+        Tensor<TargetType>* out = outputs[0];
+        saber_hip_resize_desc d;
+        memset(&d, 0, sizeof d);
+        d.n = in->num(); d.c = in->channel(); d.h = in->height(); d.w = in->width();
+        d.mode = (int)param.resize_type;
+        d.scale_h = param.height_scale; d.scale_w = param.width_scale;
+        d.out_h = param.out_height; d.out_w = param.out_width;
+        d.in_layout = mi355x_layout(in->get_layout());
+        d.out_layout = mi355x_layout(out->get_layout());
+        d.dtype = in->get_dtype() == AK_FLOAT && out->get_dtype() == AK_FLOAT ? SABER_HIP_F32 : mi355x_dtype(AK_INT8);
+        if (_op) { saber_hip_resize_destroy(_op); _op = nullptr; }
+        int rc = saber_hip_resize_create(&d, &_op);
+        if (rc) return mi355x_status(rc);
+        int oh = 0, ow = 0;
+        saber_hip_resize_out_shape(_op, &oh, &ow);
+        if (out->num() != d.n || out->channel() != d.c || out->height() != oh || out->width() != ow) return SaberInvalidValue;
+        return SaberSuccess;
+    }
+    virtual SaberStatus dispatch(const std::vector<Tensor<TargetType>*>& inputs, std::vector<Tensor<TargetType>*>& outputs,
+                                 ResizeParam<TargetType>& param) {
+        if (!_op) return SaberNotInitialized;      // (a failed create() is not reported by BaseFunc::init: see SaberConvEltwiseMI355X::dispatch)
+        return mi355x_status(saber_hip_resize_run(_op, inputs[0]->data(), outputs[0]->mutable_data(),
+                                                  (saber_hip_stream_t)this->_ctx->get_compute_stream()));
+    }
+    const char* algo() const { return _op ? saber_hip_resize_algo(_op) : ""; }
+    int set_tile(int form) { return _op ? saber_hip_resize_set_tile(_op, form) : SABER_HIP_INVALID_VALUE; }
+
+private:
+    saber_hip_resize_t* _op;
+};
+
 // Concat<MI355X, OpDtype> (saber/funcs/concat.h; x86: saber_concat.cpp) along the channel axis of 1 .. 8 tensors of one dtype:
 // NHWC (axis 3: the 8-bit edges and the target's FP32 edges) or any layout whose pixels collapse to one (NCHW [n, c, 1, 1], axis 1).
 // f32 and s8: a copy. u8: the x86 create's loops as they are written (saber_concat.cpp:163-201) - scale_max starts at the first

@@ -15,3 +15,4 @@ template class anakin::saber::SaberGemmMI355X<X86>;
 template class anakin::saber::SaberConcatMI355X<X86, AK_INT8>;
 template class anakin::saber::SaberConcatMI355X<X86, AK_FLOAT>;
 template class anakin::saber::SaberDeconv2DMI355X<X86, AK_FLOAT>;
+template class anakin::saber::SaberResizeMI355X<X86, AK_FLOAT>;
