@@ -157,6 +157,20 @@ int capture_resize(saber_hip_resize* op, const void* x, void* y) {      // (the 
     return SABER_HIP_OK;
 }
 
+int capture_detout(saber_hip_detout* op, const void* loc, const void* conf, const void* prior, void* y, void* count) {      // (checked by saber_hip_detout_run)
+    Capture& c = *g_capture;
+    const saber_hip_detout_desc& d = op->d;
+    const int l = c.read(loc, (size_t)d.n * d.priors * 4 * 4);
+    const int s = c.read(conf, (size_t)d.n * d.priors * d.classes * 4);
+    const int p = prior ? c.read(prior, (size_t)2 * d.priors * 4 * 4) : -1;
+    const int out = c.write(y, (size_t)d.n * d.keep_top_k * 7 * 4);
+    const int cnt = c.write(count, (size_t)(1 + d.n) * 4);
+    if (c.failed || l < 0 || s < 0 || (prior && p < 0) || out < 0 || cnt < 0) return c.bad("bad tensor");
+    if (saber_hip_net_add_detout(c.net, op, l, s, p, out, cnt) < 0) return c.bad("saber_hip_net_add_detout failed");
+    ++c.ops;
+    return SABER_HIP_OK;
+}
+
 int capture_fc(saber_hip_fc* fc, const void* x, float* y, bool quantised_input) {
     Capture& c = *g_capture;
     if (!fc || !x || !y) return fail(SABER_HIP_INVALID_VALUE, "null argument");

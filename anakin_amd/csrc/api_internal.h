@@ -14,6 +14,7 @@
 //   api_gemm.hip          FP32 GEMM on the bf16-plane kernels (device-side plane split, per-thread plan cache)
 //   api_deconv.hip        transposed convolution (FP32): create / set_weights (repack + fragment stream) / run, its forms and static rule
 //   api_resize.hip        resize (FP32): create (the host index / fraction tables) / run / run_sum, its forms and static rule
+//   api_detout.hip        DetectionOutput (FP32): create / run (the op's scratch), its forms and static rule
 //   api_capture.hip       op-list capture: the *_run calls of a caller's own op loop recorded into a saber_hip_net
 #pragma once
 #include "../../include/saber_hip.h"
@@ -334,6 +335,17 @@ struct saber_hip_resize {
     std::string algo_name;
 };
 
+// a DetectionOutput (api_detout.hip, detout.hip): FP32 only, a type of its own
+struct saber_hip_detout {
+    saber_hip_detout_desc d;
+    int form = 0;            // 0: detout_direct_f32; 1: detout_mask_f32 (written by detout_set_form only)
+    // the kept candidates of every (image, class) between the two launches; on the device from the first run or saber_hip_net_add_detout on
+    DevBuf<int> d_cnt;
+    DevBuf<uint2> d_key;
+    DevBuf<float4> d_box;
+    std::string algo_name;
+};
+
 struct saber_hip_fc {
     saber_hip_fc_desc d;
     saber_hip_conv* conv = nullptr;
@@ -436,7 +448,7 @@ struct ColdScope {
 
 // op-list executor
 namespace saber_api {
-enum OpKind { OP_CONV, OP_CONV_PAIR, OP_FC, OP_QUANT, OP_DEQUANT, OP_TRANSPOSE_IN, OP_ELT_I8, OP_ELT_F32, OP_POOL_I8, OP_POOL_F32, OP_POOL_F32_I8, OP_FC_Q, OP_SOFTMAX, OP_RELU_F32, OP_ACT_F32, OP_CONCAT, OP_DECONV, OP_RESIZE };
+enum OpKind { OP_CONV, OP_CONV_PAIR, OP_FC, OP_QUANT, OP_DEQUANT, OP_TRANSPOSE_IN, OP_ELT_I8, OP_ELT_F32, OP_POOL_I8, OP_POOL_F32, OP_POOL_F32_I8, OP_FC_Q, OP_SOFTMAX, OP_RELU_F32, OP_ACT_F32, OP_CONCAT, OP_DECONV, OP_RESIZE, OP_DETOUT };
 // What an op launches in the current selection: DERIVED from the sites' decisions by net_resolve (api_net_optimize.hip), never set elsewhere
 enum Launch { LAUNCH_NONE, LAUNCH_OWN, LAUNCH_CHAIN, LAUNCH_CHAIN3, LAUNCH_STAGE, LAUNCH_STEM_PAIR, LAUNCH_SEP, LAUNCH_IR, LAUNCH_FIRE, LAUNCH_RESIZE_SUM };
 // A SITE is a group of adjacent ops that can run as one launch. The op that heads a site holds the site's object and its DECISION (*_on: stored
@@ -450,6 +462,7 @@ struct NetOp {
     saber_hip_fc* fc = nullptr;
     saber_hip_deconv* deconv = nullptr;      // OP_DECONV
     saber_hip_resize* resize = nullptr;      // OP_RESIZE
+    saber_hip_detout* detout = nullptr;      // OP_DETOUT: ins = {loc, conf[, prior]}, out = y, out2 = count
     int in = -1, in2 = -1, out = -1, out2 = -1;
     // OP_CONCAT: EVERY input id in channel order (in = ins[0], in2 stays -1), their channel counts in elements and - u8 with rescaling - the
     // per-input multipliers (empty: a copy). Whatever asks which tensors an op reads goes through op_for_each_input / op_reads below.
@@ -522,10 +535,10 @@ struct NetOp {
     float f[6] = {0};
     size_t count = 0;
 };
-// the tensors an op READS as operands (a concat: its whole input list; every other kind: in and in2)
+// the tensors an op READS as operands (a concat, a detout: the whole input list; every other kind: in and in2)
 template <typename F>
 inline void op_for_each_input(const NetOp& o, F&& f) {
-    if (o.kind == OP_CONCAT) {
+    if (o.kind == OP_CONCAT || o.kind == OP_DETOUT) {
         for (int t : o.ins) f(t);
         return;
     }
@@ -593,6 +606,7 @@ int capture_fc(saber_hip_fc* fc, const void* x, float* y, bool quantised_input);
 int capture_unsupported(const char* what);
 int capture_deconv(saber_hip_deconv* op, const void* x, void* y);
 int capture_resize(saber_hip_resize* op, const void* x, void* y);
+int capture_detout(saber_hip_detout* op, const void* loc, const void* conf, const void* prior, void* y, void* count);
 int capture_concat(size_t pixels, int n_inputs, const void* const* xs, const int* channels, const float* mult, int dtype, void* y);
 // streaming ops: kind + the argument block of the matching saber_hip_net_add_* call; in2 / out2 may be null
 int capture_stream_op(OpKind kind, const char* name, const int* p, int np, const float* f, int nf, size_t count, const void* in,
@@ -678,6 +692,11 @@ bool resize_sum_static_on(const saber_hip_resize* op);      // the executor's st
 void for_each_resize_form(const saber_hip_resize* op, const std::function<void(int form)>& fn);      // the autotuner's candidates, form 0 first
 int resize_prepare(saber_hip_resize* op);      // the tables on the device (not under stream capture)
 void net_set_resize_sum(saber_hip_net* net, int i, bool on);      // api_net_optimize.hip: the site headed by ops[i] on / off
+// detection outputs (api_detout.hip)
+bool detout_form_valid(const saber_hip_detout* op, int form);      // the form exists for this op
+int detout_static_form(const saber_hip_detout* op);      // create's choice (profiles/detout/README.md)
+void for_each_detout_form(const saber_hip_detout* op, const std::function<void(int form)>& fn);      // the autotuner's candidates, form 0 first
+int detout_prepare(saber_hip_detout* op);      // the scratch on the device (not under stream capture)
 // api_chain.hip; y_tail: the tail's output - the tail then runs inside the launch (a stage created with one), null: the blocks only
 // y_head: the second output of the stage's head - the pair then runs inside the launch (a stage created with one), x is the PAIR's input and res is not read
 int stage_run(saber_hip_chain_stage* st, const void* x, const void* res, void* const* y1, void* const* y2, hipStream_t s, void* y_tail = nullptr,

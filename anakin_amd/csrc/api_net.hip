@@ -102,6 +102,8 @@ int net_launch(saber_hip_net* net, const NetOp& o, hipStream_t s) {
         return saber_hip_concat_nhwc(o.count, (int)o.ins.size(), xs, o.cat_c.data(), o.cat_m.empty() ? nullptr : o.cat_m.data(), o.p[0], T(o.out), s);
     }
     case OP_DECONV: return saber_hip_deconv2d_run(o.deconv, T(o.in), T(o.out), s);
+    case OP_DETOUT:
+        return saber_hip_detout_run(o.detout, T(o.ins[0]), T(o.ins[1]), o.ins.size() > 2 ? T(o.ins[2]) : nullptr, T(o.out), T(o.out2), s);
     case OP_RESIZE: {
         if (o.launch != LAUNCH_RESIZE_SUM) return saber_hip_resize_run(o.resize, T(o.in), T(o.out), s);
         // resize + the eltwise behind it in one launch (the ops of a net are contiguous): the resized operand's coefficient first - the sum of
@@ -309,6 +311,32 @@ int saber_hip_net_add_resize(saber_hip_net_t* net, saber_hip_resize_t* op, int i
     NetOp o;
     o.kind = OP_RESIZE; o.resize = op; o.in = in_id; o.out = out_id;
     o.name = std::string("resize:") + op->algo_name;
+    return push(net, std::move(o));
+}
+int saber_hip_net_add_detout(saber_hip_net_t* net, saber_hip_detout_t* op, int loc_id, int conf_id, int prior_id, int y_id, int count_id) {
+    if (!net || !op) return fail(SABER_HIP_INVALID_VALUE, "null argument");
+    const int nt = (int)net->tensor_bytes.size();
+    const saber_hip_detout_desc& d = op->d;
+    if ((d.has_prior != 0) != (prior_id >= 0)) return fail(SABER_HIP_INVALID_VALUE, "detout: a prior tensor is given exactly where the op was created with has_prior");
+    const int ids[5] = {loc_id, conf_id, prior_id, y_id, count_id};
+    for (int k = 0; k < 5; ++k) {
+        if (k == 2 && prior_id < 0) continue;
+        if (ids[k] < 0 || ids[k] >= nt) return fail(SABER_HIP_INVALID_VALUE, "bad tensor id");
+        for (int j = 0; j < k; ++j)
+            if (ids[j] == ids[k]) return fail(SABER_HIP_INVALID_VALUE, "detout: the five tensors are distinct");
+    }
+    if (net->tensor_bytes[loc_id] < (size_t)d.n * d.priors * 16) return fail(SABER_HIP_INVALID_VALUE, "detout: the loc tensor is smaller than n x priors x 4 floats");
+    if (net->tensor_bytes[conf_id] < (size_t)d.n * d.priors * d.classes * 4) return fail(SABER_HIP_INVALID_VALUE, "detout: the conf tensor is smaller than n x priors x classes floats");
+    if (prior_id >= 0 && net->tensor_bytes[prior_id] < (size_t)d.priors * 32) return fail(SABER_HIP_INVALID_VALUE, "detout: the prior tensor is smaller than 2 x priors x 4 floats");
+    if (net->tensor_bytes[y_id] < (size_t)d.n * d.keep_top_k * 28) return fail(SABER_HIP_INVALID_VALUE, "detout: the output tensor is smaller than n x keep_top_k x 7 floats");
+    if (net->tensor_bytes[count_id] < (size_t)(1 + d.n) * 4) return fail(SABER_HIP_INVALID_VALUE, "detout: the count tensor is smaller than 1 + n int32");
+    const int rc = detout_prepare(op);      // the scratch is allocated here: a pass may be captured into a hipGraph before it ever ran eagerly
+    if (rc) return rc;
+    NetOp o;
+    o.kind = OP_DETOUT; o.detout = op; o.in = loc_id; o.out = y_id; o.out2 = count_id;
+    o.ins = {loc_id, conf_id};
+    if (prior_id >= 0) o.ins.push_back(prior_id);
+    o.name = std::string("detout:") + op->algo_name;
     return push(net, std::move(o));
 }
 int saber_hip_net_add_softmax(saber_hip_net_t* net, int rows, int cols, int in_id, int out_id) {
@@ -640,6 +668,14 @@ int saber_hip_net_op_work(const saber_hip_net_t* net, int index, double* bytes, 
         const double wel = (double)d.c * (d.k / d.group) * d.kh * d.kw;
         *bytes = 4.0 * ((double)d.n * d.h * d.w * d.c + (double)d.n * o.deconv->oh * o.deconv->ow * d.k + wel);
         *flops = 2.0 * d.n * d.h * d.w * wel;
+        return SABER_HIP_OK;
+    }
+    case OP_DETOUT: {      // every score once, the survivors' loc / prior entries, the kept candidates out and in again, the output; one
+        // overlap (~20 flops) per pair of survivors at most
+        const saber_hip_detout_desc& d = o.detout->d;
+        const double cls = (double)d.n * d.classes, k = d.nms_top_k;
+        *bytes = 4.0 * d.n * d.priors * d.classes + cls * k * (d.has_prior ? 48.0 : 16.0) + 2.0 * cls * k * 24.0 + 28.0 * d.n * d.keep_top_k;
+        *flops = 20.0 * cls * k * k / 2.0;
         return SABER_HIP_OK;
     }
     case OP_RESIZE: {      // input + output once (+ the output's size again: the fused sum's second operand); 7 flops per output element

@@ -21,6 +21,8 @@ static saber_hip_conv* net_op_conv(saber_hip_net* net, int index) {
 int saber_hip_net_get_choice(saber_hip_net_t* net, int index) {
     if (net && index >= 0 && index < (int)net->ops.size() && net->ops[index].kind == OP_DECONV)
         return (18 << 16) | saber_hip_deconv2d_get_tile(net->ops[index].deconv);      // a deconv op: variant 18, its form code in the low byte
+    if (net && index >= 0 && index < (int)net->ops.size() && net->ops[index].kind == OP_DETOUT)
+        return (20 << 16) | saber_hip_detout_get_tile(net->ops[index].detout);      // a detout op: variant 20, its form code in the low byte
     if (net && index >= 0 && index < (int)net->ops.size() && net->ops[index].kind == OP_RESIZE) {      // a resize op: variant 19, its form code in the low byte; bit 8: its resize + sum site is on
         const NetOp& o = net->ops[index];
         return (19 << 16) | (o.rsum && o.rsum_on ? 1 << 8 : 0) | saber_hip_resize_get_tile(o.resize);
@@ -55,6 +57,14 @@ int saber_hip_net_set_choice(saber_hip_net_t* net, int index, int choice) {
     if (net && index >= 0 && index < (int)net->ops.size() && net->ops[index].kind == OP_DECONV) {
         if (net->reproducible_fp32 || ((choice >> 16) & 0xff) != 18) return SABER_HIP_OK;      // flag 8192: FP32 ops keep the static selection; a word without a deconv decision changes nothing
         const int rc = saber_hip_deconv2d_set_tile(net->ops[index].deconv, choice & 0xffff);
+        if (rc) return rc;
+        net_resolve(net);
+        net_drop_graph(net);
+        return SABER_HIP_OK;
+    }
+    if (net && index >= 0 && index < (int)net->ops.size() && net->ops[index].kind == OP_DETOUT) {
+        if (((choice >> 16) & 0xff) != 20) return SABER_HIP_OK;      // a word without a detout decision changes nothing (flag 8192 does not hold it back: both forms compute the same bits)
+        const int rc = saber_hip_detout_set_tile(net->ops[index].detout, choice & 0xff);
         if (rc) return rc;
         net_resolve(net);
         net_drop_graph(net);
@@ -289,6 +299,25 @@ int saber_hip_net_autotune(saber_hip_net_t* net, saber_hip_stream_t stream, int 
         int rc = saber_hip_resize_set_tile(o.resize, best_form);
         if (site) net_set_resize_sum(net, (int)i, best_on);
         if (!rc) rc = run();      // every written output holds the selected form's result
+        if (rc) return rc;
+    }
+    // detout ops: both forms where the op accepts both, on the real tensors. The forms write the same bits: nothing here is held back by flag 8192.
+    for (size_t i = 0; i < net->ops.size(); ++i) {
+        NetOp& o = net->ops[i];
+        if (o.kind != OP_DETOUT) continue;
+        hipStream_t s = (hipStream_t)stream;
+        auto run = [&]() -> int { return net_launch(net, net->ops[i], s); };
+        float best = 0.f;
+        int best_form = -1;
+        for_each_detout_form(o.detout, [&](int form) {
+            float us = -1.f;
+            if (saber_hip_detout_set_tile(o.detout, form) != SABER_HIP_OK) return;
+            if (time_enqueued(s, run, 20, &us) != SABER_HIP_OK) return;
+            if (best_form < 0 || us < best) { best = us; best_form = form; }
+        });
+        if (best_form < 0) return fail(SABER_HIP_RUNTIME_ERROR, "autotune: no form of a detout op could be timed");
+        int rc = saber_hip_detout_set_tile(o.detout, best_form);
+        if (!rc) rc = run();      // both outputs hold the selected form's result
         if (rc) return rc;
     }
     net_resolve(net);      // (the names of the tuned selections)

@@ -86,6 +86,8 @@ void net_resolve(saber_hip_net* net) {
         o.skip = o.launch == LAUNCH_NONE;
         if (o.kind == OP_CONCAT) {
             o.name = "concat" + std::to_string(o.ins.size()) + (o.skip ? " (in the fire launch)" : "");
+        } else if (o.kind == OP_DETOUT) {
+            o.name = std::string("detout:") + o.detout->algo_name;
         } else if (o.kind == OP_DECONV) {
             o.name = std::string("deconv:") + o.deconv->algo_name;
         } else if (o.kind == OP_RESIZE) {

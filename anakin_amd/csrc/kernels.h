@@ -500,6 +500,30 @@ bool resize_x2_tables_ok(bool nearest, int in, const std::vector<ResizeTap>& t);
 // form 0 resize_direct_f32 (every descriptor), 1 resize_rows_f32, 2 resize_x2_f32; the same bits in all, with and without the fused sum
 hipError_t launch_resize_f32(int form, const ResizeKArgs& a, hipStream_t s);
 
+// FP32 DetectionOutput (detout.hip): box decode, per-class NMS and the per-image keep_top_k cut in two launches, fixed-shape output.
+constexpr int DETOUT_SORT_CAP = 4096;            // 64-bit keys one workgroup sorts in LDS at a time (both forms, and the per-image cut)
+constexpr int DETOUT_MAX_NMS_TOP_K = 1024;       // the survivors of one (image, class): boxes, and form 1's K x K / 64 bit matrix, stay in LDS
+constexpr size_t DETOUT_LDS_LIMIT = 160 * 1024 - 64;
+struct DetoutKArgs {
+    const float* loc;        // [N, P * 4]: the predictions (prior != null) or decoded boxes
+    const float* conf;       // prior != null: [N, P, C] (what the softmax writes); else [N, C, P]
+    const float* prior;      // [2, P * 4]: boxes, then variances; or null
+    float* y;                // [N * keep, 7]
+    int* count;              // [1 + N]
+    int* cls_cnt;            // scratch [N * C]: how many candidates NMS kept per (image, class)
+    uint2* cls_key;          // scratch [N * C * K]: their score bits and prior index, in the order they were kept
+    float4* cls_box;         // scratch [N * C * K]: their boxes
+    int N, C, P, K, keep, bg;      // K = nms_top_k
+    int code, vit;           // CodeType 1 CORNER, 2 CENTER_SIZE, 3 CORNER_SIZE; variance_encode_in_target
+    float conf_t, nms_t, eta;
+    int region0;             // (set by the launcher)
+};
+// the per-image cut selects in LDS: keep_top_k fits beside one step of new keys, or is so large that no image can exceed it
+inline bool detout_keep_fits(int C, int K, long long keep) { return keep <= DETOUT_SORT_CAP - 1024 || keep >= (long long)C * K; }
+size_t detout_lds_bytes(int form, int K);      // dynamic LDS of launch 1
+// form 0 detout_direct_f32 (any eta), 1 detout_mask_f32 (eta == 1); then detout_pack_f32. The same bits from both forms.
+hipError_t launch_detout_f32(int form, const DetoutKArgs& a, hipStream_t s);
+
 // reads `bytes` of device memory through every XCD (autotuning: the timed launch then finds none of its operands in
 // an L2, which is how it runs inside the op list)
 hipError_t launch_l2_flush(const void* buf, size_t bytes, unsigned* sink, hipStream_t s);

@@ -16,6 +16,7 @@ ACT_NONE, ACT_RELU = 0, 1
 POOL_MAX, POOL_AVG_INCL, POOL_AVG_EXCL = 0, 1, 2
 RES_NONE, RES_SUM_INPLACE, RES_ELTWISE = 0, 1, 2
 BILINEAR_ALIGN, BILINEAR_NO_ALIGN, RESIZE_CUSTOM, NEAREST_ALIGN = 0, 1, 2, 3      # ResizeType (saber/saber_types.h)
+CORNER, CENTER_SIZE, CORNER_SIZE = 1, 2, 3      # CodeType (saber/saber_types.h)
 TILES = ["32x32", "64x32", "64x64", "128x64", "64x128", "128x128"]
 
 # every symbol include/saber_hip.h declares (tests/test_abi.py checks the .so exports each one)
@@ -65,6 +66,8 @@ SYMBOLS = [
     "saber_hip_net_add_deconv",
     "saber_hip_resize_create", "saber_hip_resize_out_shape", "saber_hip_resize_run", "saber_hip_resize_run_sum", "saber_hip_resize_algo",
     "saber_hip_resize_set_tile", "saber_hip_resize_get_tile", "saber_hip_resize_destroy", "saber_hip_net_add_resize",
+    "saber_hip_detout_create", "saber_hip_detout_out_rows", "saber_hip_detout_run", "saber_hip_detout_read_total", "saber_hip_detout_algo", "saber_hip_detout_set_tile",
+    "saber_hip_detout_get_tile", "saber_hip_detout_destroy", "saber_hip_net_add_detout",
 ]
 
 
@@ -85,6 +88,12 @@ class ConvDesc(C.Structure):
 class ResizeDesc(C.Structure):
     _fields_ = [("n", C.c_int), ("c", C.c_int), ("h", C.c_int), ("w", C.c_int), ("mode", C.c_int), ("scale_h", C.c_float), ("scale_w", C.c_float),
                 ("out_h", C.c_int), ("out_w", C.c_int), ("in_layout", C.c_int), ("out_layout", C.c_int), ("dtype", C.c_int)]
+
+
+class DetoutDesc(C.Structure):
+    _fields_ = [(n, C.c_int) for n in ("n", "classes", "priors", "code_type", "variance_in_target", "has_prior", "share_location", "background_id",
+                                       "keep_top_k", "nms_top_k")] + \
+               [("conf_thresh", C.c_float), ("nms_thresh", C.c_float), ("nms_eta", C.c_float), ("dtype", C.c_int)]
 
 
 class FcDesc(C.Structure):
@@ -312,6 +321,17 @@ def load():
     lib.saber_hip_resize_destroy.argtypes = [P]
     lib.saber_hip_resize_destroy.restype = None
     lib.saber_hip_net_add_resize.argtypes = [P, P, I, I]
+    lib.saber_hip_detout_create.argtypes = [C.POINTER(DetoutDesc), C.POINTER(P)]
+    lib.saber_hip_detout_out_rows.argtypes = [P]
+    lib.saber_hip_detout_run.argtypes = [P, P, P, P, P, P, P]
+    lib.saber_hip_detout_read_total.argtypes = [P, P, C.POINTER(I)]
+    lib.saber_hip_detout_algo.argtypes = [P]
+    lib.saber_hip_detout_algo.restype = C.c_char_p
+    lib.saber_hip_detout_set_tile.argtypes = [P, I]
+    lib.saber_hip_detout_get_tile.argtypes = [P]
+    lib.saber_hip_detout_destroy.argtypes = [P]
+    lib.saber_hip_detout_destroy.restype = None
+    lib.saber_hip_net_add_detout.argtypes = [P, P, I, I, I, I, I]
     _lib = lib
     return lib
 

@@ -328,6 +328,66 @@ class SaberResize:
             pass
 
 
+class SaberDetectionOutput:
+    """SaberDetectionOutput<MI355X, AK_FLOAT> (saber/funcs/detection_output.h, DetectionOutputParam): box decode, per-class NMS and the
+    per-image keep_top_k cut on the device, FP32 only.
+
+    With prior=True (SSD) run takes loc [n, priors * 4], conf [n, priors, classes] and prior [2, priors * 4]; with prior=False loc holds
+    decoded boxes, conf is [n, classes, priors] and no prior is passed. The output has a fixed shape: y [n * keep_top_k, 7], the kept rows
+    packed from row 0 and every later row -1; count int32 [1 + n], the total and the rows per image."""
+
+    def __init__(self, n, classes, priors, keep_top_k, nms_top_k, conf_thresh, nms_thresh=0.3, background_id=0, code_type=L.CORNER,
+                 variance_in_target=False, prior=True, nms_eta=1.0, share_location=True, dtype=L.F32):
+        self.h = C.c_void_p()
+        d = L.DetoutDesc()
+        d.n, d.classes, d.priors = int(n), int(classes), int(priors)
+        d.code_type, d.variance_in_target, d.has_prior = int(code_type), int(bool(variance_in_target)), int(bool(prior))
+        d.share_location, d.background_id = int(bool(share_location)), int(background_id)
+        d.keep_top_k, d.nms_top_k = int(keep_top_k), int(nms_top_k)
+        d.conf_thresh, d.nms_thresh, d.nms_eta = float(conf_thresh), float(nms_thresh), float(nms_eta)
+        d.dtype = dtype
+        self.desc = d
+        L.check(L.load().saber_hip_detout_create(C.byref(d), C.byref(self.h)))
+
+    def out_rows(self):
+        return L.load().saber_hip_detout_out_rows(self.h)
+
+    def new_outputs(self):
+        return (torch.empty((self.out_rows(), 7), dtype=torch.float32, device="cuda"),
+                torch.empty((1 + self.desc.n,), dtype=torch.int32, device="cuda"))
+
+    def run(self, loc, conf, prior, y, count):
+        L.check(L.load().saber_hip_detout_run(self.h, _p(loc), _p(conf), None if prior is None else _p(prior), _p(y), _p(count), _stream()))
+        return y, count
+
+    dispatch = run
+
+    def algo(self):
+        return L.load().saber_hip_detout_algo(self.h).decode()
+
+    def set_tile(self, form):
+        L.check(L.load().saber_hip_detout_set_tile(self.h, int(form)))
+
+    def tile(self):
+        return L.load().saber_hip_detout_get_tile(self.h)
+
+    def forms(self):
+        """every form code this op accepts, form 0 first; the selection is left as it was"""
+        cur, ok = self.tile(), []
+        for f in range(2):
+            if L.load().saber_hip_detout_set_tile(self.h, f) == 0:
+                ok.append(f)
+        self.set_tile(cur)
+        return ok
+
+    def __del__(self):
+        try:
+            if self.h:
+                L.load().saber_hip_detout_destroy(self.h)
+        except Exception:
+            pass
+
+
 class SaberConv2DPooling:
     """SaberConv2DPooling<MI355X, AK_INT8> (saber/funcs/conv_pooling.h, ConvPoolingParam): conv followed by pooling.
     One fused kernel where the library has one (saber_hip_conv2d_set_pooling: the ResNet stem + 3x3/2 max pooling);
@@ -1071,6 +1131,13 @@ class Net:
         """a SaberResize inside the op list (saber_hip_net_add_resize), named resize:<algo>"""
         self.keep.append(resize)
         return self._chk(L.load().saber_hip_net_add_resize(self.h, resize.h, self.tid(x), self.tid(y)))
+
+    def add_detout(self, detout, loc, conf, prior, y, count):
+        """a SaberDetectionOutput inside the op list (saber_hip_net_add_detout), named detout:<algo>. prior is None for an op made with
+        prior=False; count is a tensor of 1 + n four-byte elements (declare it (1 + n,) L.F32 and view it as int32)"""
+        self.keep.append(detout)
+        return self._chk(L.load().saber_hip_net_add_detout(self.h, detout.h, self.tid(loc), self.tid(conf), -1 if prior is None else self.tid(prior),
+                                                           self.tid(y), self.tid(count)))
 
     def add_softmax(self, rows, cols, x, y):
         return self._chk(L.load().saber_hip_net_add_softmax(self.h, rows, cols, self.tid(x), self.tid(y)))

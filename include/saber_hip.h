@@ -438,6 +438,62 @@ int saber_hip_resize_set_tile(saber_hip_resize_t* op, int form);
 int saber_hip_resize_get_tile(const saber_hip_resize_t* op);
 void saber_hip_resize_destroy(saber_hip_resize_t* op);
 
+/* ------------------------------------------------------------------------------------------- */
+/* DetectionOutput (DetectionOutput<T,D>: saber/funcs/detection_output.h; x86: saber_detection_output.cpp, detection_helper.cpp), FP32 only */
+/* ------------------------------------------------------------------------------------------- */
+/* Box decode, per-class non-maximum suppression and the per-image keep_top_k cut, all on the device with a FIXED-SHAPE output, so the
+ * operator can be part of a captured pass (the reference's GPU route runs nms_detect on the host between two copies and a stream
+ * synchronisation). Inputs, f32:
+ *   has_prior = 1 (SSD):  loc [n, priors * 4] predictions; conf [n, priors, classes] (what saber_hip_softmax_f32 writes over n * priors
+ *                         rows; read with stride `classes`, no permute pass); prior [2, priors * 4]: the boxes, then the variances
+ *   has_prior = 0:        loc [n, priors * 4] decoded boxes; conf [n, classes, priors]; prior is NULL (the reference's two-input path)
+ * Decode: the reference's six decode_bbox_* functions, code_type 1 CORNER, 2 CENTER_SIZE, 3 CORNER_SIZE (CodeType), with and without
+ * variance_in_target; every product, sum and quotient rounded to float32; CENTER_SIZE's exp is the double exponential rounded to float
+ * once. Only the boxes NMS looks at are decoded.
+ * Per image and class other than background_id (-1: none): the priors with score > conf_thresh (a NaN is no candidate), by score
+ * descending and index ascending, cut to nms_top_k; greedy NMS in that order: a candidate is kept if jaccard_overlap(candidate, kept) <=
+ * the adaptive threshold for every box kept before it (float32; an inverted box has size 0; 0 / 0 = NaN fails and suppresses); after a keep
+ * the threshold is multiplied by nms_eta while nms_eta < 1 and the threshold > 0.5. Per image: where more than keep_top_k boxes were kept,
+ * the first keep_top_k by score descending, label ascending, index ascending.
+ * Output: y f32 [n * keep_top_k, 7], rows [image, label, score, xmin, ymin, xmax, ymax] (score and box copied bits) by image ascending,
+ * label ascending, score descending, index ascending, packed from row 0; every later row is seven times -1.0f (so an empty result shows the
+ * reference's single row of -1 in row 0). count int32 [1 + n]: the total, then the rows per image. Both are written completely by every
+ * run; no memset, no host work, no synchronisation; two launches. The op owns its scratch: create needs no device; the FIRST run (or
+ * saber_hip_net_add_detout) allocates and clears it and sets the kernels' LDS attribute, which are not stream operations - a caller who
+ * captures a stream of its own must have run the op once (or added it to a net) before hipStreamBeginCapture.
+ * Kernels (anakin_amd/csrc/detout.hip), bit-identical to each other:
+ *   form 0 "detout_direct_f32": every accepted descriptor; candidates one after the other, the lanes testing against the kept list;
+ *   form 1 "detout_mask_f32":   nms_eta == 1 only; the survivors' suppression relation as a bit matrix, one wave walks it.
+ * One workgroup sorts 4096 keys at a time and carries the running top nms_top_k from chunk to chunk: any number of priors.
+ * SABER_HIP_UNIMPL (with a saber_hip_last_error text): dtype other than SABER_HIP_F32; share_location = 0 (the two-stage path with
+ * sequence offsets); keep_top_k < 1; nms_top_k outside 1 .. 1024; keep_top_k in 3073 .. classes * nms_top_k - 1 (the per-image cut
+ * selects in LDS; from classes * nms_top_k on no image can exceed it). SABER_HIP_INVALID_VALUE: a non-positive size, an unknown code_type,
+ * background_id outside -1 .. classes - 1, nms_eta outside (0, 1], sizes whose products pass 2^31.
+ * set_tile takes a form code; a code the op is not eligible for returns SABER_HIP_INVALID_VALUE and changes nothing. */
+typedef struct {
+    int n, classes, priors;
+    int code_type;
+    int variance_in_target;
+    int has_prior;
+    int share_location;
+    int background_id;
+    int keep_top_k, nms_top_k;
+    float conf_thresh, nms_thresh, nms_eta;
+    int dtype;
+} saber_hip_detout_desc;
+typedef struct saber_hip_detout saber_hip_detout_t;
+int saber_hip_detout_create(const saber_hip_detout_desc* desc, saber_hip_detout_t** out);
+int saber_hip_detout_out_rows(const saber_hip_detout_t* op);      /* n * keep_top_k */
+int saber_hip_detout_run(saber_hip_detout_t* op, const void* loc, const void* conf, const void* prior_or_null, void* y, void* count,
+                         saber_hip_stream_t stream);
+/* The host's read of the total (count[0]) for a caller that wants the reference's variable-shape result: a four-byte copy on `stream` and
+ * one synchronisation of it. Not part of a captured pass; refused while an op-list capture records. */
+int saber_hip_detout_read_total(const void* count, saber_hip_stream_t stream, int* total);
+const char* saber_hip_detout_algo(const saber_hip_detout_t* op);
+int saber_hip_detout_set_tile(saber_hip_detout_t* op, int form);
+int saber_hip_detout_get_tile(const saber_hip_detout_t* op);
+void saber_hip_detout_destroy(saber_hip_detout_t* op);
+
 /* XCD-resident stage: a run of INT8 convolutions over SMALL feature maps (h * w <= 64 pixels per image: ResNet's res5) as
  * ONE persistent launch. Image i is computed entirely on XCD i % 8 (32 CUs, one workgroup each); the convolutions
  * ("phases") follow each other inside the kernel, separated by an XCD-local barrier where one reads what an earlier one
@@ -815,6 +871,12 @@ int saber_hip_net_add_deconv(saber_hip_net_t* net, saber_hip_deconv_t* op, int i
  * SABER_HIP_NET_REPRODUCIBLE_FP32 too: all forms compute the same bits - and saber_hip_net_get_choice / _set_choice carry the form code as
  * (19 << 16) | form, bit 8 set while the op's resize + sum site is on. The handle must outlive the net. */
 int saber_hip_net_add_resize(saber_hip_net_t* net, saber_hip_resize_t* op, int in_id, int out_id);
+/* saber_hip_detout_run inside an op list, named detout:<algo>. prior_id is -1 for an op created with has_prior = 0. The arena planner sees
+ * the three inputs and both outputs (y: n * keep_top_k * 7 floats, count: 1 + n int32); the scratch is the op's own. saber_hip_net_op_work,
+ * capture / replay, the op-list capture and saber_hip_net_run_op see it; saber_hip_net_autotune times every form the op accepts - under
+ * SABER_HIP_NET_REPRODUCIBLE_FP32 too: the forms compute the same bits - and saber_hip_net_get_choice / _set_choice carry the form code as
+ * (20 << 16) | form. No saber_hip_net_optimize rewrite touches it. The handle must outlive the net. */
+int saber_hip_net_add_detout(saber_hip_net_t* net, saber_hip_detout_t* op, int loc_id, int conf_id, int prior_id, int y_id, int count_id);
 /* Caller-owned storage for tensor `id` instead of a slot of the net's arena (the net's inputs and outputs when the caller
  * has buffers of its own: the reference's Net owns its edge tensors). Before finalize any tensor can be bound (ptr != NULL)
  * or returned to the arena (NULL); after finalize only the address of an already external tensor can change. A captured

@@ -10,7 +10,7 @@
 //   SoftmaxParam                                         saber/saber_funcs_param.h:48-110,470-677,1077-1140,1236-1279,2085-2153
 //   ImplBase<T, Op, Param>                               saber/funcs/impl/impl_base.h:33-69
 //   SaberConv2D / SaberConvEltwise / SaberConv2DPooling / SaberFc / SaberPooling / SaberEltwise / SaberSoftmax /
-//   SaberActivation / SaberConcat / SaberDeconv2D / SaberResize <MI355X, OpDtype>, Gemm<MI355X>      the per-target specialisations of saber/funcs/impl/<target>/
+//   SaberActivation / SaberConcat / SaberDeconv2D / SaberResize / SaberDetectionOutput <MI355X, OpDtype>, Gemm<MI355X>      the per-target specialisations of saber/funcs/impl/<target>/
 // As in the reference, weights and bias are TENSORS OF THE TARGET (device memory here); the implementations copy them to
 // the host once per init (saber_mi355x_impl.h: mi355x_host_view). HostBlob below is a convenience that builds such a tensor
 // from host data.
@@ -39,6 +39,7 @@ enum ActiveType { Active_unknow = 0, Active_sigmoid = 1, Active_relu = 2, Active
 enum EltwiseType { Eltwise_unknow = 0, Eltwise_prod = 1, Eltwise_sum = 2, Eltwise_max = 3 };
 enum PoolingType { Pooling_unknow = 0, Pooling_max = 1, Pooling_average_include_padding = 2,
                    Pooling_average_exclude_padding = 3 };   // saber_types.h:305-311
+enum CodeType { CORNER = 1, CENTER_SIZE = 2, CORNER_SIZE = 3 };   // saber_types.h:328-332
 enum ResizeType { BILINEAR_ALIGN = 0, BILINEAR_NO_ALIGN = 1, RESIZE_CUSTOM = 2, NEAREST_ALIGN = 3 };   // saber_types.h:362-367
 
 inline size_t type_bytes(DataType t) { return t == AK_FLOAT || t == AK_INT32 ? 4 : 1; }
@@ -102,8 +103,8 @@ private:
 template <typename TargetType>
 class Tensor {
 public:
-    Tensor() : _dtype(AK_FLOAT), _data(nullptr), _bytes(0) {}
-    Tensor(const Shape& s, DataType t = AK_FLOAT) : _dtype(AK_FLOAT), _data(nullptr), _bytes(0) { re_alloc(s, t); }
+    Tensor() : _dtype(AK_FLOAT), _data(nullptr), _bytes(0), _cap(0) {}
+    Tensor(const Shape& s, DataType t = AK_FLOAT) : _dtype(AK_FLOAT), _data(nullptr), _bytes(0), _cap(0) { re_alloc(s, t); }
     ~Tensor() {
         if (_data) (void)hipFree(_data);
     }
@@ -115,7 +116,15 @@ public:
         _dtype = t;
         _bytes = (size_t)s.count() * type_bytes(t);
         _data = nullptr;
+        _cap = 0;
         if (_bytes && hipMalloc(&_data, _bytes) != hipSuccess) return SaberOutOfMem;
+        _cap = _bytes;
+        return SaberSuccess;
+    }
+    SaberStatus reshape(const Shape& s) {      // Tensor::reshape: the buffer stays where the new shape fits into it
+        if ((size_t)s.count() * type_bytes(_dtype) > _cap) return re_alloc(s, _dtype);
+        _shape = s;
+        _bytes = (size_t)s.count() * type_bytes(_dtype);
         return SaberSuccess;
     }
     const void* data() const { return _data; }
@@ -147,6 +156,7 @@ private:
     DataType _dtype;
     void* _data;
     size_t _bytes;
+    size_t _cap;      // the allocation; _bytes follows reshape
     std::vector<float> _scale;
 };
 
@@ -291,6 +301,22 @@ struct ResizeParam {   // saber_funcs_param.h:2509-2549: the type, the two scale
     ResizeType resize_type;
 };
 
+template <typename TargetType>
+struct DetectionOutputParam {   // saber_funcs_param.h:947-1034
+    DetectionOutputParam() : share_location(true), variance_encode_in_target(false), class_num(0), background_id(0), keep_top_k(-1), type(CORNER),
+                             conf_thresh(0.f), nms_top_k(-1), nms_thresh(0.3f), nms_eta(1.f) {}
+    DetectionOutputParam(int classes, int bg_id, int keep_topk, int nms_topk, float nms_threshold, float confidence_threshold, bool share_loc = true,
+                         bool variance_in_target = false, int codetype = 1, float eta = 1.f)
+        : share_location(share_loc), variance_encode_in_target(variance_in_target), class_num(classes), background_id(bg_id), keep_top_k(keep_topk),
+          type((CodeType)codetype), conf_thresh(confidence_threshold), nms_top_k(nms_topk), nms_thresh(nms_threshold), nms_eta(eta) {}
+    bool share_location, variance_encode_in_target;
+    int class_num, background_id, keep_top_k;
+    CodeType type;
+    float conf_thresh;
+    int nms_top_k;
+    float nms_thresh, nms_eta;
+};
+
 }  // namespace saber
 }  // namespace anakin
 
@@ -351,6 +377,8 @@ template <typename TargetType, DataType OpDtype>
 using SaberDeconv2D = SaberDeconv2DMI355X<TargetType, OpDtype>;
 template <typename TargetType, DataType OpDtype>
 using SaberResize = SaberResizeMI355X<TargetType, OpDtype>;
+template <typename TargetType, DataType OpDtype>
+using SaberDetectionOutput = SaberDetectionOutputMI355X<TargetType, OpDtype>;
 template <typename TargetType, DataType OpDtype>
 using SaberActivation = SaberActivationMI355X<TargetType, OpDtype>;
 template <typename TargetType>

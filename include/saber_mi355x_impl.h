@@ -578,6 +578,86 @@ private:
     saber_hip_resize_t* _op;
 };
 
+// SaberDetectionOutput<MI355X, AK_FLOAT> (saber/funcs/detection_output.h; x86: saber_detection_output.cpp). inputs: loc [N, P * 4], conf and -
+// SSD - the prior boxes [1, 2, P * 4]; with three inputs conf is [N, P, C] (the softmax's output, read with stride C: no permute pass), with
+// two loc holds decoded boxes and conf is [N, C, P] (the reference's multiclass_nms path). The output tensor has the shape
+// DetectionOutput::compute_output_shape gives it, {1, 1, N * keep_top_k, 7}: that is its CAPACITY. The device writes the kept rows from row 0
+// and -1 rows behind them, and the totals into a count tensor the op owns (count_tensor(): int32 [1 + N]).
+// dispatch OUTSIDE an op-list capture then reads the four-byte total (one stream synchronisation) and reshapes the output to
+// {1, 1, total, 7} - {1, 1, 1, 7}, a row of -1, when nothing was kept - as the reference does. WHILE saber_hip_capture_active() it records
+// the op, reads nothing back and leaves the capacity shape with its -1 rows: a replayed pass has no host step.
+// share_location = false, keep_top_k < 1, nms_top_k outside 1 .. 1024 and OpDtype other than AK_FLOAT: SaberUnImplError.
+template <typename TargetType, DataType OpDtype>
+class SaberDetectionOutputMI355X : public ImplBase<TargetType, OpDtype, DetectionOutputParam<TargetType> > {
+public:
+    SaberDetectionOutputMI355X() : _op(nullptr), _rows(0) {}
+    ~SaberDetectionOutputMI355X() {
+        if (_op) saber_hip_detout_destroy(_op);
+    }
+    virtual SaberStatus init(const std::vector<Tensor<TargetType>*>& inputs, std::vector<Tensor<TargetType>*>& outputs,
+                             DetectionOutputParam<TargetType>& param, Context<TargetType>& ctx) {
+        this->_ctx = &ctx;
+        return create(inputs, outputs, param, ctx);
+    }
+    virtual SaberStatus create(const std::vector<Tensor<TargetType>*>& inputs, std::vector<Tensor<TargetType>*>& outputs,
+                               DetectionOutputParam<TargetType>& param, Context<TargetType>& ctx) {
+        this->_ctx = &ctx;
+        if (OpDtype != AK_FLOAT || inputs.size() < 2 || inputs.size() > 3) return SaberUnImplError;
+        Tensor<TargetType>* loc = inputs[0];
+        Tensor<TargetType>* conf = inputs[1];
+        saber_hip_detout_desc d;
+        memset(&d, 0, sizeof d);
+        d.n = loc->num();
+        if (d.n <= 0 || loc->valid_size() % (4LL * d.n)) return SaberInvalidValue;
+        d.priors = (int)(loc->valid_size() / (4LL * d.n));
+        d.classes = param.class_num > 0 ? param.class_num : (int)(conf->valid_size() / ((long long)d.n * d.priors));
+        if ((long long)d.n * d.priors * d.classes != conf->valid_size()) return SaberInvalidValue;
+        d.has_prior = inputs.size() == 3;
+        if (d.has_prior && inputs[2]->valid_size() != 8LL * d.priors) return SaberInvalidValue;
+        d.code_type = (int)param.type;
+        d.variance_in_target = param.variance_encode_in_target;
+        d.share_location = param.share_location;
+        d.background_id = param.background_id;
+        d.keep_top_k = param.keep_top_k; d.nms_top_k = param.nms_top_k;
+        d.conf_thresh = param.conf_thresh; d.nms_thresh = param.nms_thresh; d.nms_eta = param.nms_eta;
+        d.dtype = loc->get_dtype() == AK_FLOAT && conf->get_dtype() == AK_FLOAT ? SABER_HIP_F32 : mi355x_dtype(AK_INT8);
+        if (_op) { saber_hip_detout_destroy(_op); _op = nullptr; }
+        int rc = saber_hip_detout_create(&d, &_op);
+        if (rc) return mi355x_status(rc);
+        _rows = saber_hip_detout_out_rows(_op);
+        // the output must HOLD the capacity (a dispatch before may have reshaped it to fewer rows: reshape brings it back); an op whose
+        // output cannot is not left behind for dispatch to find
+        if (outputs[0]->reshape(Shape({1, 1, _rows, 7}, Layout_NCHW)) != SaberSuccess || outputs[0]->valid_size() != 7LL * _rows) {
+            saber_hip_detout_destroy(_op);
+            _op = nullptr;
+            return SaberInvalidValue;
+        }
+        return _count.re_alloc(Shape({1, 1, 1, 1 + d.n}, Layout_NCHW), AK_INT32);
+    }
+    virtual SaberStatus dispatch(const std::vector<Tensor<TargetType>*>& inputs, std::vector<Tensor<TargetType>*>& outputs,
+                                 DetectionOutputParam<TargetType>& param) {
+        if (!_op) return SaberNotInitialized;      // (a failed create() is not reported by BaseFunc::init: see SaberConvEltwiseMI355X::dispatch)
+        saber_hip_stream_t s = (saber_hip_stream_t)this->_ctx->get_compute_stream();
+        const bool recording = saber_hip_capture_active() != 0;
+        if (!recording) outputs[0]->reshape(Shape({1, 1, _rows, 7}, Layout_NCHW));      // back to the capacity a run before may have shrunk
+        int rc = saber_hip_detout_run(_op, inputs[0]->data(), inputs[1]->data(), inputs.size() == 3 ? inputs[2]->data() : nullptr,
+                                      outputs[0]->mutable_data(), _count.mutable_data(), s);
+        if (rc || recording) return mi355x_status(rc);
+        int total = 0;
+        if ((rc = saber_hip_detout_read_total(_count.data(), s, &total)) != 0) return mi355x_status(rc);
+        outputs[0]->reshape(Shape({1, 1, total > 0 ? total : 1, 7}, Layout_NCHW));
+        return SaberSuccess;
+    }
+    const char* algo() const { return _op ? saber_hip_detout_algo(_op) : ""; }
+    int set_tile(int form) { return _op ? saber_hip_detout_set_tile(_op, form) : SABER_HIP_INVALID_VALUE; }
+    Tensor<TargetType>& count_tensor() { return _count; }
+
+private:
+    saber_hip_detout_t* _op;
+    int _rows;
+    Tensor<TargetType> _count;
+};
+
 // Concat<MI355X, OpDtype> (saber/funcs/concat.h; x86: saber_concat.cpp) along the channel axis of 1 .. 8 tensors of one dtype:
 // NHWC (axis 3: the 8-bit edges and the target's FP32 edges) or any layout whose pixels collapse to one (NCHW [n, c, 1, 1], axis 1).
 // f32 and s8: a copy. u8: the x86 create's loops as they are written (saber_concat.cpp:163-201) - scale_max starts at the first

@@ -16,3 +16,4 @@ template class anakin::saber::SaberConcatMI355X<X86, AK_INT8>;
 template class anakin::saber::SaberConcatMI355X<X86, AK_FLOAT>;
 template class anakin::saber::SaberDeconv2DMI355X<X86, AK_FLOAT>;
 template class anakin::saber::SaberResizeMI355X<X86, AK_FLOAT>;
+template class anakin::saber::SaberDetectionOutputMI355X<X86, AK_FLOAT>;

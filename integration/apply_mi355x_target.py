@@ -37,7 +37,7 @@ The framework half of the manual (:281-455) is applied to a copy of `framework/`
     framework/model_parser/parser/parser.cpp replaced by integration/mi355x/framework/text_model_parser.cpp (protobuf is absent and this
                                              is its only consumer): Graph::load(path) reads a TEXT model - the network as original
                                              operators + raw weight blobs - and builds the graph with Graph::AddOp / AddOpAttr / Freeze
-    + the facade ladders of saber/funcs/{pooling,eltwise,fc,softmax,activation,conv_pooling,gemm,concat,deconv,resize}.h"""
+    + the facade ladders of saber/funcs/{pooling,eltwise,fc,softmax,activation,conv_pooling,gemm,concat,deconv,resize,detection_output}.h"""
 import os
 import shutil
 import sys
@@ -230,7 +230,7 @@ def main(ref, final_dst):
     for facade, impl in (("pooling", "saber_pooling"), ("eltwise", "saber_eltwise"), ("fc", "saber_fc"),
                          ("softmax", "saber_softmax"), ("activation", "saber_activation"),
                          ("conv_pooling", "saber_conv_pooling"), ("concat", "saber_concat"), ("deconv", "saber_deconv"),
-                         ("resize", "saber_resize")):
+                         ("resize", "saber_resize"), ("detection_output", "saber_detection_output")):
         insert(os.path.join(S, "funcs", facade + ".h"), "namespace anakin",
                "#ifdef USE_MI355X_PLACE\n#include \"saber/funcs/impl/mi355x/%s.h\"\n#endif\n\n" % impl, after=False)
     # gemm.h includes its targets' specialisations at the END of the file (gemm.h:95-105)
@@ -239,7 +239,7 @@ def main(ref, final_dst):
     for subdir, names in (("core", ("mi355x_target_wrapper.h", "mi355x_impl.cpp")),
                           ("funcs", ("saber_conv.h", "saber_conv_eltwise.h", "mi355x_timer.h", "saber_pooling.h",
                                      "saber_eltwise.h", "saber_fc.h", "saber_softmax.h", "saber_activation.h",
-                                     "saber_conv_pooling.h", "saber_gemm.h", "saber_concat.h", "saber_deconv.h", "saber_resize.h"))):
+                                     "saber_conv_pooling.h", "saber_gemm.h", "saber_concat.h", "saber_deconv.h", "saber_resize.h", "saber_detection_output.h"))):
         d = os.path.join(S, subdir, "impl", "mi355x")
         os.makedirs(d, exist_ok=True)
         for n in names:
